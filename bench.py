@@ -12,25 +12,33 @@ synthetic root scenes, inputs resident in HBM.  Workload = BASELINE.json configs
         --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 10        # what the driver does; same line
 
 Prints ONE JSON line on rank 0.  `value` counts reference-equivalent ValueEstimator forwards
-(249 per root for D=2,w=2) completed per second over all ranks.  Multi-GPU:
-roots are sharded and each step ends with the one real exchange of the path, an RCCL all-gather
-of the per-shard (action, value) rows.  Scaling readings (`--scaling`):
+(249 per root for D=2,w=2) completed per second over all ranks; `ms_per_step` is the wall-clock time of
+one of the --steps timed steps.  Multi-GPU: roots are sharded and each step ends with the one real exchange of the path,
+an RCCL all-gather of the per-shard (action, value) rows.  Scaling readings (`--scaling`):
 
     both   (default)  N = 1: the workload as is (reported as "weak": nothing is split).  N > 1: `value` is the
                       FIXED-TOTAL reading SURVEY.md §8(d) prescribes (--roots roots in total, split contiguously over
-                      the ranks: "scaling": "strong"), and the same invocation also times --roots roots PER GPU and
-                      reports it as `weak_value` / `weak_ms_per_step`.
+                      the ranks: "scaling": "strong"); with --full the same invocation also times --roots roots PER GPU
+                      and reports it as `weak_value` / `weak_ms_per_step`.
     weak              --roots R roots PER GPU: per-GPU work fixed as N grows
     strong            --total-roots T roots in total, split contiguously over the ranks
                       (BASELINE configs[3]: --scaling strong --total-roots 4096 --depth 3;
                        configs[4]: --scaling strong --total-roots 2048 --humans 49 --layers 3 --contraction f16)
 
-With more than one rank the line also carries `multi_gpu`: every rank's search time per step and the exchange time per
-step, measured separately (un-pipelined) after the timed region, and `ranks_seen` = dist.get_world_size().
+A plain run does only what the headline needs: set-up, --warmup untimed steps, the --steps timed steps, the outputs of the
+last timed step if --dump-outputs is given, and the line.  `--full` adds everything else the line used to carry, each
+measured after the timed region: `step_ms_device` (HIP events between steps, a second pass of the same steps: against
+`ms_per_step` it shows whether the host is the limiter) and `step_ms_device_cold`, `roofline` / `roofline_step`, the
+`f32_mfma_line` beside a bf16x6 `value`, `cpu_baseline` (--cpu-seconds), `decisions` (digests of one more gathered step)
+and, with more than one rank, `multi_gpu` (every rank's search and exchange time per step, un-pipelined) and the per-GPU
+reading of `--scaling both`.  With more than one rank the line carries `ranks_seen` = dist.get_world_size() either way.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned for all roots, in root order,
+as DIR/best_action.npy and DIR/best_value.npy (float32; action indices are exact).  The scenes are seeded, so the same
+arguments give the same inputs in every run and two builds can be compared output for output.
 
 `--graph auto|on|off`: replay the rank's whole search from a captured hipGraph (auto: depth-1 searches of <= 512 roots per rank,
-the one case where it measured faster); `step_ms_device` (HIP events between steps) against `ms_per_step` (wall clock) shows
-whether the host is the limiter.
+the one case where it measured faster).
 
 RGL_BENCH_STUB_SEARCH=1 replaces the device search by a trivial CPU function over gloo: a test switch for the launcher
 and the exchange logic on machines without GPUs (tests/test_bench_launcher.py).  The line it prints says so and is not a
@@ -282,8 +290,16 @@ def parse_args(argv=None):
                          "uniform draw")
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="replay the rank's search from a captured hipGraph (auto: depth-1 searches of <= 512 roots per rank)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (0 = skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg of --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: per-step device "
+                         "times, roofline, the f32-MFMA line, the CPU baseline, decision digests, multi-GPU diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (best_action, best_value of every root) to DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -361,7 +377,7 @@ class Leg:
                 self.graphs[a.data_ptr()] = (g, out)
             self.single = targets[0]
             self.graph_last = self.graphs[targets[0][0].data_ptr()][1]["last"]
-        self.pending = None
+        self.pending = self.last = self.outputs = None
 
     # the two shapes ShardedRollout calls the rank's search in
     def _search_fn(self, r, h):
@@ -384,7 +400,7 @@ class Leg:
         nxt = self.sharded.launch_local(self.robot, self.humans, self.total_roots)
         if self.pending is not None and EXCHANGE_DIAG != "nowait":
             self.pending.wait()              # exchange of the previous step complete (stream-ordered); .result() unpacks
-        self.pending = nxt
+        self.pending = self.last = nxt
 
     def drain(self):
         if self.pending is not None:
@@ -399,13 +415,15 @@ class Leg:
         if not STUB:
             torch.cuda.synchronize()
 
-    def timed(self, steps, warmup, init_steps):
+    def timed(self, steps, warmup, init_steps, full=True, keep_outputs=False):
         """`init_steps` set-up steps (code objects, workspace, RCCL channels), `warmup` untimed steps, then exactly `steps`
-        timed steps between fences; returns (wall seconds MAX over ranks, sorted per-step device ms of this rank)."""
+        timed steps between fences; returns (wall seconds MAX over ranks, sorted per-step device ms of this rank, or None
+        unless `full`).  `keep_outputs`: (best_action, best_value) of all roots as the last timed step left them, copied to the
+        host after the timed region, in `self.outputs`."""
         # one event in front of each of the first (up to) 10 set-up steps and one behind the last of them: every event in the list
         # is recorded whatever `init_steps` is (ADVICE r4: with 4..10 set-up steps the last one never was, and elapsed_time raised)
         n_cold = min(init_steps, 10)
-        cold = None if STUB or n_cold == 0 else [torch.cuda.Event(enable_timing=True) for _ in range(n_cold + 1)]
+        cold = None if STUB or n_cold == 0 or not full else [torch.cuda.Event(enable_timing=True) for _ in range(n_cold + 1)]
         t_init = time.perf_counter()
         for i in range(init_steps):
             if cold and i <= n_cold:
@@ -443,10 +461,12 @@ class Leg:
         self.drain()
         self.fence()
         elapsed = time.perf_counter() - t0
+        # before anything else runs: the buffers of a captured search or of the exchange are reused by the next steps
+        self.outputs = (tuple(t.detach().cpu() for t in self.last.result()) if keep_outputs else None)
         # per-step device times: a SECOND pass of the same `steps` steps with a HIP event between them, after the timed region (an
         # event record between two launches is a marker packet the next kernel waits for: measurement, not work -- round 4 took the
         # 21 of them out of the timed steps)
-        marks = None if STUB else [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+        marks = None if STUB or not full else [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
         if marks:
             for i in range(steps):
                 marks[i].record()
@@ -454,7 +474,8 @@ class Leg:
             self.drain()
             marks[steps].record()
             self.fence()
-        step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps)) if marks else [elapsed / steps * 1e3] * steps
+        step_ms = (sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps)) if marks else
+                   [elapsed / steps * 1e3] * steps if full else None)
         if self.dist is not None:
             t = torch.tensor([elapsed], dtype=torch.float64, device=self.device)
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
@@ -631,6 +652,25 @@ def kernel_sources_digest():
     return h.hexdigest()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, best_action, best_value):
+    """--dump-outputs: the last timed step's (best_action, best_value) of every root, in root order, as float32 .npy files.
+    Above DUMP_MAX_BYTES in all, a fixed seeded sample of the roots is written instead, with its root indices (root_index.npy)."""
+    act = best_action.numpy().astype(np.float32)          # action indices < 2^24: exact in float32
+    val = best_value.numpy().astype(np.float32)
+    arrays = {"best_action": act, "best_value": val}
+    per_root = 4 + 4
+    if act.size * per_root > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (per_root + 8)           # 4096: room for the three .npy headers
+        idx = np.sort(np.random.RandomState(0).choice(act.size, keep, replace=False))
+        arrays = {"best_action": act[idx], "best_value": val[idx], "root_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def resolve_contraction(args):
     """`auto` -> the mode that carries `value` for this workload.  bf16x6 (RGL_CONTRACT_BF16X6) keeps every operand at f32's 24
     significand bits and drops <= 2^-23 |w||a| per product in the worst case (~2^-25 typically) -- it is the reference's arithmetic width on another pipe, admitted by the
@@ -708,15 +748,19 @@ def main():
     leg = Leg(args, ts, device, world, rank, main_leg[1], main_leg[2], dist)
     gc.collect()
     gc.freeze()
-    elapsed, step_ms = leg.timed(args.steps, args.warmup, INIT_STEPS)
+    dump = args.dump_outputs is not None and rank == 0
+    elapsed, step_ms = leg.timed(args.steps, args.warmup, INIT_STEPS, full=args.full, keep_outputs=dump)
     per_root = ts.logical_value_evals_per_root()
     total_roots, B = leg.total_roots, leg.B
     value = per_root * total_roots * args.steps / elapsed
-    multi = leg.diagnose() if dist is not None else None
-    digest = leg.decisions_digest()
+    if dump:
+        dump_outputs(args.dump_outputs, *leg.outputs)
+    # everything below the headline: --full only
+    multi = leg.diagnose() if dist is not None and args.full else None
+    digest = leg.decisions_digest() if args.full else None
 
     weak = None
-    if extra_leg is not None:
+    if extra_leg is not None and args.full:
         leg2 = Leg(args, ts, device, world, rank, extra_leg[1], extra_leg[2], dist)
         e2, s2 = leg2.timed(args.steps, args.warmup, INIT_STEPS)
         weak = {"weak_value": per_root * leg2.total_roots * args.steps / e2, "weak_ms_per_step": e2 / args.steps * 1e3,
@@ -727,7 +771,7 @@ def main():
 
     A, W = ts.num_actions, ts.kept_per_node
     roofline = roofline_step = None
-    if not STUB and B > 0:
+    if args.full and not STUB and B > 0:
         if not leg.graphs:                                   # leave the main leg's levels in the shared workspace
             ts.search(leg.robot, leg.humans, roots_are_joint_states=False, want_root_values=False)
         roofline = children_roofline(args, ts, device, N, H, leg.graph_last, leg.robot, leg.humans)
@@ -744,7 +788,8 @@ def main():
 
     # ---- the plain f32-MFMA line beside a bf16x6 `value` ("the f32-MFMA line still printed beside it")
     f32_line, ts32 = None, None
-    if not STUB and world == 1 and args.contraction == "bf16x6" and B > 0 and os.environ.get("RGL_BENCH_NO_F32_LINE") != "1":
+    if (args.full and not STUB and world == 1 and args.contraction == "bf16x6" and B > 0
+            and os.environ.get("RGL_BENCH_NO_F32_LINE") != "1"):
         import copy
         a32 = copy.copy(args)
         a32.contraction = "f32"
@@ -770,12 +815,7 @@ def main():
     result = {
         "metric": ("STUB SEARCH, NOT A MEASUREMENT: " if STUB else "") + metric,
         "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": main_leg[0],
-        "step_ms_device": {"p10": step_ms[len(step_ms) // 10], "median": step_ms[len(step_ms) // 2],
-                           "p90": step_ms[(len(step_ms) * 9) // 10], "note": "rank 0, HIP events between steps, a second pass of the same steps after the timed region"},
-        "step_ms_device_cold": (None if not getattr(leg, "cold_ms", None) else
-                                {"median": leg.cold_ms[len(leg.cold_ms) // 2], "max": leg.cold_ms[-1],
-                                 "note": "set-up steps 2..9 of this process, before the device reached its steady clock (not timed into `value`)"}),
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": main_leg[0], "full": args.full,
         "vs_baseline": None, "dtype": {"f32": "f32", "f16": "f16 inputs / f32 accumulate (middle-layer products only; everything else f32)",
                                        "bf16x6": "f32 (24-bit operands throughout; 13 312 of the 14 224 products of the children kernel's 32 x 32, 32 x 100 and "
                                                  "100 x 100 head matrices, its embedding / graph weight products (w_r's second layer, Wa, W1, W_last) "
@@ -798,10 +838,17 @@ def main():
                    "scenes": "human placement: " + args.scenes,
                    "graph_replay": bool(leg.graphs),
                    "exchange": "all_gather_into_tensor of (roots_per_gpu,2) fp32 per rank" if world > 1 else "none"},
-        "roofline": roofline,
-        "roofline_step": roofline_step,
-        "decisions": digest,
     }
+    if args.full:
+        result.update({
+            "step_ms_device": {"p10": step_ms[len(step_ms) // 10], "median": step_ms[len(step_ms) // 2],
+                               "p90": step_ms[(len(step_ms) * 9) // 10], "note": "rank 0, HIP events between steps, a second pass of the same steps after the timed region"},
+            "step_ms_device_cold": (None if not getattr(leg, "cold_ms", None) else
+                                    {"median": leg.cold_ms[len(leg.cold_ms) // 2], "max": leg.cold_ms[-1],
+                                     "note": "set-up steps 2..9 of this process, before the device reached its steady clock (not timed into `value`)"}),
+            "roofline": roofline,
+            "roofline_step": roofline_step,
+            "decisions": digest})
     if f32_line is not None:
         result["f32_mfma_line"] = f32_line
     if args.contraction == "bf16x6":
@@ -813,7 +860,7 @@ def main():
                      "features 0..95, and (round 6) w_r's 64 x 32 layer, Wa, W1 and W_last in the tile chain and the crowd computation (what the CU's LDS "
                      "holds as three bf16 pieces with w_h's second matrix in registers and the 4 x 4 x 1 fragments stored compact); scene_graph_kernel: "
                      "Wa, W_l, motion head; everything else f32",
-            "float64_check": "cpu_baseline.float64_check of this line (needs --cpu-seconds > 0); "
+            "float64_check": "cpu_baseline.float64_check of this line (needs --full and --cpu-seconds > 0); "
                              "tests/test_gpu_parity.py::test_bf16x6_head_matrix_at_size_and_in_other_shapes asserts it",
             "suite_under_the_mode": "profiles/r06_final_suite_under_bf16x6.txt (RGL_CONTRACT_F32_AS=bf16x6: every f32 search of the GPU suite in this mode)"}
     result["config"]["contraction"] = args.contraction
@@ -824,15 +871,16 @@ def main():
         result.update(weak)
     if multi is not None:
         result["multi_gpu"] = multi
-        result["ranks_seen"] = multi["ranks_seen"]
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not STUB:
+    if dist is not None:
+        result["ranks_seen"] = dist.get_world_size()
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and not STUB:
         dv = {("%s kernels" % args.contraction): ts.search(leg.robot[:64], leg.humans[:64], roots_are_joint_states=False,
                                                            want_root_values=False)["best_value"].clone()}
         if ts32 is not None:
             dv["f32 kernels"] = ts32.search(leg.robot[:64], leg.humans[:64], roots_are_joint_states=False,
                                             want_root_values=False)["best_value"].clone()
         result["cpu_baseline"] = cpu_baseline(args, leg.robot_cpu, leg.humans_cpu, args.cpu_seconds, dv)
-    elif rank == 0:
+    elif args.full and rank == 0:
         result["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -24,7 +24,7 @@ def _run(argv, extra_env=None, launcher=None):
 
 
 def test_bench_launches_its_own_ranks_and_reports_both_readings():
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--roots", "11"])
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--roots", "11", "--full"])
     assert r["stub_search"] is True and r["metric"].startswith("STUB SEARCH")
     assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["steps"] == 4 and r["warmup"] == 1
     # `value`: the fixed-total reading -- 11 roots split 6 + 5
@@ -50,14 +50,14 @@ def test_eight_ranks_uneven_shards_and_the_single_process_decisions():
             (["--roots", "2048"], 2048, [256] * 8),
             (["--scaling", "strong", "--total-roots", "4096", "--depth", "3"], 4096, [512] * 8),
             (["--scaling", "strong", "--total-roots", "2051"], 2051, [257] * 3 + [256] * 5)):
-        r8 = _run(["--gpus", "8", "--steps", "2", "--warmup", "1"] + argv)
+        r8 = _run(["--gpus", "8", "--steps", "2", "--warmup", "1", "--full"] + argv)
         assert r8["n_gpus"] == 8 and r8["ranks_seen"] == 8 and r8["scaling"] == "strong"
         assert r8["config"]["total_roots"] == total and r8["multi_gpu"]["roots_per_rank"] == per_rank
         assert sum(r8["multi_gpu"]["roots_per_rank"]) == total
         assert len(r8["multi_gpu"]["search_ms_per_step_by_rank"]) == 8 and len(r8["multi_gpu"]["exchange_ms_per_step_by_rank"]) == 8
         assert r8["decisions"]["roots"] == total
         one = ["--scaling", "strong", "--total-roots", str(total)] + (["--depth", "3"] if "--depth" in argv else [])
-        r1 = _run(["--gpus", "1", "--steps", "2", "--warmup", "1"] + one)
+        r1 = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"] + one)
         assert r1["n_gpus"] == 1 and r1["config"]["total_roots"] == total and "multi_gpu" not in r1
         assert r1["decisions"] == r8["decisions"], (argv, r1["decisions"], r8["decisions"])
         if argv[0] == "--roots":                      # `both`: the per-GPU-fixed reading rides along (2048 roots on each of 8 ranks)
@@ -65,11 +65,11 @@ def test_eight_ranks_uneven_shards_and_the_single_process_decisions():
 
 
 def test_single_rank_line_keeps_its_shape():
-    r = _run(["--steps", "3", "--warmup", "1", "--roots", "7"])
+    r = _run(["--steps", "3", "--warmup", "1", "--roots", "7", "--full"])
     assert r["n_gpus"] == 1 and r["scaling"] == "weak" and r["config"]["total_roots"] == 7 and "weak_value" not in r
     assert "multi_gpu" not in r and "ranks_seen" not in r
     assert r["config"]["init_steps"] >= 40 and r["config"]["init_ms"] == 80.0
-    short = _run(["--steps", "3", "--warmup", "1", "--roots", "7"], extra_env={"RGL_BENCH_INIT_MS": "0", "RGL_BENCH_INIT_STEPS": "3"})
+    short = _run(["--steps", "3", "--warmup", "1", "--roots", "7", "--full"], extra_env={"RGL_BENCH_INIT_MS": "0", "RGL_BENCH_INIT_STEPS": "3"})
     assert short["config"]["init_steps"] == 3 and short["decisions"] == r["decisions"]
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "step_ms_device", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "decisions"):
@@ -79,10 +79,10 @@ def test_single_rank_line_keeps_its_shape():
 def test_the_drivers_torchrun_command_gives_the_same_multi_rank_line():
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                 "127.0.0.1", "--master-port", "29541"]
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--roots", "8", "--scaling", "strong", "--total-roots", "9"],
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--roots", "8", "--scaling", "strong", "--total-roots", "9", "--full"],
              launcher=launcher)
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["multi_gpu"]["roots_per_rank"] == [5, 4] and "weak_value" not in r
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--roots", "8", "--scaling", "weak"], launcher=launcher)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--roots", "8", "--scaling", "weak", "--full"], launcher=launcher)
     assert r["scaling"] == "weak" and r["config"]["total_roots"] == 16 and r["multi_gpu"]["roots_per_rank"] == [8, 8]
 
 
@@ -107,3 +107,59 @@ def test_clearance_scenes():
     assert (r2 == robot).all() and (h2 == humans).all()                       # seeded
     r3, h3 = bench.synth_scenes(1000, 64, 19, "uniform")                      # the round-1/2 generator: same robots
     assert (r3 == robot).all() and not (h3 == humans).all()
+
+
+def test_plain_line_carries_the_headline_and_nothing_measured_beside_it():
+    """Without --full the run is set-up, warm-up, exactly --steps timed steps and the line: the headline keys keep their meaning,
+    the measurements and checks of --full are not made."""
+    r = _run(["--steps", "5", "--warmup", "2", "--roots", "7"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "scaling", "config"):
+        assert key in r, key
+    assert r["full"] is False and r["steps"] == 5 and r["warmup"] == 2 and r["unit"] == "evals/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 249 * 7 * 5 / (r["ms_per_step"] * 5e-3)) < 1e-6 * r["value"]
+    for key in ("step_ms_device", "step_ms_device_cold", "roofline", "roofline_step", "decisions", "cpu_baseline",
+                "f32_mfma_line", "multi_gpu", "ranks_seen"):
+        assert key not in r, key
+    r2 = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--roots", "11"])
+    assert r2["n_gpus"] == 2 and r2["ranks_seen"] == 2 and r2["scaling"] == "strong" and r2["config"]["total_roots"] == 11
+    assert "weak_value" not in r2 and "multi_gpu" not in r2 and "decisions" not in r2
+
+
+def test_dump_outputs_hold_every_roots_result_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: best_action / best_value of all roots in root order, float32, from the seeded scenes -- the same with one
+    rank and with the roots split over two, and what the search returns for those scenes."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    one, two = str(tmp_path / "one"), str(tmp_path / "two")
+    _run(["--steps", "3", "--warmup", "1", "--scaling", "strong", "--total-roots", "9", "--dump-outputs", one])
+    _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--scaling", "strong", "--total-roots", "9", "--dump-outputs", two])
+    robot, humans = bench.synth_scenes(1000, 9, 19)
+    want = bench._StubSearch(2).search(robot, humans)
+    for d in (one, two):
+        assert sorted(os.listdir(d)) == ["best_action.npy", "best_value.npy"]
+        act, val = np.load(os.path.join(d, "best_action.npy")), np.load(os.path.join(d, "best_value.npy"))
+        assert act.dtype == np.float32 and val.dtype == np.float32 and act.shape == val.shape == (9,)
+        assert np.array_equal(act, want["best_action"].numpy().astype(np.float32))
+        assert np.array_equal(val, want["best_value"].numpy())
+
+
+def test_dump_outputs_sample_a_large_output_under_the_size_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 800)
+    act = torch.arange(1000, dtype=torch.int32) % 81
+    val = torch.linspace(-1, 1, 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), act, val)
+    files = {f: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(files) == ["best_action.npy", "best_value.npy", "root_index.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= bench.DUMP_MAX_BYTES
+    idx = files["root_index.npy"].astype(np.int64)
+    assert idx.size == 50 and (np.diff(idx) > 0).all()
+    assert np.array_equal(files["best_action.npy"], act.numpy()[idx].astype(np.float32))
+    assert np.array_equal(files["best_value.npy"], val.numpy()[idx])
+    for f in files:                                                        # a fixed sample: the same roots every time
+        assert np.array_equal(files[f], np.load(str(tmp_path / "b" / f)))

@@ -2523,7 +2523,7 @@ def test_bench_runs_under_torchrun_over_rccl(dev):
     env = dict(os.environ, RGL_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--scaling", "strong", "--total-roots", "96", "--depth", "3", "--cpu-seconds", "0"]
+           "--scaling", "strong", "--total-roots", "96", "--depth", "3", "--cpu-seconds", "0", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
@@ -2531,6 +2531,34 @@ def test_bench_runs_under_torchrun_over_rccl(dev):
     assert r["scaling"] == "strong" and r["n_gpus"] == 1 and r["config"]["total_roots"] == 96
     assert r["multi_gpu"]["roots_per_rank"] == [96] and r["multi_gpu"]["exchange_ms_per_step_slowest_rank"] >= 0.0
     assert r["value"] > 0 and r["roofline"]["frac"] > 0
+
+
+@pytest.mark.parametrize("depth", [2, 1])
+def test_bench_dump_outputs_are_what_the_search_returns(depth, dev, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run): the last timed step's actions and values of every root, in root order, are
+    those of one search of bench.py's own seeded scenes in the mode it reports in.  Depth 2 runs the direct C-ABI call, depth 1
+    (<= 512 roots) the replay of a captured hipGraph, whose outputs sit in fixed buffers."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--roots", "64",
+           "--depth", str(depth), "--dump-outputs", d]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
+    r = json.loads(lines[0])
+    assert r["full"] is False and r["steps"] == 3 and r["config"]["graph_replay"] == (depth == 1) and "roofline" not in r
+    assert r["config"]["contraction"] == "bf16x6"
+    act, val = np.load(os.path.join(d, "best_action.npy")), np.load(os.path.join(d, "best_value.npy"))
+    assert act.dtype == np.float32 and val.dtype == np.float32 and act.shape == val.shape == (64,)
+    pol = _bench_policy(2, depth, 19, "bf16x6", dev)
+    robot, humans = bench.synth_scenes(1000, 64, 19)
+    o = pol.tree_search().search(robot.to(dev), humans.to(dev), roots_are_joint_states=False, want_root_values=False)
+    assert np.array_equal(act, o["best_action"].cpu().numpy().astype(np.float32))
+    close(val, o["best_value"].cpu().numpy(), reg=REG_F32)
 
 
 def test_backward_refuses_stale_parameters_and_state_gradients(dev):

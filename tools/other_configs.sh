@@ -7,7 +7,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 : > $O/${TAG}_other_configs.jsonl
-run() { python bench.py --steps 100 --warmup 10 --cpu-seconds 0 "$@" 2>/dev/null | grep "^{" >> $O/${TAG}_other_configs.jsonl; }
+run() { python bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 "$@" 2>/dev/null | grep "^{" >> $O/${TAG}_other_configs.jsonl; }
 run --humans 4 --depth 1 --roots 512
 run --humans 5 --depth 1 --roots 512
 run --depth 3 --roots 512

@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 { python -m pytest tests -m gpu -x -q -k "$KEXPR" 2>&1 | tail -4
   python tools/kiter.py --contraction bf16x6 --quick --parents 256 512 2048 4096 2>&1 | grep -v "^$" | head -12
-  python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 2>/dev/null | grep "^{" | python -c "
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 2>/dev/null | grep "^{" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('bench ms_per_step %.4f  device median %.4f  children launch_ms %.4f  frac %.3f  f32_line %.4f' % (d['ms_per_step'], d['step_ms_device']['median'], d['roofline']['launch_ms'], d['roofline']['frac'], d.get('f32_mfma_line',{}).get('ms_per_step',0)))"

@@ -11,9 +11,9 @@ print('%-34s ms_per_step %.4f  device median %.4f  host: search enqueue %s ms, e
 T="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511"
 {
 for roots in 256 512 2048; do
-  timeout 300 python bench.py --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 2>/dev/null | grep '^{' | p "plain, roots $roots"
-  timeout 300 $T bench.py --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 2>/dev/null | grep '^{' | p "1-rank RCCL, roots $roots"
-  timeout 300 $T bench.py --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 --graph off 2>/dev/null | grep '^{' | p "1-rank RCCL, --graph off, roots $roots"
+  timeout 300 python bench.py --full --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 2>/dev/null | grep '^{' | p "plain, roots $roots"
+  timeout 300 $T bench.py --full --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 2>/dev/null | grep '^{' | p "1-rank RCCL, roots $roots"
+  timeout 300 $T bench.py --full --gpus 1 --steps 50 --warmup 10 --roots $roots --cpu-seconds 0 --graph off 2>/dev/null | grep '^{' | p "1-rank RCCL, --graph off, roots $roots"
 done
 } > $O/r06_rccl_one_rank.txt 2>&1
 cat $O/r06_rccl_one_rank.txt

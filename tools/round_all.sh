@@ -10,14 +10,14 @@ cd $R
 # 1. kernel trace + PMC passes + the HBM-traffic record; the bench line embedded in the summary is taken AFTER the record exists
 bash tools/round_profile.sh $TAG $HASH > $O/${TAG}_round_profile.log 2>&1
 cp $O/${TAG}_traffic.json $R/profiles/${TAG}_traffic.json 2>/dev/null
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep "^{" > $O/${TAG}_bench_driver_style.json      # what the driver runs
-python bench.py --steps 50 --warmup 10 2>/dev/null | grep "^{" > $O/${TAG}_bench_default.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep "^{" > $O/${TAG}_bench_driver_style.json      # the driver's command, with --full's figures
+python bench.py --full --steps 50 --warmup 10 2>/dev/null | grep "^{" > $O/${TAG}_bench_default.json
 python - <<PY
 import json, re
 p = "$O/$TAG.md"
 s = open(p).read()
 line = open("$O/${TAG}_bench_default.json").read().strip()
-s = re.sub(r"bench line of the same run:\n\n\`\`\`\n.*?\n\`\`\`", "bench line (python bench.py --steps 50 --warmup 10, after the traffic record below was written):\n\n\`\`\`\n" + line.replace("\\\\", "\\\\\\\\") + "\n\`\`\`", s, count=1, flags=re.S)
+s = re.sub(r"bench line of the same run:\n\n\`\`\`\n.*?\n\`\`\`", "bench line (python bench.py --full --steps 50 --warmup 10, after the traffic record below was written):\n\n\`\`\`\n" + line.replace("\\\\", "\\\\\\\\") + "\n\`\`\`", s, count=1, flags=re.S)
 open(p, "w").write(s)
 PY
 # 2. the other BASELINE configurations, the share regime, timelines
@@ -32,7 +32,7 @@ bash tools/timeline.sh $O/${TAG}_timeline.md --humans 49 --layers 3 --roots 256 
 # 3. configs[4]: kernel trace of the bench commands + PMC passes of the deep kernel / head kernel, f32 and f16 (VERDICT r3 missing 2)
 ( cd /tmp && export TMPDIR=/tmp
   { echo "# $TAG: BASELINE configs[4] per-GPU share (N = 50, L = 3, D = 2, w = 2, 256 roots), source revision $HASH"; echo;
-    for c in f32 f16; do rm -rf /tmp/prof_c5; RGL_BENCH_NO_F32_LINE=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_c5 -o c5 -- python $R/bench.py --steps 50 --warmup 10 --cpu-seconds 0 --humans 49 --layers 3 --roots 256 --contraction $c > /tmp/c5.log 2>&1
+    for c in f32 f16; do rm -rf /tmp/prof_c5; RGL_BENCH_NO_F32_LINE=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_c5 -o c5 -- python $R/bench.py --full --steps 50 --warmup 10 --cpu-seconds 0 --humans 49 --layers 3 --roots 256 --contraction $c > /tmp/c5.log 2>&1
       echo "== contraction $c"; echo; echo '```'; grep "^{" /tmp/c5.log; echo '```'; echo; python $R/tools/rocpd_summary.py $(find /tmp/prof_c5 -name "*results.db" | head -1) | head -12; echo; done; } > $O/${TAG}_c5_kernel_stats.md )
 bash tools/deep_pmc.sh 512 > /dev/null 2>&1
 cat $O/deep_pmc.md >> $O/${TAG}_c5_kernel_stats.md

@@ -9,11 +9,11 @@ TAG=${1:-r03_x}
 HASH=${2:-unknown}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --steps 50 --warmup 10 --cpu-seconds 0 > $O/bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --full --steps 50 --warmup 10 --cpu-seconds 0 > $O/bench.log 2>&1
 {
   echo "# $TAG: kernel trace + counters of the headline workload (source revision $HASH)"
   echo
-  echo '`rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 --cpu-seconds 0` on one MI355X (tools/rocpd_summary.py over the rocpd DB).'
+  echo '`rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 50 --warmup 10 --cpu-seconds 0` on one MI355X (tools/rocpd_summary.py over the rocpd DB).'
   echo
   echo 'bench line of the same run:'
   echo

@@ -7,7 +7,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 : > $O/${TAG}_share_regime.jsonl
-run() { python bench.py --steps 200 --warmup 20 --cpu-seconds 0 "$@" 2>/dev/null | grep "^{" >> $O/${TAG}_share_regime.jsonl; }
+run() { python bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 "$@" 2>/dev/null | grep "^{" >> $O/${TAG}_share_regime.jsonl; }
 for g in off on; do
   run --roots 256 --graph $g
   run --roots 512 --graph $g

@@ -420,8 +420,8 @@ int mprl_tree_level_view(const MprlPlanner* planner, int B, int H, int level, Mp
  * Batched crowd simulator (next row of the scope table): B independent environments, float64 state.
  * crowd_step_f64 replaces CrowdSim.step (crowd_sim/envs/crowd_sim.py:252-368) incl. Agent.step /
  * compute_position (crowd_sim/envs/utils/agent.py:113-139) and, for human_policy LINEAR, Linear.predict
- * (crowd_sim/envs/policy/linear.py:16-22).  ORCA humans (external rvo2) are out of scope: supply their
- * actions with human_policy GIVEN.
+ * (crowd_sim/envs/policy/linear.py:16-22).  ORCA humans: crowd_orca_humans_f64 (below) computes their
+ * actions on device, which crowd_step_f64 then applies with human_policy GIVEN.
  *   robot [B][9], humans [B][H][5], time [B], done [B] (int, in/out): updated in place when update != 0
  *   (update = 0 is the reference's onestep_lookahead: outputs only); environments with done != 0 are frozen.
  *   human_goals [B][H][2], human_vpref [B][H] (LINEAR); human_actions [B][H][2] (GIVEN); robot_action [B][2]
@@ -446,6 +446,44 @@ int crowd_step_f64(const CrowdSimConfig* cfg, double* robot, double* humans, con
                    rgl_stream_t stream);
 int crowd_observe_f32(const double* robot, const double* humans, int B, int H, float* robot32, float* humans32,
                       rgl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ORCA on device (ABI 8, additive): RVO2 2.0's doStep for agents without obstacles, as Python-RVO2 runs it
+ * (crowd_sim/envs/policy/orca.py:75-161).  Every agent quantity is rounded from float64 to float32 once; the
+ * arithmetic is float32 with no contraction and correctly rounded division and square root, so the velocities
+ * are Python-RVO2's (RVO2 finds neighbours with a kd-tree, these kernels in agent index order: the two differ only
+ * on exact distance ties at the max_neighbors cut-off).  Outputs are float32 values widened to float64.
+ *   Agent radii are radius + 0.01 + safety_space (added in float64, then rounded); a preferred velocity points at
+ *   the agent's goal, (g - p) / |g - p| when |g - p| > 1 and g - p otherwise (float64, then rounded).
+ *   done [B] may be NULL; environments with done != 0 are skipped (their output rows are not written).
+ *
+ * crowd_orca_humans_f64: CentralizedORCA.predict as CrowdSim.step calls it (crowd_sim/envs/crowd_sim.py:256-262):
+ *   the agents are the H humans, plus the robot appended last when robot_visible (its own answer is discarded).
+ *   max_speed_rule CROWD_ORCA_MAX_SPEED_ONE: every agent's max_speed is 1 (centralized planning);
+ *   CROWD_ORCA_MAX_SPEED_VPREF: a human's max_speed is its v_pref (human_vpref [B][H], required): decentralized
+ *   planning, where each human's own ORCA.predict depends only on its own preferred velocity and max_speed.
+ *   robot [B][9], humans [B][H][5], human_goals [B][H][2]; out [B][H][2] (vx, vy).
+ * crowd_orca_robot_f64: ORCA.predict for the robot (orca.py:75-125; the imitation-learning expert): agent 0 is the
+ *   robot with max_speed = v_pref (robot[7]) and its preferred velocity toward its goal, the humans follow with
+ *   preferred velocity (0, 0).  out [B][2].
+ * Errors: RGL_ERR_NULL for a missing pointer, RGL_ERR_BAD_SHAPE for B, H < 1 or max_neighbors outside
+ * [0, CROWD_ORCA_MAX_NEIGHBORS], RGL_ERR_BAD_MODE for an unknown max_speed_rule.
+ * ------------------------------------------------------------------------------------------- */
+#define CROWD_ORCA_MAX_NEIGHBORS 32
+enum { CROWD_ORCA_MAX_SPEED_ONE = 0, CROWD_ORCA_MAX_SPEED_VPREF = 1 };
+
+typedef struct CrowdOrcaParams {
+    double time_step;           /* the simulator's (0.25); the collision case's horizon                     */
+    double neighbor_dist;       /* 10 (ORCA.__init__, orca.py:58-67)                                         */
+    double time_horizon;        /* 5                                                                          */
+    double safety_space;        /* 0; added to every radius with the 0.01 pad                                 */
+    int max_neighbors;          /* 10; at most CROWD_ORCA_MAX_NEIGHBORS                                       */
+    int max_speed_rule;         /* CROWD_ORCA_MAX_SPEED_* (crowd_orca_humans_f64; ignored by the robot entry) */
+    int reserved;
+} CrowdOrcaParams;
+
+int crowd_orca_humans_f64(const CrowdOrcaParams* params, const double* robot, const double* humans, const double* human_goals, const double* human_vpref, const int* done, int B, int H, int robot_visible, double* out, rgl_stream_t stream);
+int crowd_orca_robot_f64(const CrowdOrcaParams* params, const double* robot, const double* humans, const int* done, int B, int H, double* out, rgl_stream_t stream);
 
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);

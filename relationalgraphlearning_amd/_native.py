@@ -73,6 +73,15 @@ class CrowdSimConfig(C.Structure):
                 ("discomfort_penalty_factor", C.c_double), ("kinematics", C.c_int), ("human_policy", C.c_int)]
 
 
+class CrowdOrcaParams(C.Structure):
+    _fields_ = [("time_step", C.c_double), ("neighbor_dist", C.c_double), ("time_horizon", C.c_double),
+                ("safety_space", C.c_double), ("max_neighbors", C.c_int), ("max_speed_rule", C.c_int), ("reserved", C.c_int)]
+
+
+CROWD_ORCA_MAX_NEIGHBORS = 32
+ORCA_MAX_SPEED_RULES = {"one": 0, "v_pref": 1}
+
+
 class MprlLevelView(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in
                 ("n_parents", "robot_off", "humans_off", "humans_next_off", "child_robot_off", "reward_off",
@@ -128,6 +137,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "crowd_observe_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crowd_orca_humans_f64": (C.c_int, [C.POINTER(CrowdOrcaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "crowd_orca_robot_f64": (C.c_int, [C.POINTER(CrowdOrcaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }

@@ -4,7 +4,9 @@ Mirrors the parts of crowd_sim/envs/crowd_sim.py the rollout needs: seeded scene
 `generate_human`, :117-169 -- host numpy, reproducing the reference's RNG stream so test case k is the same scene),
 `step` / `onestep_lookahead` (:248-368, device: crowd_step_f64) and an Explorer-style episode loop over many
 environments at once (crowd_nav/utils/explorer.py:21-111).  Humans follow the reference's `linear` policy
-(crowd_sim/envs/policy/linear.py), constant velocity, or externally supplied actions; ORCA (external rvo2) is out of scope.
+(crowd_sim/envs/policy/linear.py), constant velocity, externally supplied actions, or ORCA (`human_policy="orca"`: the
+reference's default crowd, CentralizedORCA or per-human ORCA on device -- orca.py, csrc/rgl_orca.hip -- whose velocities
+the step then applies as supplied actions).
 """
 import ctypes as C
 
@@ -15,7 +17,7 @@ from . import _native as nat
 from .nets import _stream
 
 INFO = {0: "", 1: "Discomfort", 2: "Collision", 3: "Reaching goal", 4: "Timeout", 5: "(finished earlier)"}
-HUMAN_POLICY = {"given": 0, "linear": 1, "constant_velocity": 2}
+HUMAN_POLICY = {"given": 0, "linear": 1, "constant_velocity": 2, "orca": 0}     # orca: crowd_orca_humans_f64, then GIVEN
 BASE_SEED = {"train": 2000, "val": 0, "test": 1000}       # crowd_sim.py:185-186 with its case capacities
 
 
@@ -29,6 +31,7 @@ class SimConfig(object):
         self.scenario, self.square_width, self.circle_radius, self.human_num = "circle_crossing", 20, 4, 5
         self.human_radius, self.human_v_pref = 0.3, 1
         self.robot_radius, self.robot_v_pref = 0.3, 1
+        self.robot_visible, self.centralized_planning = False, True          # config.py:37, 47 (read by human_policy "orca")
         for k, v in over.items():
             if not hasattr(self, k):
                 raise AttributeError(k)
@@ -43,7 +46,8 @@ class SimConfig(object):
                          discomfort_penalty_factor=c.reward.discomfort_penalty_factor, scenario=c.sim.test_scenario,
                          square_width=c.sim.square_width, circle_radius=c.sim.circle_radius, human_num=c.sim.human_num,
                          human_radius=c.humans.radius, human_v_pref=c.humans.v_pref, robot_radius=c.robot.radius,
-                         robot_v_pref=c.robot.v_pref)
+                         robot_v_pref=c.robot.v_pref, robot_visible=c.robot.visible,
+                         centralized_planning=c.sim.centralized_planning)
 
 
 def generate_scene(cfg, phase, case):
@@ -104,6 +108,8 @@ class BatchedCrowdSim(object):
     def __init__(self, device, config=None, human_policy="linear", kinematics="holonomic"):
         self.cfg = config or SimConfig()
         self.device = torch.device(device)
+        if human_policy not in HUMAN_POLICY:
+            raise ValueError("unknown human policy %r" % human_policy)
         self.human_policy = human_policy
         self.kinematics = kinematics
         self.B = 0
@@ -133,6 +139,7 @@ class BatchedCrowdSim(object):
         self.done = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._r32 = torch.empty(self.B, 9, dtype=torch.float32, device=dev)
         self._h32 = torch.empty(self.B, self.H, 5, dtype=torch.float32, device=dev)
+        self._orca = torch.zeros(self.B, self.H, 2, dtype=torch.float64, device=dev) if self.human_policy == "orca" else None
         return self.observe()
 
     def observe(self):
@@ -150,6 +157,18 @@ class BatchedCrowdSim(object):
         c.human_policy = HUMAN_POLICY[self.human_policy]
         return c
 
+    def orca_params(self):
+        from .orca import OrcaParams
+        return OrcaParams(time_step=self.cfg.time_step)
+
+    def _orca_humans(self, robot, humans, goals, vpref, done, out):
+        """The humans' ORCA velocities for the state before anyone moves (crowd_sim.py:256-262) into `out`."""
+        from .orca import orca_human_velocities
+        if goals is None or (not self.cfg.centralized_planning and vpref is None):
+            raise ValueError("human_policy 'orca' needs the humans' goals (and v_pref under decentralized planning)")
+        return orca_human_velocities(robot, humans, goals, vpref, done, self.cfg.robot_visible, self.orca_params(),
+                                     self.cfg.centralized_planning, out)
+
     # -- dynamics ------------------------------------------------------------------------------------------------
     def step(self, robot_actions, human_actions=None, update=True):
         """robot_actions (B,2) float64 (vx,vy)|(v,r).  Returns (obs, reward (B,) fp32, done (B,) bool, info (B,) int32);
@@ -157,6 +176,8 @@ class BatchedCrowdSim(object):
         dev = self.device
         act = torch.as_tensor(robot_actions, dtype=torch.float64).to(dev).contiguous()
         ha = None if human_actions is None else torch.as_tensor(human_actions, dtype=torch.float64).to(dev).contiguous()
+        if ha is None and update and self.human_policy == "orca":
+            ha = self._orca_humans(self.robot, self.humans, self.human_goals, self.human_vpref, self.done, self._orca)
         reward = torch.empty(self.B, dtype=torch.float32, device=dev)
         info = torch.empty(self.B, dtype=torch.int32, device=dev)
         dmin = torch.empty(self.B, dtype=torch.float64, device=dev)
@@ -195,10 +216,14 @@ class BatchedCrowdSim(object):
         info = torch.empty(A, dtype=torch.int32, device=dev)
         dmin = torch.empty(A, dtype=torch.float64, device=dev)
         cfg = self._config()
+        ha = None
+        if self.human_policy == "orca":
+            ha = self._orca_humans(robot, humans, goals, vpref, None, None)
         with torch.cuda.device(dev):
             rc = nat.lib().crowd_step_f64(C.byref(cfg), robot.data_ptr(), humans.data_ptr(),
                                           None if goals is None else goals.data_ptr(),
-                                          None if vpref is None else vpref.data_ptr(), act.data_ptr(), None,
+                                          None if vpref is None else vpref.data_ptr(), act.data_ptr(),
+                                          None if ha is None else ha.data_ptr(),
                                           time.data_ptr(), done.data_ptr(), A, self.H, 1, reward.data_ptr(),
                                           info.data_ptr(), dmin.data_ptr(), _stream())
         nat.check(rc, "crowd_step_f64")

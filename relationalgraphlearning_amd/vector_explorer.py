@@ -10,6 +10,10 @@ Differences that follow from vectorisation (documented, not hidden): episodes of
 of the phase (the reference draws them one after another from the same counter, so the set is identical; the order
 inside the replay memory is episode-major here as well); epsilon-greedy exploration draws its random numbers per
 time step for all environments at once, so the random stream differs from k sequential episodes.
+
+A policy with `acts_in_velocity = True` (orca.OrcaPolicy, the imitation-learning expert of train.py:143-154) returns (B,2)
+velocities from `predict_batch(robot, humans, done=...)`, given the simulator's float64 state; they go to the simulator as
+they are and `last_run["actions"]` holds them as (vx, vy) pairs.  Index-returning policies are unaffected.
 """
 import logging
 
@@ -146,6 +150,8 @@ class VectorExplorer(object):
         return cases
 
     def _act(self, robot32, humans32, phase, n_actions):
+        if getattr(self.policy, "acts_in_velocity", False):
+            return self.policy.predict_batch(self.sim.robot, self.sim.humans, roots_are_joint_states=True, done=self.sim.done)
         idx, _ = self.policy.predict_batch(robot32, humans32, roots_are_joint_states=True)
         idx = idx.long()
         eps = getattr(self.policy, "epsilon", None)
@@ -160,9 +166,14 @@ class VectorExplorer(object):
         sim, policy = self.sim, self.policy
         robot32, humans32 = sim.reset(phase, cases)
         B = sim.B
-        if policy.action_space is None:
-            policy.build_action_space(sim.cfg.robot_v_pref)
-        table = torch.tensor(as_array(policy.action_space), dtype=torch.float64, device=sim.device)
+        velocity = bool(getattr(policy, "acts_in_velocity", False))
+        if velocity:
+            policy.check_kinematics(sim.kinematics)
+            table = None
+        else:
+            if policy.action_space is None:
+                policy.build_action_space(sim.cfg.robot_v_pref)
+            table = torch.tensor(as_array(policy.action_space), dtype=torch.float64, device=sim.device)
         max_steps = int(round(sim.cfg.time_limit / sim.cfg.time_step)) + 2
         outcome = torch.zeros(B, dtype=torch.int32, device=sim.device)
         rewards, infos, dmins, states, actions = [], [], [], [], []
@@ -171,8 +182,10 @@ class VectorExplorer(object):
                 break
             if keep_states:
                 states.append((robot32.clone(), humans32.clone()))
-            idx = self._act(robot32, humans32, phase, table.shape[0])
-            (robot32, humans32), reward, _, info = sim.step(table[idx])
+            idx = self._act(robot32, humans32, phase, None if velocity else table.shape[0])
+            (robot32, humans32), reward, _, info = sim.step(idx if velocity else table[idx])
+            if velocity:
+                idx = idx.clone()                        # the policy may hand out one buffer per call
             actions.append(idx)
             rewards.append(reward)
             infos.append(info)
@@ -205,6 +218,7 @@ class VectorExplorer(object):
             if (run["outcome"] == 0).any():
                 raise ValueError('Invalid end signal from environment')
             cum, avg_ret = discounted_statistics(run["rewards"], run["lengths"], step_discount)
+            velocity = bool(getattr(self.policy, "acts_in_velocity", False))
             acts = torch.stack(run["actions"]).cpu().numpy() if run["actions"] else np.zeros((0, len(chunk)), np.int64)
             for b in range(len(chunk)):
                 i = lo + b
@@ -223,7 +237,10 @@ class VectorExplorer(object):
                 per_episode["outcome"].append(code)
                 per_episode["time"].append(float(run["time"][b]))
                 per_episode["length"].append(int(run["lengths"][b]))
-                per_episode["actions"].append([int(a) for a in acts[:int(run["lengths"][b]), b]])
+                if velocity:
+                    per_episode["actions"].append([(float(a[0]), float(a[1])) for a in acts[:int(run["lengths"][b]), b]])
+                else:
+                    per_episode["actions"].append([int(a) for a in acts[:int(run["lengths"][b]), b]])
             danger = run["info"] == 1
             discomfort += int(danger.sum())
             min_dist.extend(run["dmin"][danger].tolist())

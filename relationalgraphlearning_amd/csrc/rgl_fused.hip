@@ -120,6 +120,18 @@ __device__ __forceinline__ float head_chain(const float* lds, const f32x4 (&tin)
     return kgroups_sum(v);
 }
 
+// BX: one 16 x 16 block of A B^T over a K = 32 chunk whose BOTH operands are three-piece register operands (split3_pair of two
+// D-layout tiles: the crowd's S = G Xh^T and U = E Xh, the tile's robot row / column of S) -- the six terms of layer_mfma_b6, small
+// ones first
+__device__ __forceinline__ f32x4 b6_block(const Split3& a, const Split3& b, f32x4 acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.m, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.h, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.m, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, acc, 0, 0, 0);
+}
+
 // scale of the PK row pass (children_fused_kernel): its ReLU sits in the clamp bit of v_pk_fma_f32 (rgl_mfma.h), which clamps to [0, 1]
 constexpr float kRowScale = 0x1p-110f, kRowUnscale = 0x1p110f;
 
@@ -188,6 +200,11 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
     }
     f32x4 gq[NT][2], xq[NT][2], ms[NT], zs[NT], xt[NT][2], uw4[HRL / 4];
     float xt1p[2] = {0.f, 0.f}, ms1 = 0.f, zs1 = 1.f;      // T1P: Xh^T[f][node 16 + q], msh / Zsh of node 16 + q
+    constexpr int NTS = T1P ? 1 : NT;                        // node tiles of the tile's robot row / column of S on the 16 x 16 MFMA
+    // BXS: those products as six terms, their A operands (rows of G, Xh) held as pieces, split once per item -- where one node tile
+    // takes them (+8 VGPRs); two (N > 20, or a plain similarity with N > 16) would add 16 to kernels that spill already
+    constexpr bool BXS = BX && NTS == 1;
+    Split3 gpc[BXS ? NTS : 1], xpc[BXS ? NTS : 1];
     // item wi = (order position o, local parent), o-major; group j = (o + rot) % items_per_parent covers the full tiles j G ..; the
     // LAST group (the short one) also carries the parent's partial tile, which it runs first.  Tile sequence ts .. t1-1, where
     // t < t0 means "the partial tile".
@@ -311,16 +328,33 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         __builtin_amdgcn_wave_barrier();
         
         // part 2 (every Xh row is in registers now): S_ij = G_i . Xh_j over humans j, msh / E / Zsh, U = E Xh, UW = U W1
+        // BX: S and U as six-term products; Xh and Xh^T are split once per item (one K = 32 chunk each: the 32 features of a node
+        // tile, the <= 32 nodes of a feature tile)
+        Split3 xqs[BX ? NT : 1], xts[BX ? 2 : 1];
+        if constexpr (BX) {
+            static_assert(NT <= 2, "Xh^T: one chunk over the nodes");
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) xqs[jt] = split3_pair(xq[jt][0], xq[jt][1]);
+            if constexpr (BXS) xpc[0] = xqs[0];
+#pragma unroll
+            for (int ft = 0; ft < 2; ++ft) xts[ft] = split3_pair(xt[0][ft], NT > 1 ? xt[NT > 1 ? 1 : 0][ft] : zero4());
+        }
 #pragma unroll
         for (int pct = 0; pct < NT; ++pct) {
             const int node = 16 * pct + n;
             const bool node_ok = node >= 1 && node < N;
             f32x4 e[NT];
             float mx = NEG_INF;
+            Split3 gs;
+            if constexpr (BX) {
+                gs = split3_pair(gq[pct][0], gq[pct][1]);
+                if (BXS && pct == 0) gpc[0] = gs;
+            }
 #pragma unroll
             for (int jt = 0; jt < NT; ++jt) {
                 f32x4 sacc = zero4();
-                {
+                if constexpr (BX) sacc = b6_block(xqs[jt], gs, sacc);
+                else {
 #pragma unroll
                 for (int ft = 0; ft < 2; ++ft)
 #pragma unroll
@@ -354,6 +388,11 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
             f32x4 u[2] = {zero4(), zero4()};
             f32x4 uw[2] = {zero4(), zero4()};
             {
+            if constexpr (BX) {
+                const Split3 es = split3_pair(e[0], NT > 1 ? e[NT > 1 ? 1 : 0] : zero4());
+                u[0] = b6_block(xts[0], es, u[0]);
+                u[1] = b6_block(xts[1], es, u[1]);
+            } else {
 #pragma unroll
             for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
@@ -361,6 +400,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
                     u[0] = mfma4(xt[jt][0][r], e[jt][r], u[0]);                               // U^T[f][i] = sum_j Xh[j][f] E[i][j]
                     u[1] = mfma4(xt[jt][1][r], e[jt][r], u[1]);
                 }
+            }
             if constexpr (BX) layer_mfma_b6<XD, XD, false>(w1, u, uw, lane);
             else {
 #pragma unroll
@@ -478,6 +518,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         // ---------------- embedding: x0 = w_r(robot'), y = x0 W1, g0 = x0 Wa (transposed MFMA chain) ----------------
         f32x4 xacc[2] = {zero4(), zero4()}, gacc[2] = {zero4(), zero4()}, yacc[2] = {zero4(), zero4()};
         float s00 = 0.f;
+        Split3 sx;                                         // BX: pieces of x0 (the products with Wa, W1 and the robot column of S)
         {
             f32x4 hacc[4] = {zero4(), zero4(), zero4(), zero4()};
 #pragma unroll
@@ -501,7 +542,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
                 for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) xacc[ot][r] = relu1(xacc[ot][r]);
-                const Split3 sx = split3_pair(xacc[0], xacc[1]);
+                sx = split3_pair(xacc[0], xacc[1]);
                 layer_mfma_b6_pre<XD, false>(wa, sx, gacc, lane);
                 layer_mfma_b6_pre<XD, false>(w1, sx, yacc, lane);
             } else {
@@ -568,10 +609,15 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
                 if (16 + q >= N) { sc1 = NEG_INF; p1 = NEG_INF; }
                 mx0 = p1;
             }
+            Split3 sg;                                   // BX: pieces of g0 = x0 Wa
+            if constexpr (BXS) sg = split3_pair(gacc[0], gacc[1]);
 #pragma unroll
-            for (int nt = 0; nt < (T1P ? 1 : NT); ++nt) {
+            for (int nt = 0; nt < NTS; ++nt) {
                 f32x4 sc = zero4(), s0 = zero4();
-                {
+                if constexpr (BXS) {
+                    sc = b6_block(gpc[0], sx, sc);
+                    s0 = b6_block(xpc[0], sg, s0);
+                } else {
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot)
 #pragma unroll

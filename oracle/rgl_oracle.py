@@ -120,9 +120,9 @@ def similarity_matrix(X, gsd, mode):
         S2 = S * S
         return S2 / S2.sum(dim=2, keepdim=True)
     if mode == "equal_attention":
-        return (torch.ones(N, N) / N).expand(B, N, N)
+        return (torch.ones(N, N, dtype=X.dtype) / N).expand(B, N, N)
     if mode == "diagonal":
-        return torch.eye(N, N).expand(B, N, N)
+        return torch.eye(N, N, dtype=X.dtype).expand(B, N, N)
     raise NotImplementedError(mode)
 
 
@@ -738,12 +738,13 @@ def gcn_predict_sequential(robot9, humans, sd, cfg):
     return best, vals
 
 
-def gcn_predict_batched(robot, humans, sd, cfg, chunk=4096):
+def gcn_predict_batched(robot, humans, sd, cfg, chunk=4096, dtype=torch.float32):
     """Batched restatement of gcn_predict_sequential (the loop of multi_human_rl.py:36-64 for B root scenes at once).
     robot (B,9), humans (B,H,5): arrays / tensors of the ROOT states (float32 values as the fixtures hold them; all arithmetic
     of propagate / compute_reward in float64 like the python floats of the sequential walk, the joint rows rounded to float32
     exactly where it builds its tensor).  Returns (best action (B,) int64, action_values (B,A) float64).
-    Pinned against fixture F7 (`path_g.npz`) in tests/test_oracle_golden.py next to the sequential form."""
+    Pinned against fixture F7 (`path_g.npz`) in tests/test_oracle_golden.py next to the sequential form.  `dtype`: the value
+    network's arithmetic (torch.float64 with a float64 `sd`: the high-precision reference of the GPU's float32 rows)."""
     robot = np.asarray(robot, dtype=np.float64)
     humans = np.asarray(humans, dtype=np.float64)
     B, H = humans.shape[0], humans.shape[1]
@@ -783,7 +784,7 @@ def gcn_predict_batched(robot, humans, sd, cfg, chunk=4096):
         rew = np.where(collision, -0.25, np.where(reaching, 1.0, np.where(dmin < 0.2, (dmin - 0.2) * 0.5 * dt, 0.0)))
         joint = np.concatenate([np.repeat(nr[:, :, None, :], H, axis=2),
                                 np.repeat(nh[:, None, :, :], A, axis=1)], axis=3).astype(np.float32)   # (b,A,H,14)
-        joint = torch.tensor(joint.reshape(-1, 14))
+        joint = torch.tensor(joint.reshape(-1, 14)).to(dtype)
         v = np.zeros(len(sel) * A)
         with torch.no_grad():
             for lo in range(0, len(sel) * A, chunk):

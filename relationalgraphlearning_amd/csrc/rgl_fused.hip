@@ -1322,8 +1322,9 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
         }
     }
     FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);
-    // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch) do not fit a CU
-    // with it -- they run the f32 form of this kernel on an f32 image packed here (the caller's image is in the other layout)
+    // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch), and of 17..20 with a
+    // plain-weight similarity (unpacked row pass: 172 944 bytes), do not fit a CU with it -- they run the f32 form of this kernel on
+    // an f32 image packed here (the caller's image is in the other layout; tests/test_bf16x6_kernels.py pins the envelope)
     bool own_image = false;
     if (!fp.ok && mode) {
         fp = plan_fused(*g, *head, P, A, H, unit, kModeF32);

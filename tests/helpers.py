@@ -1,4 +1,7 @@
 """Test helpers: build product policies/modules loaded with the golden weight sets."""
+import numpy as np
+import torch
+
 import relationalgraphlearning_amd as rga
 from relationalgraphlearning_amd.config import policy_config
 from tests import golden_io as gio
@@ -37,6 +40,27 @@ def make_gcn_policy(L=2, layerwise=False, skip=True, device=None):
     if device is not None:
         pol.set_device(device)
     return pol
+
+
+def dense_scenes(rng, P, H):
+    """P parents with DENSE crowds of H humans drawn from `rng` (a quarter of the humans within 0.45-1.6 m of the robot, robots
+    near or at their goals): every branch of the reward step -- collisions, discomfort, goals -- occurs.  (robot (P,9), humans
+    (P,H,5)) float32 tensors."""
+    robot = np.zeros((P, 9), np.float32)
+    robot[:, 0:2] = rng.uniform(-3, 3, (P, 2))
+    robot[:, 2:4] = rng.uniform(-0.5, 0.5, (P, 2))
+    robot[:, 4] = 0.3
+    robot[:, 5:7] = robot[:, 0:2] + rng.uniform(-0.6, 0.6, (P, 2)) * (rng.rand(P, 1) < 0.3) + rng.uniform(-4, 4, (P, 2)) * (rng.rand(P, 1) < 0.7)
+    robot[:, 7] = 1.0
+    robot[:, 8] = rng.uniform(-np.pi, np.pi, P)
+    humans = np.zeros((P, H, 5), np.float32)
+    ang = rng.uniform(0, 2 * np.pi, (P, H))
+    rad = np.where(rng.rand(P, H) < 0.25, rng.uniform(0.45, 1.6, (P, H)), rng.uniform(1.6, 6.0, (P, H)))      # a quarter of them close
+    humans[:, :, 0] = robot[:, None, 0] + rad * np.cos(ang)
+    humans[:, :, 1] = robot[:, None, 1] + rad * np.sin(ang)
+    humans[:, :, 2:4] = rng.uniform(-1, 1, (P, H, 2))
+    humans[:, :, 4] = 0.3
+    return torch.tensor(robot), torch.tensor(humans)
 
 
 class JS(object):

@@ -15,7 +15,7 @@ from relationalgraphlearning_amd import _native as nat
 from relationalgraphlearning_amd.config import policy_config
 from oracle import rgl_oracle as orc
 from tests import golden_io as gio
-from tests.helpers import make_mprl_policy, make_gcn_policy, JS
+from tests.helpers import make_mprl_policy, make_gcn_policy, dense_scenes, JS
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -173,22 +173,7 @@ def test_reward_step_over_crowd_sizes_and_dense_scenes(kin, dev):
     rng = np.random.RandomState(606)
     n_coll = n_disc = n_goal = 0
     for H in (1, 2, 31, 32, 33, 63, 64, 65):
-        P = 37
-        robot = np.zeros((P, 9), np.float32)
-        robot[:, 0:2] = rng.uniform(-3, 3, (P, 2))
-        robot[:, 2:4] = rng.uniform(-0.5, 0.5, (P, 2))
-        robot[:, 4] = 0.3
-        robot[:, 5:7] = robot[:, 0:2] + rng.uniform(-0.6, 0.6, (P, 2)) * (rng.rand(P, 1) < 0.3) + rng.uniform(-4, 4, (P, 2)) * (rng.rand(P, 1) < 0.7)
-        robot[:, 7] = 1.0
-        robot[:, 8] = rng.uniform(-np.pi, np.pi, P)
-        humans = np.zeros((P, H, 5), np.float32)
-        ang = rng.uniform(0, 2 * np.pi, (P, H))
-        rad = np.where(rng.rand(P, H) < 0.25, rng.uniform(0.45, 1.6, (P, H)), rng.uniform(1.6, 6.0, (P, H)))      # a quarter of them close
-        humans[:, :, 0] = robot[:, None, 0] + rad * np.cos(ang)
-        humans[:, :, 1] = robot[:, None, 1] + rad * np.sin(ang)
-        humans[:, :, 2:4] = rng.uniform(-1, 1, (P, H, 2))
-        humans[:, :, 4] = 0.3
-        rt, ht = torch.tensor(robot), torch.tensor(humans)
+        rt, ht = dense_scenes(rng, 37, H)
         want_child = orc._children_robot(rt, acts, cfg).numpy()
         for joint in (False, True):
             child, reward = ts.estimate_reward(rt.to(dev), ht.to(dev), parents_are_joint_states=joint)
@@ -1968,7 +1953,10 @@ AT_SIZE_CASES = [
     ("configs[1] in full (N=6)", 5, 2, 1, 512, "f32", TOL),
     ("configs[1] in full (N=6), the arithmetic bench.py reports it in", 5, 2, 1, 512, "bf16x6", TOL),
     ("configs[2] in full", 19, 2, 2, 2048, "f32", TOL),
+    ("configs[2] per-GPU share (256 roots)", 19, 2, 2, 256, "f32", TOL),
+    ("configs[2] per-GPU share (256 roots), the arithmetic bench.py reports it in", 19, 2, 2, 256, "bf16x6", TOL),
     ("configs[3] per-GPU share", 19, 2, 3, 512, "f32", TOL),
+    ("configs[3] per-GPU share, the arithmetic bench.py reports it in", 19, 2, 3, 512, "bf16x6", TOL),
     ("configs[3] in full (4096 roots, depth 3)", 19, 2, 3, 4096, "f32", TOL),
     ("configs[3] in full (4096 roots, depth 3), the arithmetic bench.py reports it in", 19, 2, 3, 4096, "bf16x6", TOL),
     ("configs[4] per-GPU share in full (256 roots)", 49, 3, 2, 256, "f32", TOL),
@@ -2041,10 +2029,17 @@ FORCED_FAMILIES = {
     "general VALU kernel": ({"RGL_FORCE_GENERIC": "1"}, 256),
     "fused kernel with the round-3 register-staged weight image": ({"RGL_FUSED_IMAGE_SYNC": "1"}, 2048),
 }
+# The families with a bf16x6 form, also run in that mode.  The others have none: launch_value_children runs the two-stage pair, the
+# tile kernel and the general kernel in f32 whatever the planner's contraction mode, and the bf16x6 fused kernel takes every launch
+# size already (RGL_CHILDREN_FUSED=1 changes nothing there).
+FORCED_FAMILIES_BF16X6 = ["fused kernel without its tail (stand-alone select / back-up / root kernels)",
+                          "fused kernel with the round-3 register-staged weight image"]
+FORCED_CASES = [pytest.param(f, "f32", id=f.split(" (")[0].replace(" ", "_")) for f in FORCED_FAMILIES] + \
+               [pytest.param(f, "bf16x6", id=f.split(" (")[0].replace(" ", "_") + "-bf16x6") for f in FORCED_FAMILIES_BF16X6]
 
 
-@pytest.mark.parametrize("family", list(FORCED_FAMILIES), ids=lambda f: f.split(" (")[0].replace(" ", "_"))
-def test_forced_kernel_families_at_size(family, dev, tmp_path):
+@pytest.mark.parametrize("family,contraction", FORCED_CASES)
+def test_forced_kernel_families_at_size(family, contraction, dev, tmp_path):
     """DESIGN.md section 5 says every kernel family serves the whole path; the driver's `pytest -m gpu` only sees the default
     dispatch.  Here the at-size configs[2] oracle check (bench.py's scenes and weights, all 2048 roots; the first 256 for the
     general VALU kernel) is re-run in a child process under each forcing switch -- the switches are read once per process.  The
@@ -2060,26 +2055,30 @@ def test_forced_kernel_families_at_size(family, dev, tmp_path):
     np.savez(ref, oa=oracle_out[0].numpy()[:B], ov=oracle_out[1].numpy()[:B], orv=oracle_out[2].numpy()[:B],
              okept=oracle_out[3].numpy()[:B], v1=v1.numpy()[:B])
     code = r'''
-import sys, numpy as np, torch
+import os, sys, numpy as np, torch
 import bench
 from tests import test_gpu_parity as T
 ref = np.load(sys.argv[1])
 B = int(sys.argv[2])
+contraction = sys.argv[3]
 dev = torch.device("cuda:0")
-pol = T._bench_policy(2, 2, 19, "f32", dev)
+pol = T._bench_policy(2, 2, 19, contraction, dev)
 robot, humans = bench.synth_scenes(1000, 2048, 19)
 act, val = pol.predict_batch(robot[:B].to(dev), humans[:B].to(dev), roots_are_joint_states=True)
 err = T.close(val.cpu().numpy(), ref["ov"], tol=T.TOL, reg=T.REG_F32)
 oracle_out = [torch.tensor(ref[k]) for k in ("oa", "ov", "orv", "okept")]
 n = T.check_decisions("forced", act, val, oracle_out, [{"value1": torch.tensor(ref["v1"])}], T.TOL)
+if contraction != "f32" and not os.environ.get("RGL_CONTRACT_F32_AS"):     # the mode ran: an f32 search under the same switch differs
+    _, v32 = T._bench_policy(2, 2, 19, "f32", dev).predict_batch(robot[:B].to(dev), humans[:B].to(dev), roots_are_joint_states=True)
+    assert not torch.equal(v32, val)
 print("OK max |dV| = %.2e, %d of %d decisions differ (ties in the oracle)" % (err, n, B))
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", code, ref, str(B)], cwd=root, env=dict(os.environ, **env_add), capture_output=True,
-                         text=True, timeout=900)
+    out = subprocess.run([sys.executable, "-c", code, ref, str(B), contraction], cwd=root, env=dict(os.environ, **env_add),
+                         capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "OK" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-    report("configs[2] at size (%d roots) with %s forced (%s): %s" % (B, family, " ".join("%s=%s" % kv for kv in env_add.items()),
-                                                                      out.stdout.strip().splitlines()[-1]))
+    report("configs[2] at size (%d roots) with %s forced (%s), %s: %s" % (B, family, " ".join("%s=%s" % kv for kv in env_add.items()),
+                                                                          contraction, out.stdout.strip().splitlines()[-1]))
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -91,7 +91,10 @@ int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, i
 int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, int H, const float* child_robot,
                           const float* humans_next, float* child_value, void* workspace, size_t workspace_bytes,
                           int image_ready, hipStream_t stream, const float* caller_image = nullptr,
-                          const void* tail = nullptr, size_t tail_bytes = 0, int* tail_done = nullptr, int mode = 0);
+                          const void* tail = nullptr, size_t tail_bytes = 0, int* tail_done = nullptr, int mode = 0,
+                          const void* prologue = nullptr, size_t prologue_bytes = 0);
+// `prologue` (optional, launch_fused_children and launch_value_children): a LevelPrologue -- the launch also runs the level's state
+// predictor and reward / next-state pairs (fused_prologue_fits must hold; it is an error otherwise)
 // mode 2: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
                          hipStream_t stream, int mode = 0);   // P = the largest launch; 1 = the fused kernel does not apply
@@ -100,7 +103,7 @@ const float* fused_workspace_image(const void* workspace, size_t workspace_bytes
 int launch_value_children(const MprlPlanner* pl, const float* child_robot, const float* humans_next, int P, int H,
                           float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream,
                           int image_ready = 0, const void* tail = nullptr, size_t tail_bytes = 0,
-                          int* tail_done = nullptr);                                                                // rgl_fast.hip
+                          int* tail_done = nullptr, const void* prologue = nullptr, size_t prologue_bytes = 0);   // rgl_fast.hip
 size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);                                        // rgl_fast.hip
 // `children` (optional): a ChildrenArgs (rgl_children.h, passed opaquely with its size) describing the level's independent
 // next-state / reward work; when the MFMA scene kernel runs, it executes that work on extra workgroups of the same launch
@@ -111,6 +114,14 @@ int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float
                           float* humans_next, void* workspace, size_t workspace_bytes, hipStream_t stream,
                           const void* children = nullptr, size_t children_bytes = 0, int* children_done = nullptr,
                           const float* sp_image = nullptr);                                                           // rgl_scene.hip
+// the level prologue of the fused children kernel (RGL_LEVEL_PROLOGUE): `children` is the level's ChildrenArgs, `out` a LevelPrologue
+// (rgl_scene_body.h; both opaque here, passed with their sizes); 1 = the state predictor is outside the prologue's form
+int level_prologue_args(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
+                        float* humans_next, const float* sp_image, const void* children, size_t children_bytes, void* out,
+                        size_t out_bytes);                                                                          // rgl_scene.hip
+// true: launch_value_children takes a LevelPrologue of `scene_floats` LDS floats for these P parents (the bf16x6 fused kernel of
+// 17..20-node crowds with a softmax similarity, and a workspace it can run in)
+bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, int scene_floats);           // rgl_fused.hip
 size_t scene_image_bytes(const MprlPlanner* pl);                      // 0: no six-term bf16 scene kernel for this planner
 int pack_scene_image(const MprlPlanner* pl, float* image, hipStream_t stream);
 size_t scene_image_bytes_for(const RglGraph& g, const RglMlp* motion_head);          // the same for a graph (+ optional motion head)

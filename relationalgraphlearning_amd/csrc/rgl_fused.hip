@@ -28,6 +28,7 @@
 //     kernel, tile-packed over parents (16 `stop` children = one head tile), so the head never multiplies 15 columns of
 //     padding and the whole path is one launch.
 #include "rgl_mlp_chain.h"
+#include "rgl_scene_body.h"
 #include "rgl_tail.h"
 
 #include <mutex>
@@ -77,7 +78,17 @@ struct FusedArgs {
     TailArgs tail;                // tail.enabled: select (+ back-up chain + root step) for the owned parents at the end
 };
 
+// the level prologue's arguments: a kernel argument of the PRO instantiations only (the others keep FusedArgs' kernarg size)
+template <bool PRO> struct PrologueArgs {};
+template <> struct PrologueArgs<true> {
+    SceneArgs scene;              // the state predictor's scenes of the owned parents (LevelPrologue::scene)
+    ChildrenArgs children;        // their reward / next-state pairs
+};
+
 constexpr int kFusedWaves = 8;
+// PRO: LDS floats below the scene region of the level prologue: the image's first part [0, f_last) in whole 256-float chunks (the
+// chunk that holds f_last lands in full, so the scene region starts behind it)
+template <class LO> constexpr int kPrologueSceneBase = (LO::f_last + 255) / 256 * 256;
 static_assert(B6Floats<HID, XD>::v == HID * XD * 3 / 2 && B6Floats<XD, XD>::v == XD * XD * 3 / 2, "FusedLds sizes its BX matrices so");
 static_assert((FusedLds<32, 100, 100, true>::scratch + kFusedWaves * 1344 + 4) * 4 <= 160 * 1024, "the BX image + 8 wave scratches fit a CU");
 
@@ -137,8 +148,11 @@ constexpr float kRowScale = 0x1p-110f, kRowUnscale = 0x1p110f;
 
 // HR >= N: human rows of UW held in registers (padded rows contribute exactly 0); SOFT: softmax row normalisation
 // BX: the D2 x D3 head matrix's first 64 input features as six bf16 terms on the matrix pipe (layer_mfma_bx; RGL_CONTRACT_BF16X6)
-template <int HR, int NT, bool SKIP, bool SOFT, int D1, int D2, int D3, bool BX = false>
-__global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const FusedArgs a) {
+// PRO: the level prologue (RGL_LEVEL_PROLOGUE): the workgroup first runs the state predictor and the reward / next-state pairs of the
+// parents it owns -- the humans_next rows and child robot rows its items read, the rewards its tail reads -- so that a tree level is
+// ONE launch (instead of embeddings + rewards, scenes, children)
+template <int HR, int NT, bool SKIP, bool SOFT, int D1, int D2, int D3, bool BX = false, bool PRO = false>
+__global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const FusedArgs a, const PrologueArgs<PRO> pa) {
     const int sim = SOFT ? (int)SIM_SOFTMAX : a.sim;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using LO = FusedLds<D1, D2, D3, BX>;
@@ -190,14 +204,17 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
     // BX: w_h's second matrix [64][32] as the A-operand elements my lane feeds to its 32 MFMAs of every crowd computation --
     // fragment (ht, r, ot): row 16 ht + 4 q + r, column 16 ot + n -- held in registers for the whole kernel (see FusedLds::bh2)
     float wh2r[BX ? 32 : 1];
-    if constexpr (BX) {
+    auto wh2_loads = [&]() {
+        if constexpr (BX) {
 #pragma unroll
-        for (int ht = 0; ht < 4; ++ht)
+            for (int ht = 0; ht < 4; ++ht)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+                for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int ot = 0; ot < 2; ++ot) wh2r[(ht * 4 + r) * 2 + ot] = a.wh2[(16 * ht + 4 * q + r) * XD + 16 * ot + n];
-    }
+                    for (int ot = 0; ot < 2; ++ot) wh2r[(ht * 4 + r) * 2 + ot] = a.wh2[(16 * ht + 4 * q + r) * XD + 16 * ot + n];
+        }
+    };
+    if (!PRO) wh2_loads();
     f32x4 gq[NT][2], xq[NT][2], ms[NT], zs[NT], xt[NT][2], uw4[HRL / 4];
     float xt1p[2] = {0.f, 0.f}, ms1 = 0.f, zs1 = 1.f;      // T1P: Xh^T[f][node 16 + q], msh / Zsh of node 16 + q
     constexpr int NTS = T1P ? 1 : NT;                        // node tiles of the tile's robot row / column of S on the 16 x 16 MFMA
@@ -469,6 +486,24 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.image + fl),
                                              (__attribute__((address_space(3))) void*)(lds + c * kChunk), 16, 0, 0);
     };
+    if constexpr (PRO) {
+        // LDS during the prologue: the image's first part [0, f_last) -- requested here, it lands under the scene image's loads and
+        // is waited for with them -- and behind its last chunk the scene region (predictor image, embedding sets, 8 wave slots:
+        // 97 KB), which the rest of the image and the wave scratches overwrite behind the barrier below
+        static_assert(kPrologueSceneBase<LO> == kChunksA * kChunk, "the scene region starts behind the first part's chunks");
+        for (int c = wave; c < kChunksA; c += kFusedWaves) image_chunk(c);
+        scene_body<2, 0, kFusedWaves, false, true, true>(pa.scene, lds + kPrologueSceneBase<LO>, p_first, 1, kFusedWaves, p_first + k_b);
+        const ChildrenArgs& ca = pa.children;
+        const long long pair0 = (long long)p_first * ca.A, pair_end = (long long)(p_first + k_b) * ca.A;
+        if (ca.A >= 64 && ca.H <= 64 && !ca.robot64) {       // as the stand-alone launches: whole waves, far-human masks per parent
+            const float v_max = table_speed_bound(ca);
+            for (long long base = pair0 + 64 * wave; base < pair_end; base += 64 * kFusedWaves) children_wave(ca, base, pair_end, v_max);
+        } else {
+            for (long long idx = pair0 + tid; idx < pair_end; idx += nthreads) children_thread(ca, idx);
+        }
+        __syncthreads();                 // my parents' humans_next, child robot rows and rewards are written; the scene region is free
+        wh2_loads();
+    }
     // (the first item's state rows are requested BEFORE the image: the wait in front of the barrier covers them, and no later
     // wait for them can hold the wave until the head fragments have landed as well -- vmcnt counts in order)
     if (wave < n_items) item_loads(item_at(0));
@@ -479,7 +514,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         __syncthreads();
         image_complete = true;
     } else {
-    for (int c = wave; c < kChunksA; c += kFusedWaves) image_chunk(c);
+    if (!PRO) for (int c = wave; c < kChunksA; c += kFusedWaves) image_chunk(c);          // (PRO: loaded in the prologue)
     __builtin_amdgcn_s_waitcnt(0x0F70);                                    // vmcnt(0)
     __syncthreads();
     for (int c = kChunksA + wave; c < kChunksAll; c += kFusedWaves) image_chunk(c);
@@ -1084,6 +1119,7 @@ struct FusedPlan {
     int grid;
     int hr, nt;
     bool bx;                       // bf16 six-term hybrid of the last head matrix (RGL_CONTRACT_BF16X6)
+    const LevelPrologue* pro = nullptr;      // with the level prologue (PrologueArgs)
     int mode() const { return bx ? kModeBx : kModeF32; }
     bool ok;
 };
@@ -1233,13 +1269,24 @@ inline FusedPlan plan_fused(const RglGraph& g, const RglMlp& head, int P, int A,
     return pl;
 }
 
-template <int HR, int NT, bool SKIP, bool SOFT, bool BX = false>
+// the plans the prologue form is instantiated for: bf16x6, 17..20 nodes, softmax similarity; and its scene region fits the LDS
+inline bool prologue_form(const FusedPlan& pl, int scene_floats) {
+    return pl.ok && pl.bx && pl.hr == 20 && pl.nt == 2 && pl.a.sim == SIM_SOFTMAX && scene_floats > 0 &&
+           (size_t)(kPrologueSceneBase<FusedLds<32, 100, 100, true>> + scene_floats) * sizeof(float) <= pl.lds_bytes;
+}
+
+template <int HR, int NT, bool SKIP, bool SOFT, bool BX = false, bool PRO = false>
 int launch_fused_ts(const FusedPlan& pl, hipStream_t st) {
-    auto kern = children_fused_kernel<HR, NT, SKIP, SOFT, 32, 100, 100, BX>;
+    auto kern = children_fused_kernel<HR, NT, SKIP, SOFT, 32, 100, 100, BX, PRO>;
     RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)pl.lds_bytes));
     const int grid = pl.grid;                        // persistent, one 8-wave workgroup per CU (LDS-bound)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kFusedWaves * 64), pl.lds_bytes, st, pl.a);
+    PrologueArgs<PRO> pa{};
+    if constexpr (PRO) {
+        pa.scene = pl.pro->scene;
+        pa.children = pl.pro->children;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kFusedWaves * 64), pl.lds_bytes, st, pl.a, pa);
     RGL_LAUNCH_CHECK();
     return RGL_OK;
 }
@@ -1252,6 +1299,8 @@ int launch_fused_t(const FusedPlan& pl, hipStream_t st) {
 }
 
 inline int launch_fused(const FusedPlan& pl, bool skip, hipStream_t st) {
+    if (pl.pro)          // the only instantiations with the prologue (prologue_form)
+        return skip ? launch_fused_ts<20, 2, true, true, true, true>(pl, st) : launch_fused_ts<20, 2, false, true, true, true>(pl, st);
     switch (pl.hr) {
         case 8: return skip ? launch_fused_t<8, 1, true>(pl, st) : launch_fused_t<8, 1, false>(pl, st);
         case 20: return pl.nt == 1 ? (skip ? launch_fused_t<20, 1, true>(pl, st) : launch_fused_t<20, 1, false>(pl, st))
@@ -1303,8 +1352,10 @@ int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, in
 int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, int H, const float* child_robot,
                           const float* humans_next, float* child_value, void* workspace, size_t workspace_bytes,
                           int image_ready, hipStream_t stream, const float* caller_image, const void* tail, size_t tail_bytes,
-                          int* tail_done, int mode) {
+                          int* tail_done, int mode, const void* prologue, size_t prologue_bytes) {
     if (tail_done) *tail_done = 0;
+    const LevelPrologue* lp = (prologue && prologue_bytes == sizeof(LevelPrologue)) ? (const LevelPrologue*)prologue : nullptr;
+    if (prologue && !lp) return RGL_ERR_BAD_MODE;
     // the search's tail: selection always; the back-up chain + root step at the deepest level when handing whole roots to
     // workgroups does not starve the GPU (few roots with many parents each -- unclipped deep searches -- keep unit = 1)
     const TailArgs* ta = (tail && tail_bytes == sizeof(TailArgs) && ((const TailArgs*)tail)->enabled) ? (const TailArgs*)tail : nullptr;
@@ -1322,6 +1373,10 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
         }
     }
     FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);
+    if (lp) {
+        if (!prologue_form(fp, lp->scene_floats)) return RGL_ERR_BAD_MODE;      // fused_prologue_fits was not asked
+        fp.pro = lp;
+    }
     // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch), and of 17..20 with a
     // plain-weight similarity (unpacked row pass: 172 944 bytes), do not fit a CU with it -- they run the f32 form of this kernel on
     // an f32 image packed here (the caller's image is in the other layout; tests/test_bf16x6_kernels.py pins the envelope)
@@ -1355,6 +1410,19 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
     const int rc = launch_fused(fp, g->skip_connection != 0, stream);
     if (rc == RGL_OK && ta && tail_done) *tail_done = chain ? 2 : 1;
     return rc;
+}
+
+// Measured (profiles/level_prologue_ab.txt): with 8 and 16 parents per workgroup (configs[2]: 2048 roots) the one launch is 3 % faster
+// per step than the three; with 1 and 2 (the 256-root share) it is 6 % slower -- one scene chain per busy wave and most waves idle
+// through it, where the stand-alone split scene kernel spreads each scene over two waves.  Below 4 parents per CU the level keeps
+// its three launches.
+constexpr int kPrologueMinParentsPerCu = 4;
+
+bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, int scene_floats) {
+    if (pl->contraction_dtype != RGL_CONTRACT_BF16X6 || head_variant(pl->value_head) < 0) return false;
+    if (P < kPrologueMinParentsPerCu * fused_cu_count() - (fused_cu_count() - 1)) return false;     // ceil(P / CUs) < 4
+    if (workspace_bytes < value_children_workspace_bytes(pl, P, H)) return false;         // launch_value_children's `staged`
+    return prologue_form(plan_fused(pl->value_graph, pl->value_head, P, pl->num_actions, H, 1, kModeBx), scene_floats);
 }
 
 }  // namespace rgl

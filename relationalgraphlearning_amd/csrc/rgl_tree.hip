@@ -6,7 +6,7 @@
 // Follows (reference paths): crowd_nav/policy/model_predictive_rl.py:192-357 (predict,
 // action_clip, V_planning, estimate_reward), state_predictor.py:41-60,109-118,
 // crowd_sim/envs/utils/utils.py:4-26, multi_human_rl.py:36-96, cadrl.py:113-138,241-276.
-#include "rgl_children.h"
+#include "rgl_scene_body.h"
 #include "rgl_tail.h"
 
 #include <cstdlib>
@@ -318,6 +318,18 @@ int expand_level(const MprlPlanner& pl, const float* robot, const float* humans,
     ca.robot64 = roots64 ? pl.root_robot_f64 : nullptr;
     ca.humans64 = roots64 ? pl.root_humans_f64 : nullptr;
     int children_done = 0;              // set when the state predictor's scene kernel ran them on its extra workgroups
+    // The level as ONE launch where the fused children kernel's prologue form covers it (bf16x6, 17..20-node crowds, softmax
+    // similarity): each workgroup runs the state predictor and the reward / next-state pairs of the parents it owns, then their
+    // children.  Traced searches keep the three launches (predictor_ms / children_ms).  RGL_LEVEL_PROLOGUE=0: the three launches.
+    static const bool prologue_on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
+    LevelPrologue lp;
+    const bool fold = prologue_on && !before_children &&
+                      rgl::level_prologue_args(&pl, robot, humans, humans_per, P, H, humans_next, sp_image, &ca, sizeof(ca), &lp,
+                                               sizeof(lp)) == 0 &&
+                      rgl::fused_prologue_fits(&pl, P, H, scratch_bytes, lp.scene_floats);
+    if (fold)
+        return rgl::launch_value_children(&pl, child_robot, humans_next, P, H, child_value, scratch, scratch_bytes, st, image_ready,
+                                          tail, tail ? sizeof(TailArgs) : 0, tail_done, &lp, sizeof(lp));
     // (Round 6: the reward work inside the children launch -- every workgroup for the parents it owns, in its prologue under the
     // weight image's DMA, inputs staged in LDS -- was built and measured: the embedding launch drops from 13.6 / 15.6 to 7.9 / 7.3 us,
     // the children launches grow by 7.3 / 5.9: 277.6 against 279.0 us per 2048-root step, not worth a second home for that code;

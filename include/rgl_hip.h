@@ -485,6 +485,34 @@ typedef struct CrowdOrcaParams {
 int crowd_orca_humans_f64(const CrowdOrcaParams* params, const double* robot, const double* humans, const double* human_goals, const double* human_vpref, const int* done, int B, int H, int robot_visible, double* out, rgl_stream_t stream);
 int crowd_orca_robot_f64(const CrowdOrcaParams* params, const double* robot, const double* humans, const int* done, int B, int H, double* out, rgl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Seeded scenes on device (ABI 8, additive): CrowdSim.reset's generate_human loop (crowd_sim/envs/crowd_sim.py:117-169,
+ * 185-203) for B cases in one launch.  Case b replays np.random.RandomState(seeds[b]) -- MT19937 seeded by init_genrand,
+ * random_sample() as the 53-bit double of two outputs -- bit for bit and makes the accept / reject decisions of the sequential
+ * loop in float64 without contraction, so positions, radii and v_pref are the host generator's; circle_crossing positions
+ * differ from it only by the device's sin / cos against the host libm's (a few ulp).
+ *   seeds device [B]; robot [B][9], humans [B][H][5], goals [B][H][2], vpref [B][H] (the layout crowd_step_f64 takes)
+ *   status [B]: 0, or 1 when some human was not placed within max_attempts attempts (upstream's loop has no exit): that
+ *     case's other outputs are unspecified.  draws [B]: random_sample / uniform calls consumed.
+ * Errors: RGL_ERR_NULL for a missing pointer, RGL_ERR_BAD_SHAPE for B, H < 1, H + 1 > RGL_MAX_NODES or max_attempts < 1,
+ * RGL_ERR_BAD_MODE for an unknown scenario.
+ * ------------------------------------------------------------------------------------------- */
+enum { CROWD_SCENARIO_CIRCLE_CROSSING = 0, CROWD_SCENARIO_SQUARE_CROSSING = 1 };
+
+typedef struct CrowdSceneConfig {
+    double circle_radius;       /* sim.circle_radius (4): robot at (0, -R) heading for (0, R)                */
+    double square_width;        /* sim.square_width (20)                                                      */
+    double discomfort_dist;     /* reward.discomfort_dist (0.2): part of the clearance margin                 */
+    double robot_radius, robot_v_pref;
+    double human_radius, human_v_pref;   /* replaced by uniform(0.3, 0.5) / uniform(0.5, 1.5) draws when randomize_attributes */
+    int scenario;               /* CROWD_SCENARIO_*                                                           */
+    int randomize_attributes;
+    int max_attempts;           /* per human, position and goal attempts together                             */
+    int reserved;
+} CrowdSceneConfig;
+
+int crowd_generate_scenes_f64(const CrowdSceneConfig* cfg, const unsigned* seeds, int B, int H, double* robot, double* humans, double* goals, double* vpref, int* status, int* draws, rgl_stream_t stream);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

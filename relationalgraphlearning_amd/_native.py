@@ -82,6 +82,16 @@ CROWD_ORCA_MAX_NEIGHBORS = 32
 ORCA_MAX_SPEED_RULES = {"one": 0, "v_pref": 1}
 
 
+class CrowdSceneConfig(C.Structure):
+    _fields_ = [("circle_radius", C.c_double), ("square_width", C.c_double), ("discomfort_dist", C.c_double),
+                ("robot_radius", C.c_double), ("robot_v_pref", C.c_double), ("human_radius", C.c_double),
+                ("human_v_pref", C.c_double), ("scenario", C.c_int), ("randomize_attributes", C.c_int),
+                ("max_attempts", C.c_int), ("reserved", C.c_int)]
+
+
+CROWD_SCENARIOS = {"circle_crossing": 0, "square_crossing": 1}
+
+
 class MprlLevelView(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in
                 ("n_parents", "robot_off", "humans_off", "humans_next_off", "child_robot_off", "reward_off",
@@ -141,6 +151,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "crowd_orca_robot_f64": (C.c_int, [C.POINTER(CrowdOrcaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
+    "crowd_generate_scenes_f64": (C.c_int, [C.POINTER(CrowdSceneConfig), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }

@@ -19,6 +19,19 @@ from .nets import _stream
 INFO = {0: "", 1: "Discomfort", 2: "Collision", 3: "Reaching goal", 4: "Timeout", 5: "(finished earlier)"}
 HUMAN_POLICY = {"given": 0, "linear": 1, "constant_velocity": 2, "orca": 0}     # orca: crowd_orca_humans_f64, then GIVEN
 BASE_SEED = {"train": 2000, "val": 0, "test": 1000}       # crowd_sim.py:185-186 with its case capacities
+# Default attempt cap per human of the device generator (the reference's placement loop has none).  Measured with the host
+# generator's restatement (tests/scenegen_cpu.py) over circle_crossing H = 5 (randomize_attributes off and on), 10, 19 and
+# square_crossing H = 4, 12, 19 (off and on), cases test 0-499 (H = 19 circle: 0-199), val 0-99, train 0-255 and the last 64
+# train cases: the largest attempt count of any single human was 30 094 (19-human circle; the next configuration, the 10-human
+# circle, needed 59, every square at most 7).  Margin 8.  The cap is there to bound a launch, not to clear every case, which on
+# the 19-human circle no cap does: its attempt counts have a power-law tail (of 262 144 fresh train cases, 36 took more than
+# 300 000 draws under this cap and 19 were flagged, one case in 13 800; with a cap of 4 000 000 three took more than 3 000 000
+# draws and one was still flagged -- profiles/scenegen.txt).  8 x 30 094 attempts are about 4 600 rounds of 64 attempts, some 20 ms
+# of kernel time for one human, so a hopeless case costs a launch tens of milliseconds; the cap clears every test configuration
+# eight times over and flagged none of 262 144 train cases with 15 humans or fewer.  Training on the 19-human circle wants
+# scene_on_unplaced = "host" or a larger cap.
+SCENE_MAX_ATTEMPTS_MEASURED = 30094
+SCENE_MAX_ATTEMPTS = 8 * SCENE_MAX_ATTEMPTS_MEASURED
 
 
 class SimConfig(object):
@@ -32,6 +45,10 @@ class SimConfig(object):
         self.human_radius, self.human_v_pref = 0.3, 1
         self.robot_radius, self.robot_v_pref = 0.3, 1
         self.robot_visible, self.centralized_planning = False, True          # config.py:37, 47 (read by human_policy "orca")
+        # not upstream's: who generates reset()'s scenes ("host": generate_scene, memoised; "device": generate_scenes_device) and
+        # the device generator's attempt cap per human and what reset() does with a case that reaches it
+        self.scene_generator, self.scene_max_attempts = "host", SCENE_MAX_ATTEMPTS
+        self.scene_on_unplaced = "raise"                 # device generator, a case at the cap: "raise" | "host" (generate_scene)
         for k, v in over.items():
             if not hasattr(self, k):
                 raise AttributeError(k)
@@ -104,6 +121,76 @@ def generate_scene(cfg, phase, case):
     return robot, np.array(humans), np.array(goals), np.array(vprefs, dtype=np.float64)
 
 
+class UnplacedSceneError(RuntimeError):
+    """The device generator gave up on some cases (`cases`: their (phase, case) pairs)."""
+
+    def __init__(self, message, cases):
+        RuntimeError.__init__(self, message)
+        self.cases = cases
+
+
+def _scene_config(cfg):
+    if cfg.scenario not in nat.CROWD_SCENARIOS:
+        raise NotImplementedError(cfg.scenario)
+    c = nat.CrowdSceneConfig()
+    c.circle_radius, c.square_width, c.discomfort_dist = cfg.circle_radius, cfg.square_width, cfg.discomfort_dist
+    c.robot_radius, c.robot_v_pref = cfg.robot_radius, cfg.robot_v_pref
+    c.human_radius, c.human_v_pref = cfg.human_radius, cfg.human_v_pref
+    c.scenario, c.randomize_attributes = nat.CROWD_SCENARIOS[cfg.scenario], int(bool(cfg.randomize_attributes))
+    c.max_attempts = int(cfg.scene_max_attempts)
+    return c
+
+
+def _launch_scene_generator(cfg, phase, cases, device):
+    """crowd_generate_scenes_f64 for `cases`: (robot, humans, goals, v_pref, status, draws) on `device`, flagged cases and all."""
+    device = torch.device(device)
+    seeds = np.asarray(cases, np.int64) + BASE_SEED[phase]
+    if len(cases) == 0 or seeds.min() < 0 or seeds.max() > 0xFFFFFFFF:
+        raise ValueError("cases must be a non-empty list whose seeds (%d + case) fit 32 bits" % BASE_SEED[phase])
+    B, H = len(cases), int(cfg.human_num)
+    seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32)).to(device)
+    robot = torch.empty(B, 9, dtype=torch.float64, device=device)
+    humans = torch.empty(B, H, 5, dtype=torch.float64, device=device)
+    goals = torch.empty(B, H, 2, dtype=torch.float64, device=device)
+    vpref = torch.empty(B, H, dtype=torch.float64, device=device)
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    draws = torch.empty(B, dtype=torch.int32, device=device)
+    c = _scene_config(cfg)
+    with torch.cuda.device(device):
+        rc = nat.lib().crowd_generate_scenes_f64(C.byref(c), seeds_d.data_ptr(), B, H, robot.data_ptr(), humans.data_ptr(),
+                                                 goals.data_ptr(), vpref.data_ptr(), status.data_ptr(), draws.data_ptr(),
+                                                 _stream())
+    nat.check(rc, "crowd_generate_scenes_f64")
+    return robot, humans, goals, vpref, status, draws
+
+
+def generate_scenes_device(cfg, phase, cases, device, on_unplaced="raise"):
+    """generate_scene for every case of `cases` in one launch (crowd_generate_scenes_f64): (robot (B,9), humans (B,H,5), goals
+    (B,H,2), v_pref (B,H), status (B,) int32, draws (B,) int32) on `device`, float64.  Same stream, same accept / reject
+    decisions as the host generator; circle_crossing positions differ from it by the device's sin / cos (a few ulp).
+    A case in which some human is not placed within cfg.scene_max_attempts attempts has status 1: on_unplaced="raise" raises
+    UnplacedSceneError naming those cases, "host" fills them in with generate_scene (which has no cap: like upstream, it does
+    not return when there is no room for the human)."""
+    if on_unplaced not in ("raise", "host"):
+        raise ValueError("on_unplaced must be 'raise' or 'host', not %r" % (on_unplaced,))
+    cases = [int(k) for k in cases]
+    robot, humans, goals, vpref, status, draws = _launch_scene_generator(cfg, phase, cases, device)
+    unplaced = torch.nonzero(status).flatten().tolist()           # one synchronisation per call: the cap must not pass silently
+    if unplaced:
+        what = ("%d of %d %s cases were not placed within scene_max_attempts = %d attempts per human (%s, human_num = %d, "
+                "randomize_attributes = %s): cases %s" % (len(unplaced), len(cases), phase, int(cfg.scene_max_attempts), cfg.scenario,
+                                                          int(cfg.human_num), bool(cfg.randomize_attributes),
+                                                          [cases[b] for b in unplaced]))
+        if on_unplaced == "raise":
+            raise UnplacedSceneError(what + ".  Raise SimConfig.scene_max_attempts, or use on_unplaced='host' (SimConfig."
+                                     "scene_on_unplaced) to hand them to the host generator, which has no cap and may never "
+                                     "return.", [(phase, cases[b]) for b in unplaced])
+        for b in unplaced:
+            r, h, g, v = generate_scene(cfg, phase, cases[b])
+            robot[b], humans[b], goals[b], vpref[b] = (torch.as_tensor(a, dtype=torch.float64).to(robot.device) for a in (r, h, g, v))
+    return robot, humans, goals, vpref, status, draws
+
+
 class BatchedCrowdSim(object):
     def __init__(self, device, config=None, human_policy="linear", kinematics="holonomic"):
         self.cfg = config or SimConfig()
@@ -116,8 +203,16 @@ class BatchedCrowdSim(object):
         self._scene_cache = {}
 
     # -- state ---------------------------------------------------------------------------------------------------
-    def reset(self, phase, cases):
-        """Load seeded cases (one environment each).  Returns the fp32 observation (robot (B,9), humans (B,H,5))."""
+    def reset(self, phase, cases, generator=None):
+        """Load seeded cases (one environment each).  Returns the fp32 observation (robot (B,9), humans (B,H,5)).
+        generator: "host" (generate_scene per case, memoised), "device" (generate_scenes_device: one launch, nothing memoised,
+        no copy through the host; an unplaced case raises or goes to the host generator, cfg.scene_on_unplaced), None: cfg.scene_generator."""
+        generator = self.cfg.scene_generator if generator is None else generator
+        if generator == "device":
+            robot, humans, goals, vpref, _, _ = generate_scenes_device(self.cfg, phase, cases, self.device, self.cfg.scene_on_unplaced)
+            return self._load_tensors(robot, humans, goals, vpref)
+        if generator != "host":
+            raise ValueError("unknown scene generator %r" % (generator,))
         scenes = []
         for k in cases:                      # scene generation is sequential host work (seeded rejection sampling): memoise
             key = (phase, int(k), self.cfg.scenario, self.cfg.human_num, self.cfg.randomize_attributes, self.cfg.circle_radius,
@@ -130,11 +225,17 @@ class BatchedCrowdSim(object):
 
     def load(self, robot, humans, human_goals=None, human_vpref=None):
         dev = self.device
-        self.robot = torch.as_tensor(np.asarray(robot, np.float64)).to(dev).contiguous()
-        self.humans = torch.as_tensor(np.asarray(humans, np.float64)).to(dev).contiguous()
+        return self._load_tensors(
+            torch.as_tensor(np.asarray(robot, np.float64)).to(dev).contiguous(),
+            torch.as_tensor(np.asarray(humans, np.float64)).to(dev).contiguous(),
+            None if human_goals is None else torch.as_tensor(np.asarray(human_goals, np.float64)).to(dev).contiguous(),
+            None if human_vpref is None else torch.as_tensor(np.asarray(human_vpref, np.float64)).to(dev).contiguous())
+
+    def _load_tensors(self, robot, humans, human_goals, human_vpref):
+        """load() for contiguous float64 tensors already on the device (the simulator keeps them: its steps write in place)."""
+        dev = self.device
+        self.robot, self.humans, self.human_goals, self.human_vpref = robot, humans, human_goals, human_vpref
         self.B, self.H = self.robot.shape[0], self.humans.shape[1]
-        self.human_goals = None if human_goals is None else torch.as_tensor(np.asarray(human_goals, np.float64)).to(dev).contiguous()
-        self.human_vpref = None if human_vpref is None else torch.as_tensor(np.asarray(human_vpref, np.float64)).to(dev).contiguous()
         self.time = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.done = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._r32 = torch.empty(self.B, 9, dtype=torch.float32, device=dev)

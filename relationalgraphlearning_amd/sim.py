@@ -191,6 +191,17 @@ def generate_scenes_device(cfg, phase, cases, device, on_unplaced="raise"):
     return robot, humans, goals, vpref, status, draws
 
 
+def check_action_shapes(robot_actions, human_actions, B, H):
+    """ValueError unless robot_actions is (B, 2) and human_actions, if any, (B, H, 2): crowd_step_f64 reads exactly that many
+    values from each and knows nothing of their sizes.  Takes tensors, arrays or bare shapes; needs no device."""
+    for what, x, want in (("robot_actions", robot_actions, (int(B), 2)), ("human_actions", human_actions, (int(B), int(H), 2))):
+        if x is None:
+            continue
+        shape = tuple(x.shape) if hasattr(x, "shape") else tuple(x)
+        if shape != want:
+            raise ValueError("%s must have shape %s, not %s" % (what, want, shape))
+
+
 class BatchedCrowdSim(object):
     def __init__(self, device, config=None, human_policy="linear", kinematics="holonomic"):
         self.cfg = config or SimConfig()
@@ -231,15 +242,26 @@ class BatchedCrowdSim(object):
             None if human_goals is None else torch.as_tensor(np.asarray(human_goals, np.float64)).to(dev).contiguous(),
             None if human_vpref is None else torch.as_tensor(np.asarray(human_vpref, np.float64)).to(dev).contiguous())
 
-    def _load_tensors(self, robot, humans, human_goals, human_vpref):
-        """load() for contiguous float64 tensors already on the device (the simulator keeps them: its steps write in place)."""
-        dev = self.device
+    def _owned(self, given, shape, dtype, what):
+        """A caller-owned buffer after its check, or a fresh one."""
+        if given is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if (tuple(given.shape) != tuple(shape) or given.dtype != dtype or given.device != self.robot.device
+                or not given.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (what, dtype, tuple(shape), self.robot.device))
+        return given
+
+    def _load_tensors(self, robot, humans, human_goals, human_vpref, time=None, done=None, obs=None):
+        """load() for contiguous float64 tensors already on the device (the simulator keeps them: its steps write in place).
+        Optional caller-owned buffers, which the simulator then keeps as well: time (B,) float64 and done (B,) int32 (both
+        zeroed here), obs = (robot (B, 9), humans (B, H, 5)) float32 for the observation."""
         self.robot, self.humans, self.human_goals, self.human_vpref = robot, humans, human_goals, human_vpref
         self.B, self.H = self.robot.shape[0], self.humans.shape[1]
-        self.time = torch.zeros(self.B, dtype=torch.float64, device=dev)
-        self.done = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self._r32 = torch.empty(self.B, 9, dtype=torch.float32, device=dev)
-        self._h32 = torch.empty(self.B, self.H, 5, dtype=torch.float32, device=dev)
+        dev = self.device
+        self.time = self._owned(time, (self.B,), torch.float64, "time").zero_()
+        self.done = self._owned(done, (self.B,), torch.int32, "done").zero_()
+        self._r32 = self._owned(None if obs is None else obs[0], (self.B, 9), torch.float32, "obs[0]")
+        self._h32 = self._owned(None if obs is None else obs[1], (self.B, self.H, 5), torch.float32, "obs[1]")
         self._orca = torch.zeros(self.B, self.H, 2, dtype=torch.float64, device=dev) if self.human_policy == "orca" else None
         return self.observe()
 
@@ -254,6 +276,8 @@ class BatchedCrowdSim(object):
         c.time_step, c.time_limit = self.cfg.time_step, self.cfg.time_limit
         c.success_reward, c.collision_penalty = self.cfg.success_reward, self.cfg.collision_penalty
         c.discomfort_dist, c.discomfort_penalty_factor = self.cfg.discomfort_dist, self.cfg.discomfort_penalty_factor
+        if self.kinematics not in nat.KINEMATICS:
+            raise ValueError("unknown kinematics %r" % (self.kinematics,))
         c.kinematics = nat.KINEMATICS[self.kinematics]
         c.human_policy = HUMAN_POLICY[self.human_policy]
         return c
@@ -271,17 +295,20 @@ class BatchedCrowdSim(object):
                                      self.cfg.centralized_planning, out)
 
     # -- dynamics ------------------------------------------------------------------------------------------------
-    def step(self, robot_actions, human_actions=None, update=True):
+    def step(self, robot_actions, human_actions=None, update=True, out=None):
         """robot_actions (B,2) float64 (vx,vy)|(v,r).  Returns (obs, reward (B,) fp32, done (B,) bool, info (B,) int32);
-        `self.last_dmin` holds the closest approach (Discomfort.min_dist).  Finished environments stay frozen."""
+        `self.last_dmin` holds the closest approach (Discomfort.min_dist).  Finished environments stay frozen.
+        out: optional caller-owned (reward (B,) float32, info (B,) int32, dmin (B,) float64) the step writes instead of
+        allocating."""
         dev = self.device
         act = torch.as_tensor(robot_actions, dtype=torch.float64).to(dev).contiguous()
         ha = None if human_actions is None else torch.as_tensor(human_actions, dtype=torch.float64).to(dev).contiguous()
+        check_action_shapes(act, ha, self.B, self.H)
         if ha is None and update and self.human_policy == "orca":
             ha = self._orca_humans(self.robot, self.humans, self.human_goals, self.human_vpref, self.done, self._orca)
-        reward = torch.empty(self.B, dtype=torch.float32, device=dev)
-        info = torch.empty(self.B, dtype=torch.int32, device=dev)
-        dmin = torch.empty(self.B, dtype=torch.float64, device=dev)
+        reward = self._owned(None if out is None else out[0], (self.B,), torch.float32, "out[0]")
+        info = self._owned(None if out is None else out[1], (self.B,), torch.int32, "out[1]")
+        dmin = self._owned(None if out is None else out[2], (self.B,), torch.float64, "out[2]")
         cfg = self._config()
         with torch.cuda.device(dev):
             rc = nat.lib().crowd_step_f64(C.byref(cfg), self.robot.data_ptr(), self.humans.data_ptr(),
@@ -305,8 +332,13 @@ class BatchedCrowdSim(object):
         (multi_human_rl.py:43-44)."""
         dev = self.device
         act = torch.as_tensor(actions, dtype=torch.float64).to(dev).contiguous()
+        if act.dim() != 2:
+            raise ValueError("actions must have shape (A, 2), not %s" % (tuple(act.shape),))
         A = act.shape[0]
+        check_action_shapes(act, None, A, self.H)
         b = int(env_index)
+        if A < 1 or not 0 <= b < self.B:
+            raise ValueError("onestep_lookahead_actions needs at least one action and an env_index in [0, %d)" % self.B)
         robot = self.robot[b:b + 1].repeat(A, 1).contiguous()
         humans = self.humans[b:b + 1].repeat(A, 1, 1).contiguous()
         goals = None if self.human_goals is None else self.human_goals[b:b + 1].repeat(A, 1, 1).contiguous()
@@ -331,10 +363,12 @@ class BatchedCrowdSim(object):
         return humans, reward
 
 
-def run_episodes(sim, policy, phase, cases, gamma=0.9, max_steps=None):
+def run_episodes(sim, policy, phase, cases, gamma=0.9, max_steps=None, on_step=None):
     """Explorer.run_k_episodes for len(cases) environments in lock-step: the policy decides for every live environment
     at once (`predict_batch`), the simulator advances them together.  Returns per-case outcome codes, times and
-    discounted cumulative rewards plus the aggregate statistics the reference logs."""
+    discounted cumulative rewards plus the aggregate statistics the reference logs.
+    on_step(t, actions (B, 2) float64, info (B,) int32), if given, is called after every step with the actions the step took
+    (device tensors; a finished environment's row is what the policy chose for its frozen state and moved nothing)."""
     robot32, humans32 = sim.reset(phase, cases)
     B = sim.B
     if policy.action_space is None:
@@ -351,7 +385,10 @@ def run_episodes(sim, policy, phase, cases, gamma=0.9, max_steps=None):
         if not bool(live.any()):
             break
         act_idx, _ = policy.predict_batch(robot32, humans32, roots_are_joint_states=True)
-        (robot32, humans32), reward, done, info = sim.step(table[act_idx.long()])
+        actions = table[act_idx.long()]
+        (robot32, humans32), reward, done, info = sim.step(actions)
+        if on_step is not None:
+            on_step(t, actions, info)
         cum += disc * reward.double()
         discomfort_steps += (info == 1).int()
         ended = (info >= 2) & (info <= 4)

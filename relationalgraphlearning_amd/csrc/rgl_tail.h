@@ -42,6 +42,23 @@ struct TailArgs {
     int* root_kept;           // [B][W] or null
 };
 
+// One fp32 operation, rounded on its own.  The bookkeeping's arithmetic is the reference's chain of tensor operations -- a product
+// and the sum that takes it are two roundings -- and tests/search_bookkeeping.py replays it bit for bit.  The toolchain's
+// __fmul_rn / __fadd_rn are the plain operators, which the default -ffp-contract fuses into one fma (one rounding: a last-bit
+// difference in value1 and in every backed-up value); an operation compiled under `contract(off)` takes no part in a fusion.
+__device__ __forceinline__ float f32_mul(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ float f32_add(float x, float y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+__device__ __forceinline__ float f32_div(float x, float y) {
+#pragma clang fp contract(off)
+    return x / y;
+}
+
 __device__ __forceinline__ int tail_fallback(const int* kl, int k) { return k > 0 ? kl[k - 1] : 0; }
 
 // One WAVE, parent p of level t.level: one-step values, top-w clipping (argpartition semantics; sparse: one action per group in
@@ -84,7 +101,7 @@ __device__ __forceinline__ void tail_select(const TailArgs& t, int p, int* kl) {
         const int a = lane + 64 * k;
         val[k] = 0.f;
         if (avail[k]) {
-            val[k] = __fadd_rn(rwr[k], __fmul_rn(gamma_f, cvr[k]));
+            val[k] = f32_add(rwr[k], f32_mul(gamma_f, cvr[k]));
             v1[a] = val[k];
             if (deepest) { cvl[a] = cvr[k]; rwl[a] = rwr[k]; }
         }
@@ -170,14 +187,14 @@ __device__ __forceinline__ void tail_select(const TailArgs& t, int p, int* kl) {
             const TailLevel& U = t.lv[t.level - 1];
             const int d = 2;
             const int q = p / W, slot = p - q * W;
-            const float v_over_d = __fdiv_rn(v_up, (float)d);
+            const float v_over_d = f32_div(v_up, (float)d);
             const float c = (float)((double)(d - 1) / (double)d);
             float best = 0.f;
             int bk = -1;
             for (int k = 0; k < W; ++k) {
                 const int a = kl[k];
-                const float inner = __fadd_rn(__fmul_rn(gamma_f, cvl[a]), rwl[a]);
-                const float ret = __fadd_rn(v_over_d, __fmul_rn(c, inner));
+                const float inner = f32_add(f32_mul(gamma_f, cvl[a]), rwl[a]);
+                const float ret = f32_add(v_over_d, f32_mul(c, inner));
                 if (bk < 0 || ret > best) {
                     best = ret;
                     bk = k;
@@ -198,14 +215,14 @@ __device__ __forceinline__ void tail_backup(const TailArgs& t, int l, int p) {
     const int A = t.A, W = t.W, d = t.D - l + 1;
     const int q = p / W, slot = p - q * W;
     const float v = U.child_value[(size_t)q * A + U.keep[(size_t)q * W + slot]];
-    const float v_over_d = __fdiv_rn(v, (float)d);
+    const float v_over_d = f32_div(v, (float)d);
     const float c = (float)((double)(d - 1) / (double)d);
     float best = 0.f;
     int bk = -1;
     for (int k = 0; k < W; ++k) {
         const float r = L.reward[(size_t)p * A + L.keep[(size_t)p * W + k]];
-        const float inner = __fadd_rn(__fmul_rn(t.gamma_f, L.backup[(size_t)p * W + k]), r);
-        const float ret = __fadd_rn(v_over_d, __fmul_rn(c, inner));
+        const float inner = f32_add(f32_mul(t.gamma_f, L.backup[(size_t)p * W + k]), r);
+        const float ret = f32_add(v_over_d, f32_mul(c, inner));
         if (bk < 0 || ret > best) {
             best = ret;
             bk = k;
@@ -226,7 +243,7 @@ __device__ __forceinline__ void tail_root(const TailArgs& t, int b, int sub, boo
     if (live) {
         for (int k = sub; k < W; k += kRootLanes) {
             const int a = L.keep[(size_t)b * W + k];
-            const float val = __fadd_rn(L.reward[(size_t)b * A + a], __fmul_rn(t.gamma_f, L.backup[(size_t)b * W + k]));
+            const float val = f32_add(L.reward[(size_t)b * A + a], f32_mul(t.gamma_f, L.backup[(size_t)b * W + k]));
             if (t.root_values) t.root_values[(size_t)b * W + k] = val;
             if (t.root_kept) t.root_kept[(size_t)b * W + k] = a;
             if (val > best) {                  // strict '>' keeps the first maximum (:228)

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void mprl_select_kernel(const TailArgs t) {
 __global__ void one_step_value_kernel(const float* __restrict__ r, const float* __restrict__ v, float g, long long n,
                                       float* __restrict__ o) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = __fadd_rn(r[i], __fmul_rn(g, v[i]));
+    if (i < n) o[i] = f32_add(r[i], f32_mul(g, v[i]));      // two roundings (rgl_tail.h)
 }
 
 // Level l >= 1, one thread per parent (tail_backup); 16 lanes per root (tail_root).

@@ -133,7 +133,7 @@ int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_head, const
 
 /* ---------------------------------------------------------------------------------------------
  * rgl_graph_backward_f32 -- gradients of rgl_graph_forward_f32's outputs with respect to every
- * parameter, summed over the n_scenes scenes (deterministic: per-scene slabs reduced in scene order).
+ * parameter, summed over the n_scenes scenes (deterministic: per-scene slabs reduced in scene order, 256 scenes to a partial sum).
  * Replaces: torch autograd through RGL.forward / ValueEstimator.forward / StatePredictor.forward /
  * gcn.ValueNetwork.forward as driven by MPRLTrainer / VNRLTrainer (crowd_nav/utils/trainer.py:110-161,
  * 199-250).  Supported: all eight similarity functions, layerwise_graph 0 | 1.  Two implementations behind this entry point:
@@ -162,6 +162,27 @@ int rgl_graph_backward_f32(const RglGraph* graph, const RglMlp* value_head, cons
                            const float* robot, const float* humans, int n_scenes, int H, int detach_graph,
                            const float* d_value, const float* d_humans_next, const float* d_H,
                            float* grad_out, void* workspace, size_t workspace_bytes, rgl_stream_t stream);
+
+/* rgl_plan_mlp_rows (ABI 8, additive) -- which launch form the MFMA row kernels (rgl_backward_mfma.hip) take for one MLP over
+ * n_rows rows: the tile pipeline runs w_r (a row per scene), w_h (a row per human), the value head (a row per scene) and the
+ * motion head (a row per human) as such jobs, in the backward pass and in the forward of models outside the shipped shapes.
+ * HOST ONLY: no device call, no launch; reads n_layers and dims of `mlp` (the weight pointers are not read).  max_waves: the
+ * most waves (= gradient slabs) the job may use: 2048, halved by the backward while the caller's workspace is short.
+ *   kind          1: head_rows_kernel (weights from L2, a workgroup per 16-row tile); 10 T0 + T2: mlp2_rows_kernel<T0, T2>
+ *                 (two layers, hidden width 64, T0 / T2 16-column tiles of input / output); 0: mlp_rows_kernel
+ *   coop          1: a workgroup shares one tile; 2: the same with the weights staged a layer at a time; 0: a tile per wave
+ *   waves_per_wg  waves (LDS slices) per workgroup; 0: the MLP fits none of the forms (the pipeline answers "not mine")
+ *   n_tiles       16-row tiles; n_waves = min(n_tiles, max_waves) waves walk them (jobs of kinds >= 10 that share a launch are
+ *                 rebalanced afterwards); n_wgs workgroups
+ *   direct        the process's RGL_HEAD_ROWS_DIRECT setting as the planner read it (once): 0 = kind 1 is never chosen
+ *   lds_bytes     dynamic LDS the job asks for (a launch of two jobs takes the larger)
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (depth or a width outside the limits above, n_rows < 1, max_waves < 1). */
+typedef struct RglRowsPlan {
+    int kind, coop, waves_per_wg, n_waves, n_tiles, n_wgs;
+    int direct, reserved;
+    size_t lds_bytes;
+} RglRowsPlan;
+int rgl_plan_mlp_rows(const RglMlp* mlp, int n_rows, int max_waves, RglRowsPlan* plan);
 
 /* rgl_transpose_f32 -- dst[c][r] = src[r][c]; turns a torch Linear weight (out,in) into the
  * k-major layout RglMlp wants.  Host-side convenience of this ABI (no reference counterpart). */

@@ -44,6 +44,11 @@ class RglGatherJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_floats", C.c_int), ("src_rows", C.c_int)]
 
 
+class RglRowsPlan(C.Structure):
+    _fields_ = [("kind", C.c_int), ("coop", C.c_int), ("waves_per_wg", C.c_int), ("n_waves", C.c_int), ("n_tiles", C.c_int),
+                ("n_wgs", C.c_int), ("direct", C.c_int), ("reserved", C.c_int), ("lds_bytes", C.c_size_t)]
+
+
 class RglGraph(C.Structure):
     _fields_ = [("w_r", RglMlp), ("w_h", RglMlp), ("x_dim", C.c_int), ("num_layer", C.c_int),
                 ("similarity", C.c_int), ("layerwise_graph", C.c_int), ("skip_connection", C.c_int),
@@ -110,6 +115,7 @@ SIGNATURES = {
     "rgl_graph_backward_f32": (C.c_int, [C.POINTER(RglGraph), C.POINTER(RglMlp), C.POINTER(RglMlp), C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rgl_plan_mlp_rows": (C.c_int, [C.POINTER(RglMlp), C.c_int, C.c_int, C.POINTER(RglRowsPlan)]),
     "rgl_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rgl_transpose_many_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rgl_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

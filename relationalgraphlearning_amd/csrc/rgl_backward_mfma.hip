@@ -1628,6 +1628,12 @@ int mlp_params(const RglMlp& m) {
     return n;
 }
 
+// RGL_HEAD_ROWS_DIRECT (read once per process): 0 = the staged one-tile forms of mlp_rows_kernel instead of head_rows_kernel
+bool rows_direct() {
+    static const bool direct = [] { const char* e = getenv("RGL_HEAD_ROWS_DIRECT"); return !e || atoi(e) != 0; }();
+    return direct;
+}
+
 void plan_rows_job(RowsJob& J, const RglMlp& m, int n_rows, int max_waves) {
     J = RowsJob{};
     J.m = m;
@@ -1663,8 +1669,12 @@ void plan_rows_job(RowsJob& J, const RglMlp& m, int n_rows, int max_waves) {
         J.wave_floats = 16 * ((T0 * 16 + 2) + 66 + (T2 * 16 + 2));
         return;
     }
-    static const bool direct_rows = [] { const char* e = getenv("RGL_HEAD_ROWS_DIRECT"); return !e || atoi(e) != 0; }();
-    if (direct_rows && J.n_tiles <= 1024) {
+    // The direct form below keeps no weights in LDS and returns without a fit check: its tile is largest with every layer at the ABI's
+    // widest, and even that fits one CU (148 224 of 163 840 bytes).  validate_mlp holds every job to these limits before it is planned.
+    static_assert((16 * ((RGL_MAX_MLP_LAYERS + 1) * RGL_MAX_WIDTH + 4) + 32 * (RGL_MAX_WIDTH + 4)) * sizeof(float) <=
+                      (size_t)rgl::kLdsBytesPerCu - 1024,
+                  "head_rows_kernel: a tile of the deepest, widest MLP the ABI admits must fit the LDS of one CU");
+    if (rows_direct() && J.n_tiles <= 1024) {
         // few tiles: a workgroup per tile, the weights straight from L2 (head_rows_kernel): the tile's activations and deltas are all
         // that lives in LDS, every layer in a region of a multiple of 16 columns, rows 16 bytes aligned and four banks apart
         col = 0; widest = 0;
@@ -1856,6 +1866,21 @@ int env_int(const char* name, int dflt) {
 }
 
 }  // namespace
+
+extern "C" int rgl_plan_mlp_rows(const RglMlp* mlp, int n_rows, int max_waves, RglRowsPlan* plan) {
+    if (!mlp || !plan) return RGL_ERR_NULL;
+    if (n_rows < 1 || max_waves < 1 || mlp->n_layers < 1 || mlp->n_layers > RGL_MAX_MLP_LAYERS) return RGL_ERR_BAD_SHAPE;
+    for (int l = 0; l <= mlp->n_layers; ++l)
+        if (mlp->dims[l] < 1 || mlp->dims[l] > RGL_MAX_WIDTH) return RGL_ERR_BAD_SHAPE;
+    RowsJob J;
+    plan_rows_job(J, *mlp, n_rows, max_waves);
+    *plan = RglRowsPlan{};
+    plan->kind = J.kind; plan->coop = J.coop; plan->waves_per_wg = J.waves_per_wg;
+    plan->n_waves = J.n_waves; plan->n_tiles = J.n_tiles; plan->n_wgs = J.n_wgs;
+    plan->direct = rows_direct() ? 1 : 0;
+    plan->lds_bytes = rows_job_lds(J);
+    return RGL_OK;
+}
 
 #ifdef RGL_PHASE_TIMING
 extern "C" int rgl_debug_read_backward_phase_cycles(unsigned long long* out16, int reset) {
@@ -2071,10 +2096,13 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
             balance_narrow(heads, 2, max_waves);
         }
         auto slabs_for = [&](RowsJob& J) { J.slabs = ws.take<float>((size_t)J.n_waves * J.n_params); };
-        if (!detach_graph) { slabs_for(j_wr); slabs_for(j_wh); }
+        // (a detached graph's slabs are set aside all the same: the heads' waves, and with them the order in which their gradients
+        // are summed, must not depend on detach_graph -- the motion head's gradients of a detached step are bit for bit those of
+        // the step that is not)
+        slabs_for(j_wr); slabs_for(j_wh);
         if (has_v) slabs_for(j_v);
         if (has_m) slabs_for(j_m);
-        g_slabs = detach_graph ? nullptr : ws.take<float>((size_t)gp.grid * n_graph);
+        g_slabs = ws.take<float>((size_t)gp.grid * n_graph);
         if (ws.used <= workspace_bytes) break;
     }
     if (ws.used > workspace_bytes) return 1;

@@ -184,6 +184,29 @@ typedef struct RglRowsPlan {
 } RglRowsPlan;
 int rgl_plan_mlp_rows(const RglMlp* mlp, int n_rows, int max_waves, RglRowsPlan* plan);
 
+/* rgl_plan_graph_tiles (ABI 8, additive) -- which instantiation of the tile pipeline's graph kernel (graph_kernel<NT, XT, L, BWD,
+ * COS, LW> of rgl_backward_mfma.hip) a graph of n_scenes scenes of H humans launches, and on how many workgroups.  The answer
+ * comes from the functions the launcher itself calls.  HOST ONLY: no device call, no launch; reads x_dim, num_layer, similarity
+ * and layerwise_graph of `graph` (no pointer of it is read).  backward: 0 the forward build, 1 the backward build (the backward
+ * pipeline launches both).  max_workgroups: the cap the backward applies to its graph launch while the caller's workspace is
+ * short of a slab per workgroup; 2048 = none.
+ *   covered        0: outside what the tile kernels cover (the other fields are 0 then) -- concatenation, layerwise graphs of the
+ *                  cosine family, layerwise softmax / squared graphs beyond x_dim 32 or 32 nodes, x_dim other than 32 | 64,
+ *                  more than 3 layers, more than 64 nodes, or a scene that does not fit the LDS of a CU
+ *   node_tiles     NT: 1 (N <= 16), 2 (N <= 32), 4;   feature_tiles XT: x_dim / 16;   layers L
+ *   family         0 plain (norm 0-3), 1 cosine (norm 4-5), 2 layerwise (an adjacency per layer; a layerwise equal_attention or
+ *                  diagonal graph is family 0: its adjacency is a constant)
+ *   norm           0 softmax (embedded_gaussian, gaussian), 1 squared, 2 equal_attention, 3 diagonal, 4 cosine, 5 cosine_softmax
+ *   resident       workgroups resident at once (256 CUs x 1..6); grid = min(n_scenes, resident, max_workgroups): the kernel is
+ *                  persistent, workgroup b walks scenes b, b + grid, ..
+ *   lds_bytes      dynamic LDS of a workgroup
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (n_scenes, H or max_workgroups < 1). */
+typedef struct RglGraphTilesPlan {
+    int covered, node_tiles, feature_tiles, layers, family, norm, grid, resident;
+    size_t lds_bytes;
+} RglGraphTilesPlan;
+int rgl_plan_graph_tiles(const RglGraph* graph, int n_scenes, int H, int backward, int max_workgroups, RglGraphTilesPlan* plan);
+
 /* rgl_transpose_f32 -- dst[c][r] = src[r][c]; turns a torch Linear weight (out,in) into the
  * k-major layout RglMlp wants.  Host-side convenience of this ABI (no reference counterpart). */
 int rgl_transpose_f32(const float* src, float* dst, int rows, int cols, rgl_stream_t stream);

@@ -49,6 +49,11 @@ class RglRowsPlan(C.Structure):
                 ("n_wgs", C.c_int), ("direct", C.c_int), ("reserved", C.c_int), ("lds_bytes", C.c_size_t)]
 
 
+class RglGraphTilesPlan(C.Structure):
+    _fields_ = [("covered", C.c_int), ("node_tiles", C.c_int), ("feature_tiles", C.c_int), ("layers", C.c_int), ("family", C.c_int),
+                ("norm", C.c_int), ("grid", C.c_int), ("resident", C.c_int), ("lds_bytes", C.c_size_t)]
+
+
 class RglGraph(C.Structure):
     _fields_ = [("w_r", RglMlp), ("w_h", RglMlp), ("x_dim", C.c_int), ("num_layer", C.c_int),
                 ("similarity", C.c_int), ("layerwise_graph", C.c_int), ("skip_connection", C.c_int),
@@ -116,6 +121,7 @@ SIGNATURES = {
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "rgl_plan_mlp_rows": (C.c_int, [C.POINTER(RglMlp), C.c_int, C.c_int, C.POINTER(RglRowsPlan)]),
+    "rgl_plan_graph_tiles": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglGraphTilesPlan)]),
     "rgl_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rgl_transpose_many_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rgl_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

@@ -1806,29 +1806,35 @@ int launch_graph_kernel(const GraphArgs& ga, size_t lds, int grid, hipStream_t s
     RGL_LAUNCH_CHECK();
     return RGL_OK;
 }
+// the instantiation a graph launch takes -- decided HERE, read by plan_graph, launch_graph and rgl_plan_graph_tiles:
+// node tiles by N, feature tiles by x_dim (32 | 64), the family by the normalisation and the layerwise flag of graph_args
+struct GraphForm { int nt, xt, family; };       // family: 0 plain (norm 0-3), 1 cosine (COS: norm 4-5), 2 layerwise (LW)
+GraphForm graph_form(int N, int X, int norm, bool lw) {
+    return GraphForm{N <= 16 ? 1 : (N <= 32 ? 2 : 4), X == 32 ? 2 : 4, lw ? 2 : (norm >= 4 ? 1 : 0)};
+}
 template <int NT, int XT, int L>
-int launch_graph_nxl(const GraphArgs& ga, bool bwd, size_t lds, int grid, hipStream_t st) {
-    if (ga.lw) {        // layerwise graphs: the softmax / squared normalisations, up to 32 nodes of 32 features (tiles_cover)
+int launch_graph_nxl(const GraphArgs& ga, int family, bool bwd, size_t lds, int grid, hipStream_t st) {
+    if (family == 2) {  // layerwise graphs: the softmax / squared normalisations, up to 32 nodes of 32 features (tiles_cover)
         if constexpr (XT == 2 && NT <= 2)
             return bwd ? launch_graph_kernel<NT, XT, L, true, false, true>(ga, lds, grid, st)
                        : launch_graph_kernel<NT, XT, L, false, false, true>(ga, lds, grid, st);
         else
             return 1;
     }
-    if (ga.norm >= 4)
+    if (family == 1)
         return bwd ? launch_graph_kernel<NT, XT, L, true, true>(ga, lds, grid, st) : launch_graph_kernel<NT, XT, L, false, true>(ga, lds, grid, st);
     return bwd ? launch_graph_kernel<NT, XT, L, true, false>(ga, lds, grid, st) : launch_graph_kernel<NT, XT, L, false, false>(ga, lds, grid, st);
 }
 template <int NT, int XT>
-int launch_graph_nx(const GraphArgs& ga, int L, bool bwd, size_t lds, int grid, hipStream_t st) {
+int launch_graph_nx(const GraphArgs& ga, int family, int L, bool bwd, size_t lds, int grid, hipStream_t st) {
     switch (L) {
-        case 1: return launch_graph_nxl<NT, XT, 1>(ga, bwd, lds, grid, st);
-        case 2: return launch_graph_nxl<NT, XT, 2>(ga, bwd, lds, grid, st);
-        default: return launch_graph_nxl<NT, XT, 3>(ga, bwd, lds, grid, st);
+        case 1: return launch_graph_nxl<NT, XT, 1>(ga, family, bwd, lds, grid, st);
+        case 2: return launch_graph_nxl<NT, XT, 2>(ga, family, bwd, lds, grid, st);
+        default: return launch_graph_nxl<NT, XT, 3>(ga, family, bwd, lds, grid, st);
     }
 }
 
-struct GraphPlan { int grid; size_t lds; };
+struct GraphPlan { int grid; size_t lds; int resident; };       // resident: the grid before min(S, .)
 template <int NT, int XT>
 GraphPlan plan_graph_nx(int S, int N, int L, bool bwd, bool lw) {
     GraphPlan p{};
@@ -1840,24 +1846,37 @@ GraphPlan plan_graph_nx(int S, int N, int L, bool bwd, bool lw) {
     const int by_waves = lw ? 2 : ((NT == 2 && XT == 2) ? 16 : (NT == 1 ? 12 : 8)) / (2 * NT);
     per_cu = per_cu > by_waves ? by_waves : per_cu;
     per_cu = per_cu < 1 ? 1 : per_cu;
-    const int resident = 256 * per_cu;
-    p.grid = S < resident ? S : resident;
+    p.resident = 256 * per_cu;
+    p.grid = S < p.resident ? S : p.resident;
     return p;
 }
 // x_dim 32 or 64
 GraphPlan plan_graph(int S, int N, int X, int L, bool bwd, bool lw = false) {
-    if (X == 32) return N <= 16 ? plan_graph_nx<1, 2>(S, N, L, bwd, lw) : (N <= 32 ? plan_graph_nx<2, 2>(S, N, L, bwd, lw) : plan_graph_nx<4, 2>(S, N, L, bwd, lw));
-    return N <= 16 ? plan_graph_nx<1, 4>(S, N, L, bwd, lw) : (N <= 32 ? plan_graph_nx<2, 4>(S, N, L, bwd, lw) : plan_graph_nx<4, 4>(S, N, L, bwd, lw));
+    const GraphForm f = graph_form(N, X, 0, lw);
+    switch (f.nt * 10 + f.xt) {
+        case 12: return plan_graph_nx<1, 2>(S, N, L, bwd, lw);
+        case 22: return plan_graph_nx<2, 2>(S, N, L, bwd, lw);
+        case 42: return plan_graph_nx<4, 2>(S, N, L, bwd, lw);
+        case 14: return plan_graph_nx<1, 4>(S, N, L, bwd, lw);
+        case 24: return plan_graph_nx<2, 4>(S, N, L, bwd, lw);
+        default: return plan_graph_nx<4, 4>(S, N, L, bwd, lw);
+    }
+}
+// the backward's launch while the caller's workspace is short: a slab per workgroup, at most `max_workgroups` of them
+GraphPlan cap_graph_plan(GraphPlan p, int max_workgroups) {
+    p.grid = p.grid < max_workgroups ? p.grid : max_workgroups;
+    return p;
 }
 int launch_graph(const GraphArgs& ga, int X, int L, bool bwd, const GraphPlan& p, hipStream_t st) {
-    if (X == 32) {
-        if (ga.N <= 16) return launch_graph_nx<1, 2>(ga, L, bwd, p.lds, p.grid, st);
-        if (ga.N <= 32) return launch_graph_nx<2, 2>(ga, L, bwd, p.lds, p.grid, st);
-        return launch_graph_nx<4, 2>(ga, L, bwd, p.lds, p.grid, st);
+    const GraphForm f = graph_form(ga.N, X, ga.norm, ga.lw != 0);
+    switch (f.nt * 10 + f.xt) {
+        case 12: return launch_graph_nx<1, 2>(ga, f.family, L, bwd, p.lds, p.grid, st);
+        case 22: return launch_graph_nx<2, 2>(ga, f.family, L, bwd, p.lds, p.grid, st);
+        case 42: return launch_graph_nx<4, 2>(ga, f.family, L, bwd, p.lds, p.grid, st);
+        case 14: return launch_graph_nx<1, 4>(ga, f.family, L, bwd, p.lds, p.grid, st);
+        case 24: return launch_graph_nx<2, 4>(ga, f.family, L, bwd, p.lds, p.grid, st);
+        default: return launch_graph_nx<4, 4>(ga, f.family, L, bwd, p.lds, p.grid, st);
     }
-    if (ga.N <= 16) return launch_graph_nx<1, 4>(ga, L, bwd, p.lds, p.grid, st);
-    if (ga.N <= 32) return launch_graph_nx<2, 4>(ga, L, bwd, p.lds, p.grid, st);
-    return launch_graph_nx<4, 4>(ga, L, bwd, p.lds, p.grid, st);
 }
 
 int env_int(const char* name, int dflt) {
@@ -1929,13 +1948,16 @@ bool tiles_cover(const RglGraph& g, int H) {
     return tiles_norm(g) >= 0;
 }
 
+// the layerwise build (an adjacency per layer); constant adjacencies: layerwise or not is the same graph
+bool tiles_layerwise(const RglGraph& g) { return g.layerwise_graph != 0 && tiles_norm(g) <= 1; }
+
 void graph_args(GraphArgs& ga, const RglGraph& g, int S, int N, int spc) {
     ga = GraphArgs{};
     ga.w_a = g.similarity == RGL_SIM_EMBEDDED_GAUSSIAN ? g.w_a : nullptr;
     for (int l = 0; l < g.num_layer; ++l) ga.Ws[l] = g.Ws[l];
     ga.S = S; ga.N = N; ga.skip = g.skip_connection ? 1 : 0; ga.spc = spc;
     ga.norm = tiles_norm(g);
-    ga.lw = (g.layerwise_graph && ga.norm <= 1) ? 1 : 0;        // constant adjacencies: layerwise or not is the same graph
+    ga.lw = tiles_layerwise(g) ? 1 : 0;
     ga.xr_stride = g.x_dim; ga.xh_stride = (N - 1) * g.x_dim;
 }
 
@@ -1951,6 +1973,23 @@ struct Taker {                 // carves 256-byte aligned pieces out of a worksp
 };
 
 }  // namespace
+
+extern "C" int rgl_plan_graph_tiles(const RglGraph* graph, int n_scenes, int H, int backward, int max_workgroups,
+                                    RglGraphTilesPlan* plan) {
+    if (!graph || !plan) return RGL_ERR_NULL;
+    if (n_scenes < 1 || H < 1 || max_workgroups < 1) return RGL_ERR_BAD_SHAPE;
+    *plan = RglGraphTilesPlan{};
+    const RglGraph& g = *graph;
+    if (!tiles_cover(g, H)) return RGL_OK;
+    const bool lw = tiles_layerwise(g);
+    const GraphPlan p = cap_graph_plan(plan_graph(n_scenes, H + 1, g.x_dim, g.num_layer, backward != 0, lw), max_workgroups);
+    if (p.grid < 1) return RGL_OK;              // a scene does not fit the LDS of a CU: the pipeline answers "not mine"
+    const GraphForm f = graph_form(H + 1, g.x_dim, tiles_norm(g), lw);
+    plan->covered = 1; plan->node_tiles = f.nt; plan->feature_tiles = f.xt; plan->layers = g.num_layer;
+    plan->family = f.family; plan->norm = tiles_norm(g); plan->grid = p.grid; plan->resident = p.resident;
+    plan->lds_bytes = p.lds;
+    return RGL_OK;
+}
 
 namespace rgl {
 
@@ -1979,7 +2018,7 @@ int launch_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* 
         return 1;
     const RglGraph& g = *graph;
     const int N = H + 1, L = g.num_layer, X = g.x_dim, crowds = S / spc;
-    const GraphPlan gp = plan_graph(S, N, X, L, false, g.layerwise_graph != 0 && tiles_norm(g) <= 1);
+    const GraphPlan gp = plan_graph(S, N, X, L, false, tiles_layerwise(g));
     if (gp.grid < 1) return 1;
     Taker ws{(char*)workspace};
     float* Xr = ws.take<float>((size_t)S * X);
@@ -2059,7 +2098,7 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
     if (!tiles_cover(g, H)) return 1;
     const int N = H + 1, L = g.num_layer, X = g.x_dim;
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
-    const bool embedded = g.similarity == RGL_SIM_EMBEDDED_GAUSSIAN, lw = g.layerwise_graph != 0 && tiles_norm(g) <= 1;
+    const bool embedded = g.similarity == RGL_SIM_EMBEDDED_GAUSSIAN, lw = tiles_layerwise(g);
     const GraphPlan gpf = plan_graph(S, N, X, L, false, lw), gp_full = plan_graph(S, N, X, L, true, lw);
     if (gp_full.grid < 1 || gpf.grid < 1) return 1;
 
@@ -2084,7 +2123,7 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
     GraphPlan gp = gp_full;
     for (int max_waves = 2048; max_waves >= 1; max_waves >>= 1) {
         ws.used = used_feat;
-        gp.grid = gp_full.grid < max_waves ? gp_full.grid : max_waves;
+        gp = cap_graph_plan(gp_full, max_waves);
         plan_rows_job(j_wr, g.w_r, S, max_waves);
         plan_rows_job(j_wh, g.w_h, S * H, max_waves);
         if (has_v) plan_rows_job(j_v, *vh, S, max_waves);

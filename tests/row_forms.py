@@ -106,12 +106,20 @@ def small(run):
 # the library's plan
 # ---------------------------------------------------------------------------------------------------------------------------
 def job_mlps(run):
-    """{job: (dims, last_relu, rows)} of the run's pipeline."""
+    """{job: (dims, last_relu, rows)} of the run's pipeline (module "rgl" -- the graph model alone, tests/graph_forms.py -- has no head)."""
     jobs = collections.OrderedDict()
     jobs["w_r"] = ([9] + list(run.wr), 1, run.S)
     jobs["w_h"] = ([5] + list(run.wh), 1, run.S * run.H)
-    jobs[run.module] = ([run.X] + list(run.head), 0, run.S if run.module == "value" else run.S * run.H)
+    if run.module != "rgl":
+        jobs[run.module] = ([run.X] + list(run.head), 0, run.S if run.module == "value" else run.S * run.H)
     return jobs
+
+
+def graph_flags(run):
+    """(layers, similarity, layerwise, skip, scenes per crowd) of a run: the shipped graph unless the run's table has these columns
+    (tests/graph_forms.py)."""
+    return (getattr(run, "L", 2), getattr(run, "sim", "embedded_gaussian"), bool(getattr(run, "lw", False)),
+            bool(getattr(run, "skip", True)), getattr(run, "spc", 1))
 
 
 def plan(dims, rows, max_waves=2048, last_relu=0):
@@ -157,19 +165,25 @@ def n_params(run):
     """(w_r, w_h, graph, head) parameter counts: the slab widths of the backward."""
     count = lambda dims: sum(a * b + b for a, b in zip(dims[:-1], dims[1:]))
     mlps = job_mlps(run)
-    return count(mlps["w_r"][0]), count(mlps["w_h"][0]), 3 * run.X * run.X, count(mlps[run.module][0])
+    L, sim = graph_flags(run)[:2]
+    return (count(mlps["w_r"][0]), count(mlps["w_h"][0]), ((1 if sim == "embedded_gaussian" else 0) + L) * run.X * run.X,
+            count(mlps[run.module][0]) if run.module in mlps else 0)
 
 
-def backward_workspace(run, max_waves):
+def backward_workspace(run, max_waves, graph_workgroups=None, row_slabs=True):
     """(bytes the tile backward takes at `max_waves`, bytes the caller provides).  The accounting of backward_tiles, not the planner:
-    three [S][N][X] feature arrays, a slab per wave of every row job (the waves from rgl_plan_mlp_rows) and per workgroup of the
-    graph kernel (a workgroup per scene at these sizes), every piece a multiple of 256 bytes."""
+    three [S][N][X] feature arrays, a slab per wave of every row job (the waves from rgl_plan_mlp_rows; row_slabs=False leaves them
+    out: a lower bound, whatever the launcher's rebalancing of narrow jobs does to their waves) and per workgroup of the graph kernel
+    (graph_workgroups; None: a workgroup per scene, as at the row tables' sizes), every piece a multiple of 256 bytes."""
     wr, wh, graph, head = n_params(run)
     p = plans(run, max_waves)
     piece = lambda floats: (floats * 4 + 255) // 256 * 256
     feat = run.S * (run.H + 1) * run.X
-    used = 3 * piece(feat) + piece(p["w_r"]["n_waves"] * wr) + piece(p["w_h"]["n_waves"] * wh) + \
-        piece(p[run.module]["n_waves"] * head) + piece(min(run.S, max_waves) * graph)
+    used = 3 * piece(feat) + piece((min(run.S, max_waves) if graph_workgroups is None else graph_workgroups) * graph)
+    if row_slabs:
+        used += piece(p["w_r"]["n_waves"] * wr) + piece(p["w_h"]["n_waves"] * wh)
+        if run.module in p:
+            used += piece(p[run.module]["n_waves"] * head)
     return used, run.S * (wr + wh + graph + head) * 4
 
 
@@ -179,8 +193,10 @@ def backward_workspace(run, max_waves):
 def build(run):
     """(module, graph model, head) on the CPU: random initialisation under the run's seed, w_a / Ws scaled to the size trained
     weights have (the reference draws them from randn), the head by 0.5."""
+    L, sim, lw, skip, _ = graph_flags(run)
     cfg = policy_config("model_predictive_rl", gcn__X_dim=run.X, gcn__final_state_dim=run.X, gcn__wr_dims=list(run.wr),
-                        gcn__wh_dims=list(run.wh),
+                        gcn__wh_dims=list(run.wh), gcn__num_layer=L, gcn__similarity_function=sim, gcn__layerwise_graph=lw,
+                        gcn__skip_connection=skip,
                         model_predictive_rl__value_network_dims=list(run.head) if run.module == "value" else SHIPPED_V,
                         model_predictive_rl__motion_predictor_dims=list(run.head) if run.module == "motion" else SHIPPED_M)
     torch.manual_seed(1000 + run.seed)
@@ -188,14 +204,16 @@ def build(run):
     if run.module == "value":
         mod = rga.ValueEstimator(cfg, g)
         head = mod.value_network
-    else:
+    elif run.module == "motion":
         mod = rga.StatePredictor(cfg, g, 0.25)
         head = mod.human_motion_predictor
+    else:                                   # "rgl": the graph model alone, no head
+        mod, head = g, None
     with torch.no_grad():
         for n_, p_ in g.named_parameters():
             if n_ == "w_a" or n_.startswith("Ws"):
                 p_.mul_(1.0 / run.X ** 0.5)
-        for p_ in head.parameters():
+        for p_ in (head.parameters() if head is not None else ()):
             p_.mul_(0.5)
     return mod, g, head
 
@@ -210,13 +228,16 @@ def scenes(run):
     distinct = DISTINCT if run.H <= 5 else DISTINCT_CROWDED
     robot, humans = seeded_scenes(7000 + run.seed + run.H, min(run.S, distinct), run.H)
     reps = -(-run.S // distinct)
-    return robot.repeat(reps, 1)[:run.S].contiguous(), humans.repeat(reps, 1, 1)[:run.S].contiguous()
+    crowds = run.S // graph_flags(run)[4]   # sibling scenes share a crowd (forward only): humans [S / spc][H][5]
+    return robot.repeat(reps, 1)[:run.S].contiguous(), humans.repeat(reps, 1, 1)[:crowds].contiguous()
 
 
 def upstream(run):
     """The gradient fed into the module's output, as test_gradients_value_estimator_and_state_predictor feeds it."""
     if run.module == "value":
         return torch.linspace(-1.0, 1.5, run.S).reshape(run.S, 1)
+    if run.module == "rgl":                 # d_H on all rows, as test_gradients_rgl_output_and_path_g feeds it
+        return torch.randn(run.S, run.H + 1, run.X, generator=torch.Generator().manual_seed(5))
     return torch.randn(run.S, run.H, run.head[-1], generator=torch.Generator().manual_seed(3))
 
 
@@ -242,12 +263,15 @@ def oracle(run, dtype, detach=False):
     mod, g, head = build(run)
     robot, humans = scenes(run)
     leafs = lambda sd: {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in sd.items()}
-    gsd, hsd = leafs(g.state_dict()), leafs(head.state_dict())
-    cfg = orc.OracleConfig(x_dim=run.X)
-    r, h = robot.unsqueeze(1).to(dtype), humans.to(dtype)
+    gsd, hsd = leafs(g.state_dict()), leafs(head.state_dict() if head is not None else {})
+    L, sim, lw, skip, spc = graph_flags(run)
+    cfg = orc.OracleConfig(x_dim=run.X, num_layer=L, similarity=sim, layerwise_graph=lw, skip_connection=skip)
+    r, h = robot.unsqueeze(1).to(dtype), humans.repeat_interleave(spc, 0).to(dtype)
     with relu_inputs() as pre:
         if run.module == "value":
             out = orc.value_estimator_forward(r, h, gsd, hsd, cfg)
+        elif run.module == "rgl":
+            out, _ = orc.rgl_forward(r, h, gsd, cfg)
         else:
             emb, _ = orc.rgl_forward(r, h, gsd, cfg)
             if detach:
@@ -272,14 +296,17 @@ def grad_error(got, want):
     return float(np.abs(np.asarray(got, np.float64) - want).max()) / max(1e-3, float(np.abs(want).max()))
 
 
+TABLES = {"rows": RUN}              # tests/graph_forms.py adds its own
+
+
 @functools.lru_cache(maxsize=None)
-def reference(run_id, detach=False):
+def reference(run_id, detach=False, table="rows"):
     """The float64 result of a run, computed once, with the yardstick for the regression-level bounds: the worst deviation of the
     SAME oracle evaluated in float32 on the CPU (forward; gradients, worst over the parameters), scaled like the assertions.
     masks_agree: the two evaluations took the same side of every ReLU.  margin: the smallest over the ReLU layers of (the layer's
     smallest float64 |pre-activation|) / (the float32 evaluation's largest error in that layer); at 8 and above -- the factor the
     regression-level bounds keep -- no float32 summation order puts a row on the other side of a ReLU."""
-    run = RUN[run_id]
+    run = TABLES[table][run_id]
     out, grads, pre = oracle(run, torch.float64, detach)
     out32, grads32, pre32 = oracle(run, torch.float32, detach)
     assert sorted(grads) == sorted(grads32) and len(pre) == len(pre32)

@@ -63,7 +63,7 @@ def measure(run, dev, detach=False):
     def once():
         for p_ in mod.parameters():
             p_.grad = None
-        out = mod((r, h)) if run.module == "value" else mod((r, h), None, detach=detach)[1]
+        out = mod((r, h)) if run.module != "motion" else mod((r, h), None, detach=detach)[1]     # "rgl": the graph model alone
         (out * up).sum().backward()
         res = {"out": out.detach().cpu().numpy()}
         absent = True
@@ -72,7 +72,7 @@ def measure(run, dev, detach=False):
                 absent = absent and (v.grad is None or float(v.grad.abs().max()) == 0.0)
             else:
                 res["g/graph." + k] = v.grad.detach().cpu().numpy()
-        for k, v in head.named_parameters():
+        for k, v in (head.named_parameters() if head is not None else ()):
             res["g/%s.%s" % (run.module, k)] = v.grad.detach().cpu().numpy()
         res["graph_absent"] = np.array(absent and detach)
         return res
@@ -165,9 +165,10 @@ def child(name, tmp_path_factory):
 # ---------------------------------------------------------------------------------------------------------------------------
 # a. against float64
 # ---------------------------------------------------------------------------------------------------------------------------
-def against_float64(got, prefix, run, detach, tag):
-    """Section a for the arrays under `prefix`; returns (forward deviation, worst gradient deviation)."""
-    ref = rf.reference(run.id, detach)
+def against_float64(got, prefix, run, detach, tag, table="rows", what="mlp row forms"):
+    """Section a for the arrays under `prefix`; returns (forward deviation, worst gradient deviation).  `table`, `what`: the case
+    table the run is of and the parity report's heading (tests/test_graph_forms.py runs its own table through here)."""
+    ref = rf.reference(run.id, detach, table)
     assert ref["masks_agree"] and ref["n_masks"] > 0, (run.id, "the float32 and float64 oracles differ in a ReLU mask: a wrong seed")
     assert ref["margin"] >= 8, (run.id, "a pre-activation within 8 float32 errors of zero: a wrong seed", ref["margin"])
     names = sorted(k[len(prefix) + 3:] for k in got if k.startswith(prefix + "/g/"))
@@ -187,9 +188,9 @@ def against_float64(got, prefix, run, detach, tag):
         assert got["%s/g/%s" % (prefix, k)].shape == ref["grads"][k].shape, (tag, k)
         assert errs[k] <= GRAD_TOL, (tag, k, errs[k])
         assert errs[k] <= reg_g, ("regression-level bound", tag, k, errs[k], reg_g)
-    report("mlp row forms, %s: forward %.2e of the float64 oracle (float32 oracle on the CPU %.2e; asserted %.0e and %.2e), gradients %.2e "
+    report("%s, %s: forward %.2e of the float64 oracle (float32 oracle on the CPU %.2e; asserted %.0e and %.2e), gradients %.2e "
            "at %s (float32 oracle %.2e; asserted %.0e and %.2e)"
-           % (tag, e_f, ref["yard_fwd"], TOL, reg_f, errs[worst], worst, ref["yard_grad"], GRAD_TOL, reg_g))
+           % (what, tag, e_f, ref["yard_fwd"], TOL, reg_f, errs[worst], worst, ref["yard_grad"], GRAD_TOL, reg_g))
     return e_f, errs[worst]
 
 

@@ -30,10 +30,12 @@ struct ChildrenArgs {
 
 __device__ __forceinline__ double seg_point_dist_origin(double px, double py, double ex, double ey, bool f32_degenerate,
                                                         float fpx, float fpy) {
-    // distance from the origin to the segment (px,py)-(ex,ey); utils.py:4-26 with (x3,y3) = 0
+    // distance from the origin to the segment (px,py)-(ex,ey); utils.py:4-26 with (x3,y3) = 0.  numpy scalar arithmetic: no product
+    // is fused into the sum that takes it
+#pragma clang fp contract(off)
     const double sx = ex - px, sy = ey - py;
     if (sx == 0.0 && sy == 0.0) {
-        if (f32_degenerate) return (double)sqrtf(__fadd_rn(__fmul_rn(fpx, fpx), __fmul_rn(fpy, fpy)));
+        if (f32_degenerate) return (double)sqrtf(fpx * fpx + fpy * fpy);
         return sqrt(px * px + py * py);
     }
     double u = ((0.0 - px) * sx + (0.0 - py) * sy) / (sx * sx + sy * sy);
@@ -62,16 +64,16 @@ __device__ __forceinline__ double pair_reward(const ChildrenArgs& ca, int p, int
     if (ca.kinematics == RGL_HOLONOMIC) {
         avx = a0;
         avy = a1;
-        nx = R(0) + a0 * dt;
-        ny = R(1) + a1 * dt;
+        nx = f64_mad(a0, dt, R(0));
+        ny = f64_mad(a1, dt, R(1));
     } else {
         // estimate_reward uses theta (slot 8) for the relative velocity and the goal test
         const double th = a1 + R(8);
         avx = a0 * cos(th);
         avy = a0 * sin(th);
         const double th2 = R(8) + a1;
-        nx = R(0) + cos(th2) * a0 * dt;
-        ny = R(1) + sin(th2) * a0 * dt;
+        nx = f64_mad(cos(th2) * a0, dt, R(0));
+        ny = f64_mad(sin(th2) * a0, dt, R(1));
     }
     bool collision = false;
     double dmin = INFINITY;
@@ -104,7 +106,7 @@ __device__ __forceinline__ double pair_reward(const ChildrenArgs& ca, int p, int
             py = (double)fpy;
         }
         const double vx = HU(2) - avx, vy = HU(3) - avy;
-        const double ex = px + vx * dt, ey = py + vy * dt;
+        const double ex = f64_mad(vx, dt, px), ey = f64_mad(vy, dt, py);
         // Exact shortcut: the outcome depends on this human only if its clearance d is < 0.2 (collision, or the minimum
         // when that is below the discomfort distance).  dist(origin, segment) >= |p| - |e - p|, so with
         // T = radii + 0.25 the test |p|^2 >= 2 (|e - p|^2 + T^2)  (=> |p| >= |e - p| + T) proves d >= 0.25 without the
@@ -128,7 +130,7 @@ __device__ __forceinline__ double pair_reward(const ChildrenArgs& ca, int p, int
     const double gx = nx - R(5), gy = ny - R(6);
     // norm < radius (model_predictive_rl.py:336-345): away from the boundary the squares decide -- a 1e-12 relative margin is four
     // orders above every rounding of x, r^2 and the root -- and the float64 square root runs only inside it
-    const double gd2 = gx * gx + gy * gy, gr2 = R(4) * R(4);
+    const double gd2 = f64_dot2(gx, gx, gy, gy), gr2 = R(4) * R(4);
     const bool reaching = (R(4) > 0.0 && gd2 <= gr2 * (1.0 - 1e-12)) ? true
                           : ((R(4) > 0.0 && gd2 >= gr2 * (1.0 + 1e-12)) ? false : sqrt(gd2) < R(4));
     if (collision) return -0.25;
@@ -154,7 +156,7 @@ __device__ __forceinline__ double stop_reward_f32(const ChildrenArgs& ca, int p,
     auto visit = [&](int h) {
         const float* hu = hs + h * 5;
         const float px = __fsub_rn(hu[0], r[0]), py = __fsub_rn(hu[1], r[1]);
-        const float ex = __fadd_rn(px, __fmul_rn(hu[2], fdt)), ey = __fadd_rn(py, __fmul_rn(hu[3], fdt));
+        const float ex = f32_add(px, f32_mul(hu[2], fdt)), ey = f32_add(py, f32_mul(hu[3], fdt));
         const float sx = __fsub_rn(ex, px), sy = __fsub_rn(ey, py);
         {
             // the same exact shortcut as pair_reward: provably >= 0.25 of clearance, the human cannot influence the reward
@@ -163,12 +165,12 @@ __device__ __forceinline__ double stop_reward_f32(const ChildrenArgs& ca, int p,
         }
         float dist;
         if (sx == 0.f && sy == 0.f) {
-            dist = sqrtf(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)));
+            dist = sqrtf(f32_add(f32_mul(px, px), f32_mul(py, py)));
         } else {
-            float u = __fdiv_rn(__fadd_rn(__fmul_rn(-px, sx), __fmul_rn(-py, sy)), __fadd_rn(__fmul_rn(sx, sx), __fmul_rn(sy, sy)));
+            float u = f32_div(f32_add(f32_mul(-px, sx), f32_mul(-py, sy)), f32_add(f32_mul(sx, sx), f32_mul(sy, sy)));
             u = u > 1.f ? 1.f : (u < 0.f ? 0.f : u);
-            const float cx = __fadd_rn(px, __fmul_rn(u, sx)), cy = __fadd_rn(py, __fmul_rn(u, sy));
-            dist = sqrtf(__fadd_rn(__fmul_rn(cx, cx), __fmul_rn(cy, cy)));
+            const float cx = f32_add(px, f32_mul(u, sx)), cy = f32_add(py, f32_mul(u, sy));
+            dist = sqrtf(f32_add(f32_mul(cx, cx), f32_mul(cy, cy)));
         }
         const float d = __fsub_rn(__fsub_rn(dist, hu[4]), r[4]);
         if (d < 0.f) collision = true;
@@ -182,7 +184,7 @@ __device__ __forceinline__ double stop_reward_f32(const ChildrenArgs& ca, int p,
     }
     for (int h = 64; h < ca.H; ++h) visit(h);
     const float gx = __fsub_rn(r[0], r[5]), gy = __fsub_rn(r[1], r[6]);
-    const bool reaching = sqrtf(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy))) < r[4];
+    const bool reaching = sqrtf(f32_add(f32_mul(gx, gx), f32_mul(gy, gy))) < r[4];
     if (collision) return -0.25;
     if (reaching) return 1.0;
     if (dmin < 0.2f) return (double)__fmul_rn(__fmul_rn(__fsub_rn(dmin, 0.2f), 0.5f), fdt);
@@ -201,18 +203,18 @@ __device__ __forceinline__ double stop_reward_wave(const ChildrenArgs& ca, int p
     if (lane < ca.H) {
         const float* hu = hs + lane * 5;
         const float px = __fsub_rn(hu[0], r[0]), py = __fsub_rn(hu[1], r[1]);
-        const float ex = __fadd_rn(px, __fmul_rn(hu[2], fdt)), ey = __fadd_rn(py, __fmul_rn(hu[3], fdt));
+        const float ex = f32_add(px, f32_mul(hu[2], fdt)), ey = f32_add(py, f32_mul(hu[3], fdt));
         const float sx = __fsub_rn(ex, px), sy = __fsub_rn(ey, py);
         const float Tf = hu[4] + r[4] + 0.25f;
         if (!(px * px + py * py >= 2.002f * (sx * sx + sy * sy + Tf * Tf))) {
             float dist;
             if (sx == 0.f && sy == 0.f) {
-                dist = sqrtf(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)));
+                dist = sqrtf(f32_add(f32_mul(px, px), f32_mul(py, py)));
             } else {
-                float u = __fdiv_rn(__fadd_rn(__fmul_rn(-px, sx), __fmul_rn(-py, sy)), __fadd_rn(__fmul_rn(sx, sx), __fmul_rn(sy, sy)));
+                float u = f32_div(f32_add(f32_mul(-px, sx), f32_mul(-py, sy)), f32_add(f32_mul(sx, sx), f32_mul(sy, sy)));
                 u = u > 1.f ? 1.f : (u < 0.f ? 0.f : u);
-                const float cx = __fadd_rn(px, __fmul_rn(u, sx)), cy = __fadd_rn(py, __fmul_rn(u, sy));
-                dist = sqrtf(__fadd_rn(__fmul_rn(cx, cx), __fmul_rn(cy, cy)));
+                const float cx = f32_add(px, f32_mul(u, sx)), cy = f32_add(py, f32_mul(u, sy));
+                dist = sqrtf(f32_add(f32_mul(cx, cx), f32_mul(cy, cy)));
             }
             d = __fsub_rn(__fsub_rn(dist, hu[4]), r[4]);
         }
@@ -221,7 +223,7 @@ __device__ __forceinline__ double stop_reward_wave(const ChildrenArgs& ca, int p
     // wave minimum on the VALU (DPP row maxima + permlane swaps of the negated value: exact) instead of six ds_bpermute trips
     const float dmin = -kgroups_max(row16_max(-d));
     const float gx = __fsub_rn(r[0], r[5]), gy = __fsub_rn(r[1], r[6]);
-    const bool reaching = sqrtf(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy))) < r[4];
+    const bool reaching = sqrtf(f32_add(f32_mul(gx, gx), f32_mul(gy, gy))) < r[4];
     if (collision) return -0.25;
     if (reaching) return 1.0;
     if (dmin < 0.2f) return (double)__fmul_rn(__fmul_rn(__fsub_rn(dmin, 0.2f), 0.5f), fdt);

@@ -152,3 +152,38 @@ inline int mlp_max_hidden(const RglMlp& m) {
 }
 
 }  // namespace rgl
+
+namespace {
+
+// One operation, rounded on its own.  The search's bookkeeping, the rewards and path G's features follow the reference's chains of
+// scalar / tensor operations -- a product and the sum that takes it are two roundings -- and tests/search_bookkeeping.py and
+// tests/path_g_steps.py replay them bit for bit.  The toolchain's __fmul_rn / __fadd_rn are the plain operators, which the default
+// -ffp-contract fuses into one fma (one rounding: a last-bit difference in a value, and a clearance of exactly 0 -- no collision --
+// turned negative); an operation compiled under `contract(off)` takes no part in a fusion.
+__device__ __forceinline__ float f32_mul(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ float f32_add(float x, float y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+__device__ __forceinline__ float f32_sub(float x, float y) {
+#pragma clang fp contract(off)
+    return x - y;
+}
+__device__ __forceinline__ float f32_div(float x, float y) {
+#pragma clang fp contract(off)
+    return x / y;
+}
+// x * y + z and a * b + c * d in float64, every product and the sum rounded
+__device__ __forceinline__ double f64_mad(double x, double y, double z) {
+#pragma clang fp contract(off)
+    return x * y + z;
+}
+__device__ __forceinline__ double f64_dot2(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+    return a * b + c * d;
+}
+
+}  // namespace

@@ -42,23 +42,6 @@ struct TailArgs {
     int* root_kept;           // [B][W] or null
 };
 
-// One fp32 operation, rounded on its own.  The bookkeeping's arithmetic is the reference's chain of tensor operations -- a product
-// and the sum that takes it are two roundings -- and tests/search_bookkeeping.py replays it bit for bit.  The toolchain's
-// __fmul_rn / __fadd_rn are the plain operators, which the default -ffp-contract fuses into one fma (one rounding: a last-bit
-// difference in value1 and in every backed-up value); an operation compiled under `contract(off)` takes no part in a fusion.
-__device__ __forceinline__ float f32_mul(float x, float y) {
-#pragma clang fp contract(off)
-    return x * y;
-}
-__device__ __forceinline__ float f32_add(float x, float y) {
-#pragma clang fp contract(off)
-    return x + y;
-}
-__device__ __forceinline__ float f32_div(float x, float y) {
-#pragma clang fp contract(off)
-    return x / y;
-}
-
 __device__ __forceinline__ int tail_fallback(const int* kl, int k) { return k > 0 ? kl[k - 1] : 0; }
 
 // One WAVE, parent p of level t.level: one-step values, top-w clipping (argpartition semantics; sparse: one action per group in

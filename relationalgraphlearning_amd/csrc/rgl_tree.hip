@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void mprl_select_kernel(const TailArgs t) {
 __global__ void one_step_value_kernel(const float* __restrict__ r, const float* __restrict__ v, float g, long long n,
                                       float* __restrict__ o) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = f32_add(r[i], f32_mul(g, v[i]));      // two roundings (rgl_tail.h)
+    if (i < n) o[i] = f32_add(r[i], f32_mul(g, v[i]));      // two roundings (rgl_common.h)
 }
 
 // Level l >= 1, one thread per parent (tail_backup); 16 lanes per root (tail_root).
@@ -80,25 +80,28 @@ __global__ void mprl_root_kernel(const TailArgs t) {
 // path G
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void rotate_row(const float* s, int unicycle, float* o) {
-    // cadrl.py:241-276; every product/sum individually rounded like the chain of torch ops
-    const float dx = __fsub_rn(s[5], s[0]), dy = __fsub_rn(s[6], s[1]);
+    // cadrl.py:241-276; every product / sum individually rounded like the chain of torch ops: compiled without contraction (plain
+    // operators: __fmul_rn / __fadd_rn would bring the contraction of the header they come from along).  tests/path_g_steps.py
+    // replays every column bit for bit given this device's atan2f / cosf / sinf.
+#pragma clang fp contract(off)
+    const float dx = s[5] - s[0], dy = s[6] - s[1];
     const float rot = atan2f(dy, dx);
     const float c = cosf(rot), sn = sinf(rot);
-    o[0] = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+    o[0] = sqrtf(dx * dx + dy * dy);
     o[1] = s[7];
-    o[2] = unicycle ? __fsub_rn(s[8], rot) : 0.f;
+    o[2] = unicycle ? s[8] - rot : 0.f;
     o[3] = s[4];
-    o[4] = __fadd_rn(__fmul_rn(s[2], c), __fmul_rn(s[3], sn));
-    o[5] = __fsub_rn(__fmul_rn(s[3], c), __fmul_rn(s[2], sn));
-    const float rx = __fsub_rn(s[9], s[0]), ry = __fsub_rn(s[10], s[1]);
-    o[6] = __fadd_rn(__fmul_rn(rx, c), __fmul_rn(ry, sn));
-    o[7] = __fsub_rn(__fmul_rn(ry, c), __fmul_rn(rx, sn));
-    o[8] = __fadd_rn(__fmul_rn(s[11], c), __fmul_rn(s[12], sn));
-    o[9] = __fsub_rn(__fmul_rn(s[12], c), __fmul_rn(s[11], sn));
+    o[4] = s[2] * c + s[3] * sn;
+    o[5] = s[3] * c - s[2] * sn;
+    const float rx = s[9] - s[0], ry = s[10] - s[1];
+    o[6] = rx * c + ry * sn;
+    o[7] = ry * c - rx * sn;
+    o[8] = s[11] * c + s[12] * sn;
+    o[9] = s[12] * c - s[11] * sn;
     o[10] = s[13];
-    const float ax = __fsub_rn(s[0], s[9]), ay = __fsub_rn(s[1], s[10]);
-    o[11] = sqrtf(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)));
-    o[12] = __fadd_rn(s[4], s[13]);
+    const float ax = s[0] - s[9], ay = s[1] - s[10];
+    o[11] = sqrtf(ax * ax + ay * ay);
+    o[12] = s[4] + s[13];
 }
 
 __global__ void gcn_rotate_kernel(const float* __restrict__ in14, float* __restrict__ out13, int R, int unicycle) {
@@ -117,6 +120,9 @@ __global__ void gcn_prepare_kernel(const float* __restrict__ robot, const float*
                                    const double* __restrict__ robot64, const double* __restrict__ humans64,
                                    const double* __restrict__ actions, int B, int H, int A, int kinematics, double dt,
                                    float* __restrict__ self6, float* __restrict__ hum7, float* __restrict__ reward) {
+    // python-float arithmetic: every float64 product and sum below is rounded on its own (a contracted end-point clearance turns an
+    // exact contact, clearance 0, into a collision)
+#pragma clang fp contract(off)
     // blockDim.x is a multiple of H: the H threads of a (root, action) pair sit in one workgroup, each contributes ITS human's
     // end-point clearance (one float64 sqrt per thread) and thread h == 0 takes the minimum -- it used to walk all H itself
     extern __shared__ double clearance[];

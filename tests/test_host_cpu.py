@@ -87,6 +87,35 @@ def test_host_side_argument_checks_without_gpu():
     assert lib.mprl_pack_children_image_f32(ctypes.byref(pl), ctypes.c_void_p(16), 0, None) != 0
 
 
+def test_path_g_steps_refuse_bad_shapes_without_gpu():
+    """gcn_prepare_f32 / gcn_predict_f32 check their arguments on the host before any launch: B < 1, H = 0, H = 128 (129 nodes),
+    A = 0, A = 257, an unknown kinematics, a NULL action table and NULL arrays are refused; no pointer is read."""
+    lib = nat.lib()
+    p = ctypes.c_void_p(4096)                        # never dereferenced: every call below returns before its launch
+    BAD_SHAPE, BAD_MODE, NULL = -1, -2, -3
+
+    def planner(A=81, kinematics=0, table=p):
+        pl = nat.GcnPlanner()
+        pl.num_actions, pl.kinematics, pl.time_step, pl.gamma = A, kinematics, 0.25, 0.9
+        pl.actions = table
+        return ctypes.byref(pl)
+
+    def prepare(pl, B=4, H=5, robot=p):
+        return lib.gcn_prepare_f32(pl, robot, p, B, H, p, p, p, None)
+
+    def predict(pl, B=4, H=5, ws=p):
+        return lib.gcn_predict_f32(pl, p, p, B, H, ws, 1 << 30, p, p, p, None)
+
+    for call in (prepare, predict):
+        assert call(planner(), B=0) == BAD_SHAPE and call(planner(), B=-3) == BAD_SHAPE
+        assert call(planner(), H=0) == BAD_SHAPE and call(planner(), H=128) == BAD_SHAPE
+        assert call(planner(A=0)) == BAD_SHAPE and call(planner(A=257)) == BAD_SHAPE
+        assert call(planner(kinematics=2)) == BAD_MODE and call(planner(kinematics=-1)) == BAD_MODE
+        assert call(planner(table=None)) in (BAD_SHAPE, NULL)
+        assert call(None) == NULL
+    assert prepare(planner(), robot=None) == NULL and predict(planner(), ws=None) == NULL
+
+
 def test_product_refuses_cpu_tensors():
     pol = make_mprl_policy("trained", 1)
     pol.set_device(torch.device("cpu"))

@@ -1,0 +1,348 @@
+"""The host replay of path G's steps (tests/path_g_steps.py) against the oracle and fixture path_g.npz, and the families the GPU
+tests of tests/test_path_g_steps.py run, with their teeth counted on the CPU.
+
+The replay is what the GPU tests hold gcn_rotate_f32 / gcn_prepare_f32 / gcn_predict_f32 to; here it is pinned to the oracle, which
+tests/test_oracle_golden.py pins to the reference's fixtures: trig-free columns and rewards bit for bit, rotated columns bit for bit
+given torch's own atan2 / cos / sin.  The `fused` switch of the replay is used for one thing only: to count how many cases of a
+family give a different answer when products and sums are contracted -- a family that counts none could not catch a contracted
+kernel.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import rgl_oracle as orc
+from relationalgraphlearning_amd import policy as rga_policy
+from tests import golden_io as gio
+from tests import path_g_steps as pg
+from tests.helpers import dense_scenes
+
+F32, F64 = np.float32, np.float64
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(pg.bits(a), pg.bits(b))
+
+
+def torch_trig(dy, dx):
+    rot = torch.atan2(torch.tensor(dy), torch.tensor(dx))
+    return rot.numpy(), torch.cos(rot).numpy(), torch.sin(rot).numpy()
+
+
+NORM_COLUMNS = {0: (5, 0, 6, 1), 11: (0, 9, 1, 10)}       # dg, da: column -> (x = s[i] - s[j], y = s[k] - s[l])
+
+
+def assert_features_are_the_oracles(rows, got, want, tag):
+    """Every column of the 13 bit for bit, but the two norms: torch's CPU norm kernel accumulates `acc + x * x` in whatever way its
+    build for the host's vector unit contracts it (with fused multiply-adds it returns sqrt(fma(y, y, rn(x * x)))), so there every
+    element must be the replay's individually rounded value or that contracted one (computed exactly), nothing else."""
+    rows, got, want = rows.reshape(-1, 14), got.reshape(-1, 13), want.reshape(-1, 13)
+    assert got.dtype == F32 and want.dtype == F32
+    n_contracted = 0
+    for k in range(13):
+        if k not in NORM_COLUMNS:
+            assert same_bits(got[:, k], want[:, k]), (tag, k, int((pg.bits(got[:, k]) != pg.bits(want[:, k])).sum()))
+            continue
+        off = np.nonzero(pg.bits(got[:, k]) != pg.bits(want[:, k]))[0]
+        if len(off):
+            i, j, m, l = NORM_COLUMNS[k]
+            x, y = (rows[off, i] - rows[off, j]).astype(F32), (rows[off, m] - rows[off, l]).astype(F32)
+            with np.errstate(all="ignore"):
+                alt = np.sqrt(pg.fma(y, y, (x * x).astype(F32), F32))
+            assert same_bits(alt, want[off, k]), (tag, k, len(off))
+            n_contracted += len(off)
+    return n_contracted
+
+
+def constant_value_sd(c):
+    """The fixture's ValueNetwork with the last layer's weight zeroed and its bias c: V = c for every scene."""
+    sd = {k: v.clone() for k, v in gio.path_g_sd().items()}
+    last = sorted(k for k in sd if k.startswith("value_net.") and k.endswith(".weight"))[-1]
+    sd[last] = torch.zeros_like(sd[last])
+    sd[last.replace(".weight", ".bias")] = torch.full_like(sd[last.replace(".weight", ".bias")], c)
+    return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# rotate
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kin", ["holonomic", "unicycle"])
+def test_rotate_is_the_oracles_given_torchs_trig(kin):
+    g = gio.load("path_g")
+    rows = np.concatenate([pg.rotate_rows(4000), g["g.rotate_in"]])
+    dx, dy = pg.goal_offsets(rows)
+    got = pg.rotate(rows, kin, torch_trig(dy, dx))
+    want = orc.rotate_pairwise(torch.tensor(rows), kin).numpy()
+    assert_features_are_the_oracles(rows, got, want, kin)
+
+
+def test_rotate_on_the_fixture():
+    """The reference's own recorded features: every column bit for bit given torch's trig (the two norms: as the recording host's
+    torch contracted them, see assert_features_are_the_oracles)."""
+    g = gio.load("path_g")
+    rows = g["g.rotate_in"]
+    dx, dy = pg.goal_offsets(rows)
+    for kin, key in (("holonomic", "g.rotate_out"), ("unicycle", "g.rotate_out_unicycle")):
+        got = pg.rotate(rows, kin, torch_trig(dy, dx))
+        assert_features_are_the_oracles(rows, got, g[key], key)
+
+
+def test_probe_rows_read_the_trig_back_exactly():
+    """with_probes / trig_from_probes on the replay itself, fused or not: (rot, c, sn) come back as given."""
+    rows = pg.rotate_rows(64)
+    dx, dy = pg.goal_offsets(rows)
+    rot, c, sn = torch_trig(dy, dx)
+    three = pg.with_probes(rows)
+    t3 = tuple(np.repeat(x, 3) for x in (rot, c, sn))
+    for fused in (False, True):
+        back = pg.trig_from_probes(pg.rotate(three, "holonomic", t3, fused), pg.rotate(three, "unicycle", t3, fused))
+        for got, want in zip(back, (rot, c, sn)):
+            assert np.array_equal(got, want)
+    assert same_bits(three[0::3], rows)
+
+
+def test_rotated_columns_can_tell_a_fused_sum():
+    """Teeth of the rotate test: a contracted `a * c + b * s` differs from the two-rounding value in about a quarter of the
+    rotated values of these rows (counted: see the assertion), so dense rows do tell a fused rotate_row from the reference's chain of torch operations."""
+    rows = pg.rotate_rows(2000)
+    rng = np.random.RandomState(31)                  # any float32 (c, sn) serve the count; no libm call, so the count is the same on every host
+    trig = (np.zeros(2000, F32), rng.uniform(-1, 1, 2000).astype(F32), rng.uniform(-1, 1, 2000).astype(F32))
+    a, b = pg.rotate(rows, "holonomic", trig), pg.rotate(rows, "holonomic", trig, fused=True)
+    differ = int((a[:, list(pg.ROTATED)] != b[:, list(pg.ROTATED)]).sum())
+    assert differ >= 2000, differ                                        # of 12000 rotated values
+    assert differ == N_ROTATE_FUSED, differ
+
+
+N_ROTATE_FUSED = 3088       # of 12000 rotated values, counted with the exact emulation (profiles/path_g_steps.txt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# prepare and decide against the oracle's one-step search
+# ---------------------------------------------------------------------------------------------------------------------------
+def _replay_search(robot, humans, sd, cfg, table):
+    """The replay's prepare -> the ORACLE's rotate + network on the replay's joint rows -> the replay's decide."""
+    joint, self6, hum7, rew = pg.prepare(robot.astype(F32), humans.astype(F32), table, cfg.kinematics, cfg.time_step, (robot, humans),
+                                         torch_trig)
+    B, A, H = joint.shape[:3]
+    with torch.no_grad():
+        rot = orc.rotate_pairwise(torch.tensor(joint.reshape(-1, 14)), cfg.kinematics)
+        v = orc.gcn_value_forward(rot.reshape(B * A, H, 13), sd, cfg)[0][:, 0].numpy()
+    # the replay's own features are the oracle's, so the network saw the replay's rows (the two norms: see the helper)
+    # (torch's vectorised atan2 / cos / sin do not give the H equal rows of a pair equal values: self6 is the first row's)
+    mine = rot.numpy().reshape(B * A, H, 13).copy()
+    mine[:, 0, :6], mine[:, :, 6:] = self6, hum7
+    assert_features_are_the_oracles(joint, mine, rot.numpy(), cfg.kinematics)
+    nr, nh = pg.propagate(None, None, table, cfg.kinematics, cfg.time_step, (robot, humans))
+    rew64 = pg.reward_of(*pg.clearances(nr, nh), nr[:, :, 4], cfg.time_step)          # the reference adds the float64 reward
+    assert same_bits(rew64.astype(F32).reshape(-1), rew)
+    as_device = pg.decide(rew.reshape(B, A), v.reshape(B, A), cfg.gamma, cfg.time_step, robot[:, 7].astype(F32))
+    as_reference = pg.decide(rew64, v.reshape(B, A), cfg.gamma, cfg.time_step, robot[:, 7].astype(F32))
+    with np.errstate(all="ignore"):       # reading the float32 rewards: half a unit of the float32 reward, then one rounding of the sum
+        r32 = rew.reshape(B, A)
+        assert (np.abs(as_device[0].astype(F64) - as_reference[0]) <= 0.5 * np.spacing(np.abs(r32)) + np.spacing(np.abs(as_reference[0]))).all()
+    return rew64, as_reference
+
+
+@pytest.mark.parametrize("kin", ["holonomic", "unicycle"])
+def test_prepare_and_decide_are_the_batched_oracle(kin):
+    """gcn_predict_batched on the fixture's scenes and on dense scenes: its float64 action values, rounded to float32, and its
+    decisions are the replay's, bit for bit -- with the trained weights and with V = c (ties everywhere)."""
+    g = gio.load("path_g")
+    cfg = orc.OracleConfig(kinematics=kin)
+    table = orc.cadrl_action_space(cfg, 1.0)
+    rt, ht = dense_scenes(np.random.RandomState(77), 24, 5)
+    scenes = [(g["g.pred_robot"], g["g.pred_humans"]), (rt.numpy().astype(F64), ht.numpy().astype(F64))]
+    n_tied = 0
+    for robot, humans in scenes:
+        for sd in (gio.path_g_sd(), constant_value_sd(0.375)):
+            ob, ov = orc.gcn_predict_batched(robot, humans, sd, cfg)
+            rew, (vals, best, best_value) = _replay_search(robot, humans, sd, cfg, table)
+            assert same_bits(vals, ov.astype(F32)), kin
+            assert np.array_equal(best, ob.astype(np.int32))
+            assert same_bits(best_value, ov[np.arange(len(ob)), ob].astype(F32))
+            n_tied += int(((vals == vals.max(1, keepdims=True)).sum(1) > 1).sum())
+    assert n_tied > 0
+
+
+def test_prepare_is_the_sequential_oracle_and_the_fixture():
+    """gcn_predict_sequential (compute_reward_g on python floats) with V = c: its values are reward + gamma^(dt v) * c, so the
+    replay's rewards are held bit for bit, scene by scene; with the trained weights the fixture's recorded decisions are met."""
+    g = gio.load("path_g")
+    cfg = orc.OracleConfig()
+    table = orc.cadrl_action_space(cfg, 1.0)
+    robot, humans = g["g.pred_robot"], g["g.pred_humans"]
+    c = 0.375
+    rew, (vals, best, _) = _replay_search(robot, humans, constant_value_sd(c), cfg, table)
+    for b in range(robot.shape[0]):
+        a, seq = orc.gcn_predict_sequential([float(x) for x in robot[b]], [[float(x) for x in row] for row in humans[b]],
+                                            constant_value_sd(c), cfg)
+        assert a == int(best[b])
+        assert same_bits(np.array(seq, F64).astype(F32), vals[b])
+    _, (vals, best, _) = _replay_search(robot, humans, gio.path_g_sd(), cfg, table)
+    assert np.array_equal(best, g["g.pred_action"])
+    assert np.abs(vals - g["g.pred_action_values"]).max() <= 2e-6
+
+
+@pytest.mark.parametrize("kin", ["holonomic", "unicycle"])
+def test_rewards_are_compute_reward_g(kin):
+    """Every (root, action) pair of dense scenes through the oracle's scalar compute_reward_g: the same branch everywhere, the
+    constants -0.25 / 0 / 1 bit for bit.  Its distances are np.linalg.norm's -- a BLAS dot product, contracted or not as the
+    host's BLAS pleases -- so a discomfort value may sit one rounding of dist^2 away: |d dist| <= ulp(dist) <= 2^-50 for the
+    distances below 8 m that reach this branch, times 0.5 * dt: 1.2e-16; held to 2e-16.  The batched oracle, whose distances are
+    individually rounded numpy operations, is met bit for bit (test_prepare_and_decide_are_the_batched_oracle)."""
+    cfg = orc.OracleConfig(kinematics=kin)
+    table = orc.cadrl_action_space(cfg, 1.0)
+    rt, ht = dense_scenes(np.random.RandomState(78), 12, 7)
+    robot, humans = rt.numpy(), ht.numpy()
+    nr, nh = pg.propagate(robot, humans, table, kin, 0.25)
+    rew = pg.reward_of(*pg.clearances(nr, nh), nr[:, :, 4], 0.25)
+    kinds = set()
+    for b in range(nr.shape[0]):
+        for a in range(nr.shape[1]):
+            want = orc.compute_reward_g([float(x) for x in nr[b, a]], [[float(x) for x in row] for row in nh[b]], 0.25)
+            kind = -1 if want == -0.25 else (1 if want == 1 else (2 if want < 0 else 0))
+            mine = -1 if rew[b, a] == -0.25 else (1 if rew[b, a] == 1 else (2 if rew[b, a] < 0 else 0))
+            assert kind == mine and (F64(want) == rew[b, a] if kind != 2 else abs(want - rew[b, a]) <= 2e-16), (b, a, want, rew[b, a])
+            kinds.add(kind)
+    assert kinds == {-1, 0, 1, 2}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the first-maximum rule
+# ---------------------------------------------------------------------------------------------------------------------------
+def decision_rows():
+    nan, inf = np.nan, np.inf
+    rows = [[1, 2, 2, 0], [3, 3, 1, 3], [0.0, -0.0, -0.0, 0.0], [-0.0, 0.0, 0.0, -0.0], [nan, 5, 6, 6], [1, nan, 0, 1],
+            [-inf, -inf, -inf, -inf], [nan, nan, nan, nan], [nan, -inf, nan, -inf], [-inf, -1, -inf, -1], [inf, inf, 1, nan],
+            [1, inf, inf, -inf], [-inf, nan, -5, -5], [nan, nan, nan, 2], [-1e-45, -0.0, 0.0, 1e-45]]
+    return np.array(rows, F64)
+
+
+def test_policys_first_strict_maximum_is_decides_rule():
+    """policy._first_strict_maximum (what query_env's search and the documentation of gcn_argmax_kernel promise) against the
+    replay's strict `>` walk from -inf: ties, the two zeros, infinities, NaNs, all-NaN and all -inf rows; float32 and float64."""
+    rows = decision_rows()
+    want, _ = pg.first_strict_maximum(rows)
+    assert want.tolist() == [1, 0, 0, 0, 2, 0, -1, -1, -1, 1, 0, 1, 2, 3, 3]
+    for dt in (torch.float64, torch.float32):
+        got = rga_policy._first_strict_maximum(torch.tensor(rows).to(dt))
+        assert got.dtype == torch.int32 and got.tolist() == pg.first_strict_maximum(rows.astype(F32 if dt == torch.float32 else F64))[0].tolist()
+    rng = np.random.RandomState(9)
+    v = rng.randint(-2, 3, (500, 33)).astype(F64)                          # many ties, the winner in every column
+    v[rng.rand(500, 33) < 0.1] = np.nan
+    v[rng.rand(500, 33) < 0.05] = -np.inf
+    want, _ = pg.first_strict_maximum(v)
+    assert rga_policy._first_strict_maximum(torch.tensor(v)).tolist() == want.tolist()
+    # decide on the same rows: value = the row, reward 0, disc 1
+    vals, best, bv = pg.decide(np.zeros_like(rows, F32), rows.astype(F32), 0.9, 0.25, np.zeros(len(rows), F32))
+    assert best.tolist() == pg.first_strict_maximum(rows.astype(F32))[0].tolist()
+    assert (bv[best < 0] == 0).all() and same_bits(bv[best >= 0], vals[best >= 0, best[best >= 0]])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the threshold families
+# ---------------------------------------------------------------------------------------------------------------------------
+# (pairs whose reference clearance is exactly 0, of those a contracted evaluation makes a collision, pairs whose contracted reward
+# differs at all) of 4096, counted with the exact emulation of the contractions
+N_CONTACT_G = (4096, 170, 342)
+N_CONTACT_M = (4096, 212, 428)
+
+
+def contact_tables():
+    """The policies' own tables (v_pref 1): path G's rotation-major one, path M's speed-major one; row 0 is the stop action."""
+    cfg = orc.OracleConfig()
+    return orc.cadrl_action_space(cfg, 1.0), orc.mprl_action_space(cfg, 1.0)[0]
+
+
+def _count_contact(segment):
+    robot, humans, table, mine = pg.contact_family(contact_tables()[int(segment)], segment=segment)
+    P = robot.shape[0]
+    idx = np.arange(P)
+    one = lambda x: x[idx, mine]
+    if segment:
+        d0, gd0 = pg.segment_clearances(robot, humans, table, 0.25)
+        sel_r, sel_h = robot, humans
+        # only the contact action of every parent through the (slow) fused evaluation: one table row per parent
+        d1 = np.stack([pg.segment_clearances(robot[p:p + 1], humans[p:p + 1], table[mine[p]:mine[p] + 1], 0.25, fused=True)[0][0, 0]
+                       for p in range(P)])
+        gd1 = one(gd0)
+    else:
+        nr, nh = pg.propagate(None, None, table, "holonomic", 0.25, (robot, humans))
+        d0, gd0 = pg.clearances(nr, nh)
+        d1 = np.stack([pg.clearances(*pg.propagate(None, None, table[mine[p]:mine[p] + 1], "holonomic", 0.25,
+                                                   (robot[p:p + 1], humans[p:p + 1]), fused=True), fused=True)[0][0, 0] for p in range(P)])
+        gd1 = one(gd0)
+    r0 = pg.reward_of(one(d0), one(gd0), robot[:, 4], 0.25)
+    r1 = pg.reward_of(d1, gd1, robot[:, 4], 0.25)
+    return (int((one(d0)[:, 0] == 0).sum()), int(((d1[:, 0] < 0) & (one(d0)[:, 0] == 0)).sum()), int((r0 != r1).sum())), (robot, humans, table, mine, r0)
+
+
+def test_exact_contact_family_of_path_g_has_teeth():
+    """float64 roots, human radius = end-point distance - robot radius: the reference's clearance is exactly 0 in most pairs
+    (reward (0 - 0.2) * 0.5 * dt = -0.025, no collision) and a contracted evaluation makes it negative (-0.25) in more than 100
+    of the 4096."""
+    counts, (robot, humans, table, mine, r0) = _count_contact(False)
+    assert counts[0] > 3000 and counts[1] >= 100, counts
+    assert (r0[pg.clearances(*pg.propagate(None, None, table, "holonomic", 0.25, (robot, humans)))[0][np.arange(len(mine)), mine, 0] == 0]
+            == (0.0 - 0.2) * 0.5 * 0.25).all()
+    assert counts == N_CONTACT_G, counts
+    # the batched oracle on the whole family, V = 0: its action values ARE its rewards
+    ob, ov = orc.gcn_predict_batched(robot, humans, constant_value_sd(0.0), orc.OracleConfig())
+    nr, nh = pg.propagate(None, None, table, "holonomic", 0.25, (robot, humans))
+    assert same_bits(ov + 0.0, pg.reward_of(*pg.clearances(nr, nh), nr[:, :, 4], 0.25) + 0.0)
+    assert np.array_equal(ov[np.arange(len(mine)), mine], r0)
+
+
+def test_exact_contact_family_of_path_m_has_teeth():
+    """The same recipe on path M's segment distance; expectations are orc.estimate_reward_batched's on the float64 arrays
+    (root=True), which the replay's segment_reward must reproduce bit for bit for the whole (P, A) table."""
+    counts, (robot, humans, table, mine, r0) = _count_contact(True)
+    want = orc.estimate_reward_batched(robot, humans, table, orc.OracleConfig(), root=True)
+    got = pg.segment_reward(robot, humans, table, 0.25)
+    assert same_bits(got + 0.0, want + 0.0)
+    assert np.array_equal(want[np.arange(len(mine)), mine], r0)
+    assert counts[0] > 3000 and counts[1] >= 100, counts
+    assert counts == N_CONTACT_M, counts
+
+
+def test_goal_boundary_family():
+    """Goal distance exactly the radius is not reaching; one float64 ulp of radius more is.  Replay, scalar oracle and the
+    construction agree."""
+    robot, humans, table, k, reach = pg.goal_boundary_family()
+    nr, nh = pg.propagate(None, None, table, "holonomic", 0.25, (robot, humans))
+    d, gd = pg.clearances(nr, nh)
+    P = len(k)
+    assert (gd[np.arange(P), k][~reach] == robot[~reach, 4]).all() and (gd[np.arange(P), k][reach] < robot[reach, 4]).all()
+    rew = pg.reward_of(d, gd, nr[:, :, 4], 0.25)
+    want = np.zeros((P, 4))
+    want[np.arange(P), k] = reach
+    assert np.array_equal(rew, want) and reach.sum() == P // 2 > 10
+    for p in range(P):
+        for a in range(4):
+            assert orc.compute_reward_g([float(x) for x in nr[p, a]], [[float(x) for x in row] for row in nh[p]], 0.25) == want[p, a]
+    # not float32 numbers: the float32 rows alone could not carry the family (they round the larger radius back)
+    assert (robot[reach, 4].astype(F32).astype(F64) != robot[reach, 4]).all()
+
+
+def test_collision_beats_goal_family():
+    robot, humans, table, want = pg.collision_beats_goal_family()
+    nr, nh = pg.propagate(None, None, table, "holonomic", 0.25, (robot, humans))
+    d, gd = pg.clearances(nr, nh)
+    assert (gd[0, :2] < robot[0, 4]).all() and d[0, 0].min() < 0 and d[0, 3].min() == 0.0
+    assert np.array_equal(pg.reward_of(d, gd, nr[:, :, 4], 0.25), want)
+    for a in range(4):
+        assert orc.compute_reward_g([float(x) for x in nr[0, a]], [[float(x) for x in row] for row in nh[0]], 0.25) == want[0, a]
+
+
+def test_unicycle_family_excludes_no_pair():
+    """The GPU test compares unicycle rewards where every decision margin of the replay exceeds 1e-9 (device and host float64
+    cos / sin differ by a few 1e-16, scaled by at most v * dt): this family is chosen so that the rule excludes nothing."""
+    cfg = orc.OracleConfig(kinematics="unicycle")
+    table = orc.cadrl_action_space(cfg, 1.0)
+    for B, H, seed in pg.UNICYCLE_CASES:
+        robot, humans, _ = pg.probe_scenes(np.random.RandomState(seed), B, H)
+        nr, nh = pg.propagate(robot, humans, table, "unicycle", 0.25)
+        d, gd = pg.clearances(nr, nh)
+        m = np.minimum.reduce(pg.margins(d, gd, nr[:, :, 4]))
+        assert (m > 1e-9).all(), (B, H, float(m.min()))

@@ -119,7 +119,7 @@ typedef struct RglGraph {
  *              NULL, models the one-wave-per-scene MFMA kernel covers (the shipped path-M shapes: w_r 9-64-32, w_h 5-64-32,
  *              x_dim 32, <= 4 layers, N <= 128 (concatenation: N <= 64), every similarity function, layerwise graphs) run on
  *              it; other embedding MLPs and x_dim = 64 (embedded_gaussian / gaussian, one adjacency, 1-3 layers, N <= 64) run on
- *              the MFMA tile kernels (rgl_backward_mfma.hip); everything else, and every call without workspace, runs on the
+ *              the MFMA tile kernels (rgl_tile_pipeline.hip); everything else, and every call without workspace, runs on the
  *              general kernel -- same numbers up to summation order.
  * Limits: N = H+1 <= RGL_MAX_NODES, x_dim <= RGL_MAX_XDIM, widths <= RGL_MAX_WIDTH.
  * ------------------------------------------------------------------------------------------- */
@@ -139,7 +139,7 @@ int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_head, const
  * 199-250).  Supported: all eight similarity functions, layerwise_graph 0 | 1.  Two implementations behind this entry point:
  * a per-scene kernel (one workgroup and one gradient slab per scene; RGL_ERR_LDS when a scene's activations exceed the 160 KB
  * LDS of a CU: N = 64 with deep MLPs) and, for embedded_gaussian / gaussian with one adjacency, x_dim 32 | 64, 1-3 layers,
- * N <= 64, a pipeline of MFMA tile kernels (rgl_backward_mfma.hip) -- taken from 256 scenes, whenever `stream` is being
+ * N <= 64, a pipeline of MFMA tile kernels (rgl_tile_pipeline.hip) -- taken from 256 scenes, whenever `stream` is being
  * captured into a hipGraph, and where the per-scene kernel does not fit.  Environment: RGL_BACKWARD_MFMA = 0 | 1 forces a
  * path (2: RGL_ERR_BAD_MODE instead of the per-scene kernel where the pipeline does not apply), RGL_BACKWARD_MFMA_MIN moves the
  * threshold.  Both are deterministic (fixed summation order per shape) -- but they are TWO summation orders: the same call below the
@@ -163,7 +163,7 @@ int rgl_graph_backward_f32(const RglGraph* graph, const RglMlp* value_head, cons
                            const float* d_value, const float* d_humans_next, const float* d_H,
                            float* grad_out, void* workspace, size_t workspace_bytes, rgl_stream_t stream);
 
-/* rgl_plan_mlp_rows (ABI 8, additive) -- which launch form the MFMA row kernels (rgl_backward_mfma.hip) take for one MLP over
+/* rgl_plan_mlp_rows (ABI 8, additive) -- which launch form the MFMA row kernels (rgl_rows.hip) take for one MLP over
  * n_rows rows: the tile pipeline runs w_r (a row per scene), w_h (a row per human), the value head (a row per scene) and the
  * motion head (a row per human) as such jobs, in the backward pass and in the forward of models outside the shipped shapes.
  * HOST ONLY: no device call, no launch; reads n_layers and dims of `mlp` (the weight pointers are not read).  max_waves: the
@@ -185,7 +185,7 @@ typedef struct RglRowsPlan {
 int rgl_plan_mlp_rows(const RglMlp* mlp, int n_rows, int max_waves, RglRowsPlan* plan);
 
 /* rgl_plan_graph_tiles (ABI 8, additive) -- which instantiation of the tile pipeline's graph kernel (graph_kernel<NT, XT, L, BWD,
- * COS, LW> of rgl_backward_mfma.hip) a graph of n_scenes scenes of H humans launches, and on how many workgroups.  The answer
+ * COS, LW> of rgl_graph_kernel.h) a graph of n_scenes scenes of H humans launches, and on how many workgroups.  The answer
  * comes from the functions the launcher itself calls.  HOST ONLY: no device call, no launch; reads x_dim, num_layer, similarity
  * and layerwise_graph of `graph` (no pointer of it is read).  backward: 0 the forward build, 1 the backward build (the backward
  * pipeline launches both).  max_workgroups: the cap the backward applies to its graph launch while the caller's workspace is

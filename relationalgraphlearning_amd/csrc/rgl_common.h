@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "rgl_hip.h"
 
 #define RGL_HIP_TRY(expr)                          \
@@ -135,15 +137,15 @@ size_t scene_children_workspace_bytes(int P, int A, int H);                     
 int launch_backward_mfma(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                          const float* humans, int n_scenes, int H, int detach_graph, const float* d_value,
                          const float* d_humans_next, const float* d_H, float* grad_out, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, int only_choice);                                                                     // rgl_backward_mfma.hip
+                         hipStream_t stream, int only_choice);                                                                     // rgl_tile_pipeline.hip
 
-// forward of models outside the shipped shapes (other embedding MLPs, x_dim = 64) on the tile kernels of rgl_backward_mfma.hip instead
+// forward of models outside the shipped shapes (other embedding MLPs, x_dim = 64) on the tile kernels of rgl_tile_pipeline.hip instead
 // of the general VALU kernel: embedded_gaussian / gaussian, one adjacency, 1-3 layers, N <= 64.  0 bytes / 1 = not covered.
 size_t tiles_forward_workspace_bytes(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, int S, int crowds_per,
                                      int H, int want_H);
 int launch_tiles_forward(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                          const float* humans, int S, int crowds_per, int H, float* H_out, float* value_out, float* humans_next,
-                         void* workspace, size_t workspace_bytes, hipStream_t stream);                               // rgl_backward_mfma.hip
+                         void* workspace, size_t workspace_bytes, hipStream_t stream);                               // rgl_tile_pipeline.hip
 
 inline int mlp_max_hidden(const RglMlp& m) {
     int w = 0;
@@ -154,6 +156,12 @@ inline int mlp_max_hidden(const RglMlp& m) {
 }  // namespace rgl
 
 namespace {
+
+// an integer environment switch, read on every call (a caller that wants it read once per process keeps a `static` of its own)
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return (e && e[0]) ? atoi(e) : dflt;
+}
 
 // One operation, rounded on its own.  The search's bookkeeping, the rewards and path G's features follow the reference's chains of
 // scalar / tensor operations -- a product and the sum that takes it are two roundings -- and tests/search_bookkeeping.py and

@@ -1150,11 +1150,6 @@ inline int fused_cu_count() {
     return n_cu;
 }
 
-inline int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e && e[0] ? atoi(e) : dflt;
-}
-
 // `unit`: parents are handed to workgroups in blocks that are multiples of this (the parents of one root at the deepest level when
 // the kernel's tail walks the back-up chain; 1 otherwise).  Workgroup b owns parents [b k, (b + 1) k), k = the smallest multiple of
 // `unit` that covers P with one workgroup per CU.  Within a workgroup the items are dealt over the 8 waves in snake passes (waves w

@@ -434,7 +434,7 @@ int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float
     const bool ok = scene_kernel_covers(g, N) && mlp_is(mh, XD, HID, 5, false) && workspace &&
                     workspace_bytes >= (size_t)P * N * XD * sizeof(float) && P % crowds_per == 0;
     if (!ok) {
-        // outside the shipped shapes: the tile kernels (rgl_backward_mfma.hip) where they cover the model, else the general kernel
+        // outside the shipped shapes: the tile kernels (rgl_tile_pipeline.hip) where they cover the model, else the general kernel
         if (P % crowds_per == 0) {
             const int rc = launch_tiles_forward(&g, nullptr, &mh, robot, humans, P, crowds_per, H, nullptr, nullptr, humans_next, workspace,
                                                 workspace_bytes, stream);

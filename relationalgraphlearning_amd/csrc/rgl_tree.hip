@@ -730,7 +730,7 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
     // inputs, 64-32 embeddings, head 150-100-100-1), else the general kernel
     rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, fwd_ws, fwd_bytes,
                                    st, rows_image);
-    if (rc == 1)      // other embedding MLPs (x_dim 32: what this workspace is sized for): the tile kernels of rgl_backward_mfma.hip
+    if (rc == 1)      // other embedding MLPs (x_dim 32: what this workspace is sized for): the tile kernels of rgl_tile_pipeline.hip
         rc = rgl::launch_tiles_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, value, nullptr, fwd_ws,
                                        fwd_bytes, st);
     if (rc == 1) {

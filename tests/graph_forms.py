@@ -1,4 +1,4 @@
-"""graph_kernel<NT, XT, L, BWD, COS, LW> of csrc/rgl_backward_mfma.hip -- the tile pipeline's similarity block, its normalisation,
+"""graph_kernel<NT, XT, L, BWD, COS, LW> of csrc/rgl_graph_kernel.h -- the tile pipeline's similarity block, its normalisation,
 the GCN layers and the way back -- in every instantiation launch_graph reaches: the case table, the instantiation and grid each
 run takes (asked of the library: rgl_plan_graph_tiles, host only) and the float64 references (tests/row_forms.py's).  Nothing
 here needs a GPU.

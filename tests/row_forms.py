@@ -1,4 +1,4 @@
-"""The MLP row kernels of csrc/rgl_backward_mfma.hip in every form they launch: the case table, the form each case takes (asked of
+"""The MLP row kernels of csrc/rgl_rows.hip in every form they launch: the case table, the form each case takes (asked of
 the library: rgl_plan_mlp_rows, host only) and the float64 references.  Nothing here needs a GPU.
 
 A "run" is one model (x_dim, wr_dims, wh_dims, value_network_dims or motion_predictor_dims) on S scenes of H humans, through the

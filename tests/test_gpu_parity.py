@@ -751,7 +751,7 @@ def test_scene_kernel_split_and_unsplit_forced(dev):
 
 
 def test_tile_pipeline_forced_over_the_module_and_training_tests(dev):
-    """The tile kernels of rgl_backward_mfma.hip are chosen by shape (forward: models outside the shipped shapes) and by batch size
+    """The tile kernels of rgl_tile_pipeline.hip are chosen by shape (forward: models outside the shipped shapes) and by batch size
     (backward: from 256 scenes).  Forced on for everything they cover -- RGL_TILES_FORWARD=2, RGL_BACKWARD_MFMA=1 -- the forward KATs,
     the state-predictor tests, the non-default heads, every gradient test and the reference-trainer fixtures must stay green (this
     run found the 6-layer head whose weights alone exceed one half of a CU's LDS)."""
@@ -1137,7 +1137,7 @@ print("OK worst relative error %.2e" % worst)
 
 def test_non_default_embeddings_and_x_dim_on_the_tile_kernels(dev):
     """VERDICT r2 item 9 / missing 3: `X_dim` = 64 and `wr_dims` / `wh_dims` other than the shipped [64, 32] used to run on the general
-    VALU kernel (1.8 % of peak).  They now take the tile kernels of rgl_backward_mfma.hip -- MFMA row kernels for any MLP, one
+    VALU kernel (1.8 % of peak).  They now take the tile kernels of rgl_tile_pipeline.hip -- MFMA row kernels for any MLP, one
     workgroup per scene for the graph block with x_dim 32 | 64 -- in the module forwards, the state predictor, the children's values
     of a search (sibling scenes share their crowd's embedded rows) and the backward pass.  With RGL_REQUIRE_MFMA_CHILDREN /
     RGL_REQUIRE_MFMA_FORWARD = 1 the library refuses the general kernel, so passing proves the path.  Randomly initialised models
@@ -2312,7 +2312,7 @@ def test_gradients_value_estimator_and_state_predictor(H, L, sim, skip, flavour,
     (4, 3, "cosine_softmax", False, "trained", 6),
     (40, 1, "cosine_softmax", True, "trained", 3),])
 def test_gradients_on_the_mfma_backward(H, L, sim, skip, flavour, B, dev, monkeypatch):
-    """The tile pipeline of rgl_backward_mfma.hip (the large-batch backward: MFMA row kernels for the MLPs, one wave per scene for the
+    """The tile pipeline of rgl_tile_pipeline.hip (the large-batch backward: MFMA row kernels for the MLPs, one wave per scene for the
     graph block) forced on for the small oracle-autograd cases of the test above (it is chosen by batch size otherwise), and for the
     RGL-output / path-G gradients."""
     monkeypatch.setenv("RGL_BACKWARD_MFMA", "2")        # 2: an error instead of the per-scene kernel where the pipeline says "not mine"

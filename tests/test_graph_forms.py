@@ -1,4 +1,4 @@
-"""graph_kernel<NT, XT, L, BWD, COS, LW> of csrc/rgl_backward_mfma.hip in every instantiation it launches, with workgroups that walk
+"""graph_kernel<NT, XT, L, BWD, COS, LW> of csrc/rgl_graph_kernel.h in every instantiation it launches, with workgroups that walk
 several scenes (tests/graph_forms.py: the runs, the instantiation and the grid each takes by the library's own planner -- held on
 the CPU by tests/test_graph_forms_cpu.py -- and the references).  The harness is tests/test_row_forms.py's.
 

@@ -1,4 +1,4 @@
-"""The MLP row kernels of csrc/rgl_backward_mfma.hip, forward and backward, in every form they launch (tests/row_forms.py: the
+"""The MLP row kernels of csrc/rgl_rows.hip, forward and backward, in every form they launch (tests/row_forms.py: the
 runs, the form each takes by the library's own planner -- held on the CPU by tests/test_row_forms_cpu.py -- and the references).
 
   a. forward and every parameter gradient of every run against torch autograd over the oracle in FLOAT64, under the project's

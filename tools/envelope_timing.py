@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Models outside the shipped shapes (X_dim = 64, other wr_dims / wh_dims): time of a depth-2 search step and of a value-estimator
-forward on the tile kernels of rgl_backward_mfma.hip against the general VALU kernel (RGL_TILES_FORWARD=0)."""
+forward on the tile kernels of rgl_tile_pipeline.hip against the general VALU kernel (RGL_TILES_FORWARD=0)."""
 import os
 import subprocess
 import sys

@@ -13,7 +13,7 @@ if [ "$1" = run ]; then
 fi
 T=$(mktemp -d); mkdir -p $T/relationalgraphlearning_amd $ROOT/ab
 cp -r $ROOT/relationalgraphlearning_amd/csrc $T/relationalgraphlearning_amd/; cp -r $ROOT/include $T/
-python - "$T/relationalgraphlearning_amd/csrc/rgl_backward_mfma.hip" <<'PY'
+python - "$T/relationalgraphlearning_amd/csrc/rgl_tile_pipeline.hip" <<'PY'
 import sys
 p = sys.argv[1]
 s = open(p).read()

@@ -85,7 +85,7 @@ def main():
                                            "flops_per_step": flops,
                                            "note": "forwards on the one-wave-per-scene MFMA kernel; backward: the per-scene VALU kernel "
                                                    "below 256 scenes of an eager step (launch / host bound there), the MFMA tile "
-                                                   "pipeline of rgl_backward_mfma.hip from 256 scenes and in every captured step"}}))
+                                                   "pipeline of rgl_tile_pipeline.hip from 256 scenes and in every captured step"}}))
 
 
 if __name__ == "__main__":

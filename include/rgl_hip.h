@@ -354,6 +354,28 @@ typedef struct MprlPlanner {
     double action_speed_bound;
 } MprlPlanner;
 
+/* rgl_plan_prologue_embedding (ABI 8, additive) -- how a tree level of P parents (crowds of H humans, crowds_per sibling parents
+ * per crowd) runs its embeddings when the fused children kernel's level prologue takes it: every workgroup embeds the rows of the
+ * parents it owns in chunks, the human rows of a chunk's distinct crowds once per crowd and packed densely into 16-row tiles, the
+ * chunk's robot rows as one tile.  The answer comes from the functions the launcher itself calls.  HOST ONLY: no launch; reads
+ * the dimensions and modes of `planner` (no pointer of it is read), the process's RGL_LEVEL_PROLOGUE setting (once) and the
+ * device's CU count (256 without a device).  unit: parents go to workgroups in multiples of it -- 1, or the parents per root at the
+ * deepest level of a search whose back-up chain runs in the kernel's tail.
+ *   prologue        0: the level keeps its three launches (the other fields are 0 then) -- outside the prologue's form (bf16x6,
+ *                   17..20 nodes, softmax similarity, a graph state predictor), fewer than 4 parents per CU, or switched off.
+ *                   (A traced search keeps the three launches whatever this says.)
+ *   parents_per_wg  workgroup b owns parents [b k, (b + 1) k); workgroups of them
+ *   chunk_parents   parents of a workgroup's first chunk: min(16, parents_per_wg, what chunk_crowds allows)
+ *   chunk_crowds    most distinct crowds of a chunk (12, fewer for a predictor of 3 or 4 layers); a chunk ends before one more
+ *   human_tiles, robot_tiles   16-row tiles of that first chunk when it starts on a crowd boundary
+ *   row_floats      LDS floats of the row buffer, [chunk_crowds][H][32] + [16][32]
+ *   chunks_per_wg   chunks a full workgroup walks
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (P, H, crowds_per or unit < 1, P no multiple of crowds_per). */
+typedef struct RglPrologueEmbeddingPlan {
+    int prologue, parents_per_wg, workgroups, chunk_parents, chunk_crowds, human_tiles, robot_tiles, row_floats, chunks_per_wg, reserved;
+} RglPrologueEmbeddingPlan;
+int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, int H, int crowds_per, int unit, RglPrologueEmbeddingPlan* plan);
+
 /* Bytes of the weight image above; 0 when the configuration has no image-based children kernel (the searches then ignore
  * `children_image`).  Depends on the architecture only (not on the weights, P, A or H).  Round 4: also offered for three-layer
  * graphs and crowds beyond 32 agents with the shipped embedding / head shapes (f32 layout): there the

@@ -54,6 +54,11 @@ class RglGraphTilesPlan(C.Structure):
                 ("norm", C.c_int), ("grid", C.c_int), ("resident", C.c_int), ("lds_bytes", C.c_size_t)]
 
 
+class RglPrologueEmbeddingPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("prologue", "parents_per_wg", "workgroups", "chunk_parents", "chunk_crowds", "human_tiles",
+                                       "robot_tiles", "row_floats", "chunks_per_wg", "reserved")]
+
+
 class RglGraph(C.Structure):
     _fields_ = [("w_r", RglMlp), ("w_h", RglMlp), ("x_dim", C.c_int), ("num_layer", C.c_int),
                 ("similarity", C.c_int), ("layerwise_graph", C.c_int), ("skip_connection", C.c_int),
@@ -122,6 +127,7 @@ SIGNATURES = {
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "rgl_plan_mlp_rows": (C.c_int, [C.POINTER(RglMlp), C.c_int, C.c_int, C.POINTER(RglRowsPlan)]),
     "rgl_plan_graph_tiles": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglGraphTilesPlan)]),
+    "rgl_plan_prologue_embedding": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglPrologueEmbeddingPlan)]),
     "rgl_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rgl_transpose_many_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rgl_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -169,6 +175,10 @@ SIGNATURES = {
     "rgl_build_target": (C.c_char_p, []),
 }
 
+# Host-only planner exports added within an ABI version: an older build of the same version (RGL_HIP_LIBRARY: the A/B of two
+# builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
+ADDITIVE = {"rgl_plan_prologue_embedding"}
+
 _lib = None
 
 
@@ -189,6 +199,8 @@ def lib():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
+                if name in ADDITIVE:
+                    continue
                 raise NativeLibraryError("librgl_hip.so lacks symbol %s" % name) from e
             fn.restype = res
             fn.argtypes = args

@@ -121,6 +121,9 @@ int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float
 int level_prologue_args(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
                         float* humans_next, const float* sp_image, const void* children, size_t children_bytes, void* out,
                         size_t out_bytes);                                                                          // rgl_scene.hip
+// its form check and LDS layout alone (host only, no array): the scene region's floats, the crowds a chunk's row buffer holds
+int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds);   // rgl_scene.hip
+int fused_prologue_region_floats();      // LDS floats the prologue's scene region may take in the fused children kernel   // rgl_fused.hip
 // true: launch_value_children takes a LevelPrologue of `scene_floats` LDS floats for these P parents (the bf16x6 fused kernel of
 // 17..20-node crowds with a softmax similarity, and a workspace it can run in)
 bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, int scene_floats);           // rgl_fused.hip

@@ -490,9 +490,22 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         // LDS during the prologue: the image's first part [0, f_last) -- requested here, it lands under the scene image's loads and
         // is waited for with them -- and behind its last chunk the scene region (predictor image, embedding sets, 8 wave slots:
         // 97 KB), which the rest of the image and the wave scratches overwrite behind the barrier below
+        // The embeddings are the workgroup's (scene_body's WGE form): the rows of the owned parents' distinct crowds and their robot
+        // rows, a chunk of 16 parents at a time, into a row buffer behind the wave slots.
         static_assert(kPrologueSceneBase<LO> == kChunksA * kChunk, "the scene region starts behind the first part's chunks");
+        static_assert(kPrologueSceneBase<LO> + prologue_scene_floats(2, 19) <= LO::scratch + kFusedWaves * fused_scratch_floats(HR, NT, SOFT) + 4,
+                      "a two-layer predictor's scene region with the row buffer of a full chunk (12 crowds of 19 humans, 16 robot rows) fits the kernel's LDS");
+        ProPhases pro_phases;
+        ProPhases* const pp = &pro_phases;
+        PRO_PHASE_START(pp);
         for (int c = wave; c < kChunksA; c += kFusedWaves) image_chunk(c);
-        scene_body<2, 0, kFusedWaves, false, true, true>(pa.scene, lds + kPrologueSceneBase<LO>, p_first, 1, kFusedWaves, p_first + k_b);
+#ifdef RGL_PROLOGUE_EMB_PER_WAVE      // measurements (the timing build's "before" column): every wave embeds its own scene's rows
+        constexpr bool kWge = false;
+#else
+        constexpr bool kWge = true;
+#endif
+        scene_body<2, 0, kFusedWaves, false, true, true, kWge>(pa.scene, lds + kPrologueSceneBase<LO>, p_first, 1, kFusedWaves,
+                                                               p_first + k_b, pp);
         const ChildrenArgs& ca = pa.children;
         const long long pair0 = (long long)p_first * ca.A, pair_end = (long long)(p_first + k_b) * ca.A;
         if (ca.A >= 64 && ca.H <= 64 && !ca.robot64) {       // as the stand-alone launches: whole waves, far-human masks per parent
@@ -501,7 +514,10 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         } else {
             for (long long idx = pair0 + tid; idx < pair_end; idx += nthreads) children_thread(ca, idx);
         }
+        PRO_PHASE_MARK(pp, 3);
         __syncthreads();                 // my parents' humans_next, child robot rows and rewards are written; the scene region is free
+        PRO_PHASE_MARK(pp, 4);
+        PRO_PHASE_FLUSH(pp);
         wh2_loads();
     }
     // (the first item's state rows are requested BEFORE the image: the wait in front of the barrier covers them, and no later
@@ -1413,6 +1429,11 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
 // its three launches.
 constexpr int kPrologueMinParentsPerCu = 4;
 
+int fused_prologue_region_floats() {
+    using LO = FusedLds<32, 100, 100, true>;
+    return LO::scratch + kFusedWaves * fused_scratch_floats(20, 2, true) + 4 - kPrologueSceneBase<LO>;
+}
+
 bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, int scene_floats) {
     if (pl->contraction_dtype != RGL_CONTRACT_BF16X6 || head_variant(pl->value_head) < 0) return false;
     if (P < kPrologueMinParentsPerCu * fused_cu_count() - (fused_cu_count() - 1)) return false;     // ceil(P / CUs) < 4
@@ -1421,6 +1442,30 @@ bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_b
 }
 
 }  // namespace rgl
+
+extern "C" int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, int H, int crowds_per, int unit,
+                                           RglPrologueEmbeddingPlan* plan) {
+    if (!planner || !plan) return RGL_ERR_NULL;
+    if (P < 1 || H < 1 || crowds_per < 1 || unit < 1 || P % crowds_per) return RGL_ERR_BAD_SHAPE;
+    *plan = RglPrologueEmbeddingPlan{};
+    static const bool prologue_on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
+    int scene_floats = 0, chunk_crowds = 0;
+    if (!prologue_on || rgl::level_prologue_layout(planner, crowds_per, P, H, &scene_floats, &chunk_crowds)) return RGL_OK;
+    if (!rgl::fused_prologue_fits(planner, P, H, ~(size_t)0, scene_floats)) return RGL_OK;
+    const FusedPlan fp = plan_fused(planner->value_graph, planner->value_head, P, planner->num_actions, H, unit, kModeBx);
+    const int k = fp.a.parents_per_wg;
+    const int c1 = prologue_chunk_end(0, k, crowds_per, chunk_crowds);              // a workgroup's first chunk; a full one where k allows
+    plan->prologue = 1;
+    plan->parents_per_wg = k;
+    plan->workgroups = fp.grid;
+    plan->chunk_parents = c1;
+    plan->chunk_crowds = chunk_crowds;
+    plan->human_tiles = (((c1 - 1) / crowds_per + 1) * H + 15) / 16;
+    plan->robot_tiles = 1;
+    plan->row_floats = prologue_row_floats(H, chunk_crowds);
+    for (int c0 = 0; c0 < k; c0 = prologue_chunk_end(c0, k, crowds_per, chunk_crowds)) ++plan->chunks_per_wg;
+    return RGL_OK;
+}
 
 // The image depends on the weights (and on the contraction mode: three-piece bf16 fragments for RGL_CONTRACT_BF16X6) only: a caller
 // with fixed weights packs it once (MprlPlanner::children_image).

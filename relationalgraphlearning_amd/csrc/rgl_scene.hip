@@ -16,27 +16,15 @@ struct RowMlpArgs {
     int M, n_tiles;
 };
 
-// One wave per 16-row tile: IN -> 64 -> 32 with ReLU after both layers.
+// One wave per 16-row tile: IN -> 64 -> 32 with ReLU after both layers (row_mlp2_tile, rgl_scene_body.h).
 template <int IN>
 __device__ __forceinline__ void row_mlp2_tiles(const RowMlpArgs& a, const float* lds_set, int first, int stride, int lane) {
-    constexpr int F1 = 0, F2 = F1 + 4 * 1 * 4 * 64, B1 = F2 + 2 * 4 * 4 * 64, B2 = B1 + HID;
     const int n = lane & 15, q = lane >> 4;
     for (int tile = first; tile < a.n_tiles; tile += stride) {
         const int row = 16 * tile + n;
         const int rc = row < a.M ? row : a.M - 1;
-        const float* src = a.rows + (size_t)rc * IN;
-        f32x4 in[1];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int feat = tile_feature<IN>(0, q, r);
-            in[0][r] = feat < IN ? src[feat] : 0.f;
-        }
-        f32x4 h[4];
-        layer_mfma<IN, HID, true>(lds_set + F1, in, h, lane, lds_set + B1);
-        relu_tiles<HID>(h);
         f32x4 o[2];
-        layer_mfma<HID, XD, true>(lds_set + F2, h, o, lane, lds_set + B2);
-        relu_tiles<XD>(o);
+        row_mlp2_tile<IN>(lds_set, a.rows + (size_t)rc * IN, lane, o);
         if (row < a.M) {
             float* dst = a.out + (size_t)row * XD;
             *reinterpret_cast<f32x4*>(dst + 4 * q) = o[0];
@@ -44,8 +32,6 @@ __device__ __forceinline__ void row_mlp2_tiles(const RowMlpArgs& a, const float*
         }
     }
 }
-
-constexpr int kRowMlpSetFloats = 4 * 1 * 4 * 64 + 2 * 4 * 4 * 64 + HID + XD;
 
 // Both embedding MLPs of a level in ONE launch (they are launch-latency sized): workgroups [0, grid_a) take the robot rows
 // (INA inputs), the others the human rows (INB inputs).  (9, 5): path M's full / observable states; (6, 7): path G's rotated
@@ -107,24 +93,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void scene_graph_kernel(const SceneA
     scene_body<NT, SK, WAVES, SPLIT, EMB, BX>(a, lds, blockIdx.x, grid_scene, grid_scene * kSlots, a.P);
 }
 
-// ---- weight image of the scene kernel: one layout for the LDS region and (BX) for its packed global copy ---------------------------
-struct SceneImageLayout { int off_wa, off_ws, off_wm1, off_bm1, off_wm2, off_bm2, total, ws_stride; };
-// bx: the matrices as three-piece bf16 fragments (layer_mfma_b6: 6 bytes per weight) instead of k-major f32 rows
-inline SceneImageLayout scene_image_layout(int L, bool bx = false) {
-    SceneImageLayout o;
-    int off = 0;
-    auto take = [&](int nfl) { int r = off; off += (nfl + 3) & ~3; return r; };
-    o.ws_stride = bx ? B6Floats<XD, XD>::v : XD * WLD;
-    o.off_wa = take(bx ? B6Floats<XD, XD>::v : XD * WLD);
-    o.off_ws = take(L * o.ws_stride);
-    o.off_wm1 = take(bx ? B6Floats<XD, HID>::v : XD * W1LD);
-    o.off_bm1 = take(HID);
-    o.off_wm2 = take(bx ? B6Floats<HID, 16>::v : HID * M2LD);
-    o.off_bm2 = take(16);
-    o.total = off;
-    return o;
-}
-
+// SceneImageLayout / scene_image_layout (the weight image's layout, LDS region and packed global copy alike): rgl_scene_body.h
 struct SceneImageArgs {
     const float* wa;                      // null: identity (gaussian)
     const float* Ws[4];
@@ -278,7 +247,7 @@ static bool scene_kernel_covers(const RglGraph& g, int N) {
 
 static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per,
                            int P, int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows, bool embed_inside,
-                           const float* sp_image, int slots);
+                           const float* sp_image, int slots, int region_floats = 0);
 
 // embeddings (one launch) + one-wave-per-scene graph forward; mh != null: motion head -> humans_next; rows_out != null: value rows
 static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per, int P,
@@ -308,11 +277,12 @@ static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* r
     }
 }
 
-// SceneArgs of the scene kernel (and of the level prologue); returns the LDS floats.  `slots` > 0: scene slots of the workgroup (the
-// level prologue: one per wave), 0: the launcher's choice
+// SceneArgs of the scene kernel (and of the level prologue); returns the LDS floats.  `slots` > 0: the level prologue -- that many
+// scene slots in the workgroup (one per wave) and the row buffer of its cooperative embeddings, as large as `region_floats` LDS floats
+// leave room for; 0: the launcher's choice
 static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per,
                            int P, int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows, bool embed_inside,
-                           const float* sp_image, int slots) {
+                           const float* sp_image, int slots, int region_floats) {
     const int N = H + 1;
     const int NT = N > 64 ? 8 : (N + 15) / 16;
     sa.robot_rows = embed_inside ? robot : nullptr;
@@ -360,8 +330,15 @@ static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, c
     // one per NT waves of its 8 (with the unsplit count a 50-agent scene workgroup held 95 KB instead of 76: one per CU, and the
     // launch's reward workgroups, which reserve the same LDS, waited for a scene workgroup to retire)
     static const bool wide_slots = [] { const char* e = getenv("RGL_SCENE_WIDE_SLOTS"); return e && e[0] == '1'; }();      // measurements
+    const bool prologue = slots > 0;
     if (slots <= 0) slots = (embed_inside && (NT == 2 || NT == 4) && !wide_slots) ? 8 / NT : (NT <= 2 ? 8 : (NT <= 4 ? 4 : 1));
     sa.off_wave = take(slots * sa.wave_stride);
+    sa.off_rows = sa.chunk_crowds = 0;
+    if (prologue) {      // the row buffer, behind everything else (prologue_scene_floats counts it so): as many crowds as the region holds
+        const int room = (region_floats - off - kPrologueChunk * XD) / (H * XD);
+        sa.chunk_crowds = room < kPrologueChunkCrowds ? room : kPrologueChunkCrowds;        // < 1: the caller refuses the form
+        sa.off_rows = take(prologue_row_floats(H, sa.chunk_crowds > 0 ? sa.chunk_crowds : 1));
+    }
     return off;
 }
 
@@ -409,16 +386,30 @@ int level_prologue_args(const MprlPlanner* pl, const float* robot, const float* 
                         float* humans_next, const float* sp_image, const void* children, size_t children_bytes, void* out,
                         size_t out_bytes) {
     if (!out || out_bytes != sizeof(LevelPrologue) || !children || children_bytes != sizeof(ChildrenArgs)) return 1;
-    if (pl->linear_state_predictor || pl->contraction_dtype != RGL_CONTRACT_BF16X6 || !sp_image) return 1;
+    if (!sp_image || level_prologue_layout(pl, crowds_per, P, H, nullptr, nullptr)) return 1;
+    LevelPrologue* lp = (LevelPrologue*)out;
+    lp->scene_floats = fill_scene_args(lp->scene, pl->predictor_graph, &pl->motion_head, robot, humans, crowds_per, P, H, humans_next,
+                                       nullptr, nullptr, nullptr, true, sp_image, 8, fused_prologue_region_floats());
+    if (!lp->scene.bx) return 1;
+    lp->children = *(const ChildrenArgs*)children;
+    return 0;
+}
+
+// The form check and the LDS layout of level_prologue_args without any array (host only; the planner export rgl_plan_prologue_embedding
+// asks it too): 0 and the scene region's LDS floats / the crowds a chunk's row buffer holds, 1 = outside the form.
+int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds) {
+    if (pl->linear_state_predictor || pl->contraction_dtype != RGL_CONTRACT_BF16X6) return 1;
     const RglGraph& g = pl->predictor_graph;
     const int N = H + 1;
     if (!scene_kernel_covers(g, N) || !mlp_is(pl->motion_head, XD, HID, 5, false) || g.w_r.dims[0] != 9) return 1;
     if (scene_similarity_mode(g) != SIM_SOFTMAX || (N + 15) / 16 != 2 || crowds_per < 1 || P % crowds_per != 0) return 1;
-    LevelPrologue* lp = (LevelPrologue*)out;
-    lp->scene_floats = fill_scene_args(lp->scene, g, &pl->motion_head, robot, humans, crowds_per, P, H, humans_next, nullptr, nullptr,
-                                       nullptr, true, sp_image, 8);
-    if (!lp->scene.bx) return 1;
-    lp->children = *(const ChildrenArgs*)children;
+    SceneArgs sa;
+    static const float image_stand_in = 0.f;      // fill_scene_args only asks whether there is an image
+    const int fl = fill_scene_args(sa, g, &pl->motion_head, nullptr, nullptr, crowds_per, P, H, nullptr, nullptr, nullptr, nullptr, true,
+                                   &image_stand_in, 8, fused_prologue_region_floats());
+    if (!sa.bx || sa.chunk_crowds < 1) return 1;
+    if (scene_floats) *scene_floats = fl;
+    if (chunk_crowds) *chunk_crowds = sa.chunk_crowds;
     return 0;
 }
 

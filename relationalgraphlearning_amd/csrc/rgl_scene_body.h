@@ -19,6 +19,10 @@ struct SceneArgs {
                                        // over a packed image of three-piece fragments (RGL_CONTRACT_BF16X6); S and A H stay f32
     int ws_stride;                     // floats between the layer matrices in the LDS image
     int image_floats;                  // BX: floats of the packed image
+    int off_rows;                      // WGE (the level prologue): LDS row buffer of a chunk of parents -- [crowd][H][32] human embeddings
+                                       // of the chunk's distinct crowds (at most chunk_crowds), then at off_rows + chunk_crowds H 32 its
+                                       // [parent][32] robot rows.  (This int and chunk_crowds sit where the struct had padding: the
+                                       // scene kernels' kernel arguments keep their size and offsets.)
     const float* image;                // BX: the weight image in this kernel's LDS layout (pack_scene_image)
     const float* xh_rows;              // [n_crowds][H][32]  human embeddings
     const float* x0_rows;              // [P][32]            robot embeddings
@@ -27,6 +31,7 @@ struct SceneArgs {
     const float* Ws[RGL_MAX_GCN_LAYERS];
     int L, skip;
     int sim;                           // SIM_* row normalisation
+    int chunk_crowds;                  // WGE: most distinct crowds of a chunk (prologue_chunk_end)
     const float *wm1, *bm1, *wm2, *bm2;   // motion head, k-major [32][64], [64], [64][5], [5]
     float* humans_next;                // [P][H][5]   (state predictor)
     float* rows_out;                   // null, or [P][64]: value mode -- rows [ (A H_{L-1})[robot] | H_{L-1}[robot] ] for robot_head_kernel
@@ -46,6 +51,93 @@ struct LevelPrologue {
 };
 
 constexpr int M2LD = 20;   // LDS row stride of the [64][5 -> 16] motion output layer (4*M2LD % 32 == 16)
+
+// The level prologue embeds the rows of the parents a workgroup owns in chunks (scene_body's WGE form): at most kPrologueChunk parents
+// (ONE w_r tile of robot rows) that use at most `max_crowds` distinct crowds -- kPrologueChunkCrowds, or fewer where a predictor of
+// three or four layers leaves less LDS behind its image (fill_scene_args).  16 sibling-sharing parents (crowds_per >= 2) span at
+// most 9 crowds; at the root level (crowds_per = 1) the crowd bound cuts a chunk to 12 parents -- 16 crowds of 19 humans would be
+// 41 KB of rows, and 32 592 B lie free behind the scene region of a two-layer predictor (rgl_fused.hip proves the fit).
+constexpr int kPrologueChunk = 16, kPrologueChunkCrowds = 12;
+// parents [c0, prologue_chunk_end) form the chunk that starts at c0: its crowds c0 / crowds_per .. (end - 1) / crowds_per
+__host__ __device__ inline int prologue_chunk_end(int c0, int end, int crowds_per, int max_crowds) {
+    int c1 = c0 + kPrologueChunk;
+    const int by_crowds = (c0 / crowds_per + max_crowds) * crowds_per;      // the first parent of one crowd too many
+    if (by_crowds < c1) c1 = by_crowds;
+    return c1 < end ? c1 : end;
+}
+constexpr int prologue_row_floats(int H, int max_crowds) { return (max_crowds * H + kPrologueChunk) * XD; }
+
+// ---- weight image of the scene kernel: one layout for the LDS region and (BX) for its packed global copy ---------------------------
+struct SceneImageLayout { int off_wa, off_ws, off_wm1, off_bm1, off_wm2, off_bm2, total, ws_stride; };
+// bx: the matrices as three-piece bf16 fragments (layer_mfma_b6: 6 bytes per weight) instead of k-major f32 rows
+constexpr SceneImageLayout scene_image_layout(int L, bool bx = false) {
+    SceneImageLayout o{};
+    int off = 0;
+    auto take = [&](int nfl) { int r = off; off += (nfl + 3) & ~3; return r; };      // (a constexpr lambda: C++17)
+    o.ws_stride = bx ? B6Floats<XD, XD>::v : XD * WLD;
+    o.off_wa = take(bx ? B6Floats<XD, XD>::v : XD * WLD);
+    o.off_ws = take(L * o.ws_stride);
+    o.off_wm1 = take(bx ? B6Floats<XD, HID>::v : XD * W1LD);
+    o.off_bm1 = take(HID);
+    o.off_wm2 = take(bx ? B6Floats<HID, 16>::v : HID * M2LD);
+    o.off_bm2 = take(16);
+    o.total = off;
+    return o;
+}
+
+constexpr int kRowMlpSetFloats = 4 * 1 * 4 * 64 + 2 * 4 * 4 * 64 + HID + XD;
+// LDS floats of the level prologue's scene region for an L-layer predictor and crowds of H humans (17..20 nodes): the BX image, the
+// two embedding sets, 8 wave slots of two node tiles, the row buffer -- what fill_scene_args lays out (level_prologue_args checks it)
+constexpr int prologue_scene_floats(int L, int H) {
+    return scene_image_layout(L, true).total + 2 * kRowMlpSetFloats + 8 * 32 * XLD + prologue_row_floats(H, kPrologueChunkCrowds);
+}
+
+// Phase marks of the level prologue (-DRGL_PHASE_TIMING, tools/phase_timing.py prologue): per-wave s_memtime deltas of 0 = image and
+// fragment loads up to the first barrier, 1 = embeddings (and the fill of the wave's node rows), 2 = scene graph, 3 = reward and
+// next-state pairs, 4 = waits at the chunk barriers and the closing barrier.  A mark costs ~400 cycles.
+#ifdef RGL_PHASE_TIMING
+struct ProPhases { unsigned long long acc[5] = {0, 0, 0, 0, 0}, t0 = 0; };
+#define PRO_PHASE_START(pp) do { if (pp) (pp)->t0 = __builtin_amdgcn_s_memtime(); } while (0)
+#define PRO_PHASE_MARK(pp, idx)                                            \
+    do {                                                                   \
+        if (pp) {                                                          \
+            const unsigned long long now__ = __builtin_amdgcn_s_memtime(); \
+            (pp)->acc[idx] += now__ - (pp)->t0;                            \
+            (pp)->t0 = now__;                                              \
+        }                                                                  \
+    } while (0)
+#define PRO_PHASE_FLUSH(pp)                                                \
+    do {                                                                   \
+        if ((threadIdx.x & 63) == 0)                                       \
+            for (int i__ = 0; i__ < 5; ++i__) atomicAdd(&g_phase_cycles[10 + i__], (pp)->acc[i__]); \
+    } while (0)
+#else
+struct ProPhases {};
+#define PRO_PHASE_START(pp) do { } while (0)
+#define PRO_PHASE_MARK(pp, idx) do { } while (0)
+#define PRO_PHASE_FLUSH(pp) do { (void)(pp); } while (0)
+#endif
+
+// One 16-row tile of a two-layer embedding MLP (IN -> 64 -> 32, ReLU after both; fragment set `lds_set`: fill_frags / frag_store
+// layout) as an MFMA chain: lane (n, q) feeds the features of row `src` and gets outputs 4 q .. 4 q + 3 and 16 + 4 q .. of that row.
+// Every output column depends on its own input column and the weights only: where a row sits in which tile does not alter its bits.
+template <int IN>
+__device__ __forceinline__ void row_mlp2_tile(const float* lds_set, const float* src, int lane, f32x4 (&o)[2]) {
+    constexpr int F1 = 0, F2 = F1 + 4 * 1 * 4 * 64, B1 = F2 + 2 * 4 * 4 * 64, B2 = B1 + HID;
+    const int q = lane >> 4;
+    f32x4 in[1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int feat = tile_feature<IN>(0, q, r);
+        in[0][r] = feat < IN ? src[feat] : 0.f;
+    }
+    f32x4 h[4];
+    layer_mfma<IN, HID, true>(lds_set + F1, in, h, lane, lds_set + B1);
+    relu_tiles<HID>(h);
+    layer_mfma<HID, XD, true>(lds_set + F2, h, o, lane, lds_set + B2);
+    relu_tiles<XD>(o);
+}
+
 // N <= 32: 8 waves share one 30 KB weight image, two workgroups per CU = 4 waves per SIMD (round 1 ran 4-wave workgroups, 2 waves
 // per SIMD: a scene is one serial chain of ~290 MFMAs with a softmax in the middle, and two waves did not cover its latencies).
 // Larger crowds (3-4 column tiles: 200+ VGPRs, 9 KB of node features per wave) keep 4-wave workgroups, two per CU.
@@ -67,11 +159,19 @@ constexpr int M2LD = 20;   // LDS row stride of the [64][5 -> 16] motion output 
 // of work (and a round trip through HBM); sibling scenes repeat their crowd's human embeddings, which only matters when the
 // kernel is throughput-bound (many scenes: the launcher keeps the two-launch form there).
 // BX (RGL_CONTRACT_BF16X6, softmax similarity): the WEIGHT products as six bf16 MFMA terms over three-piece operands (layer_mfma_b6).
+// WGE (with EMB; the level prologue): the WORKGROUP embeds the rows of its scenes, a chunk of them at a time (prologue_chunk_end),
+// into the LDS row buffer at off_rows -- the human rows of the chunk's distinct crowds once per crowd, packed densely into 16-row
+// tiles across crowd boundaries, and the chunk's robot rows as one w_r tile, the tiles dealt over the waves (row_mlp2_tile: the
+// chain of row_mlp2_tiles) -- and behind a barrier every wave fills its slot from that buffer as the rows-from-global form does
+// from x0_rows / xh_rows.  Against EMB alone: sibling scenes no longer repeat their crowd's rows and no tile is mostly padding
+// (configs[2], 16 parents of 8 crowds per workgroup: 11 tile passes instead of 48).
 // Scenes first, first + slot_step, ... (see the loop below) up to `end`, on the 64 * WAVES threads of the workgroup; `lds`: the base
 // of the region the SceneArgs offsets point into (its image is loaded here, behind a workgroup barrier).
-template <int NT, int SK, int WAVES, bool SPLIT, bool EMB = false, bool BX = false>
-__device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int first, int slot_step, int pass_step, int end) {
+template <int NT, int SK, int WAVES, bool SPLIT, bool EMB = false, bool BX = false, bool WGE = false>
+__device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int first, int slot_step, int pass_step, int end,
+                                           ProPhases* pp = nullptr) {
     static_assert(!BX || SK == 0, "six-term bf16 products: softmax similarity");
+    static_assert(!WGE || (EMB && !SPLIT), "workgroup-cooperative embeddings: the embedding sets in LDS, one scene per wave");
     static_assert(!SPLIT || (SK != 3 && NT > 1 && WAVES % NT == 0), "split scenes: whole scenes per workgroup, no pair-MLP similarity");
     constexpr int kSceneThreads = WAVES * 64;
     constexpr int NCT = SPLIT ? 1 : NT;                     // column tiles of a scene this wave owns
@@ -185,14 +285,51 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
         bias_store<XD>(ebias[3], w + a.off_eh + B2, tid);
     }
     __syncthreads();
-    // scene of slot k in pass i: first + slot_step * k + i * pass_step, below `end`.  SPLIT: the loop is uniform over the workgroup
+    PRO_PHASE_MARK(pp, 0);
+    // WGE: chunks [c0, c1) of the scenes first .. end - 1 (slot_step 1: the workgroup's own parents); otherwise one pass over all
+    if (WGE && first >= end) return;                       // (workgroup-uniform; a workgroup of the prologue owns at least one parent)
+    int c0 = first;
+    do {
+    const int c1 = WGE ? prologue_chunk_end(c0, end, a.crowds_per, a.chunk_crowds) : end;
+    const int cr0 = WGE ? c0 / a.crowds_per : 0;            // the chunk's first crowd
+    const int robot_rows0 = WGE ? a.off_rows + a.chunk_crowds * H * XD : 0;      // the robot rows' place in the row buffer
+    if constexpr (WGE) {
+        if (c0 != first) {
+            __syncthreads();                               // every wave has filled its slot from the previous chunk's rows
+            PRO_PHASE_MARK(pp, 4);
+        }
+        const int hrows = ((c1 - 1) / a.crowds_per - cr0 + 1) * H, htiles = (hrows + 15) >> 4;
+        for (int t = wave; t <= htiles; t += WAVES) {      // human tiles 0 .. htiles - 1, then the robot tile
+            f32x4 o[2];
+            int dst;
+            bool valid;
+            if (t < htiles) {
+                const int row = 16 * t + n;
+                valid = row < hrows;
+                row_mlp2_tile<5>(lds + a.off_eh, a.human_rows + ((size_t)cr0 * H + (valid ? row : hrows - 1)) * 5, lane, o);
+                dst = a.off_rows + row * XD;
+            } else {
+                valid = n < c1 - c0;
+                row_mlp2_tile<9>(lds + a.off_er, a.robot_rows + (size_t)(valid ? c0 + n : c1 - 1) * 9, lane, o);
+                dst = robot_rows0 + n * XD;
+            }
+            if (valid) {
+                *reinterpret_cast<f32x4*>(&lds[dst + 4 * q]) = o[0];
+                *reinterpret_cast<f32x4*>(&lds[dst + 16 + 4 * q]) = o[1];
+            }
+        }
+        PRO_PHASE_MARK(pp, 1);
+        __syncthreads();                                   // the chunk's rows are in place
+        PRO_PHASE_MARK(pp, 4);
+    }
+    // scene of slot k in pass i: c0 + slot_step * k + i * pass_step, below c1.  SPLIT: the loop is uniform over the workgroup
     // (barriers inside); a slot past the end recomputes the last scene and writes nothing.
-    for (int it = first + (SPLIT ? 0 : slot_step * slot); it < end; it += pass_step) {
+    for (int it = c0 + (SPLIT ? 0 : slot_step * slot); it < c1; it += pass_step) {
         const int sc_raw = SPLIT ? it + slot_step * slot : it;
-        const bool active = sc_raw < end;
-        const int sc = active ? sc_raw : end - 1;
+        const bool active = sc_raw < c1;
+        const int sc = active ? sc_raw : c1 - 1;
         // node features of this scene: row 0 = robot, rows 1..H = its crowd, rows >= N zero
-        if constexpr (EMB) {
+        if constexpr (EMB && !WGE) {
             constexpr int F1 = 0, F2 = F1 + 4 * 1 * 4 * 64, B1 = F2 + 2 * 4 * 4 * 64, B2 = B1 + HID;
             const float* er = lds + a.off_er;
             const float* eh = lds + a.off_eh;
@@ -231,6 +368,17 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
                     *reinterpret_cast<f32x4*>(&Hs[node * XLD + 16 * ot + 4 * q]) = node < N ? oh[ot] : zero4();
             }
             __builtin_amdgcn_wave_barrier();
+        } else if constexpr (WGE) {
+        const int xr = robot_rows0 + (sc - c0) * XD;            // base indices into the row buffer
+        const int xh = a.off_rows + (sc / a.crowds_per - cr0) * H * XD;
+        for (int idx = lane; idx < 16 * NCT * (XD / 4); idx += 64) {
+            const int row = (idx >> 3) + 16 * ctb, c4 = (idx & 7) * 4;
+            f32x4 val = zero4();
+            if (row == 0) val = *reinterpret_cast<const f32x4*>(&lds[xr + c4]);
+            else if (row < N) val = *reinterpret_cast<const f32x4*>(&lds[xh + (row - 1) * XD + c4]);
+            *reinterpret_cast<f32x4*>(&Hs[row * XLD + c4]) = val;
+        }
+        __builtin_amdgcn_wave_barrier();
         } else {
         const float* xr = a.x0_rows + (size_t)sc * XD;
         const float* xh = a.xh_rows + (size_t)(sc / a.crowds_per) * H * XD;
@@ -242,6 +390,7 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
             *reinterpret_cast<f32x4*>(&Hs[row * XLD + c4]) = val;
         }
         }
+        PRO_PHASE_MARK(pp, 1);
         if (SPLIT) __syncthreads();
         // adjacency of the node features currently in Hs, transposed and in B-operand order: pr[ct][jt][r] = A[i][j] for
         // column i = 16 ct + n, j = 16 jt + 4 q + r.  Once per scene, or once per layer for layerwise graphs.
@@ -533,7 +682,10 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
             if (SPLIT) __syncthreads(); else __builtin_amdgcn_wave_barrier();      // the next layer / adjacency reads the rows written above
         }
         if (SPLIT) __syncthreads();      // the slot's rows are free for the next scene
+        PRO_PHASE_MARK(pp, 2);
     }
+    c0 = c1;
+    } while (WGE && c0 < end);
 }
 
 }  // namespace

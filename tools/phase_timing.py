@@ -3,6 +3,7 @@
 make -C relationalgraphlearning_amd/csrc timing; per-wave s_memtime deltas, i.e. core-clock cycles).
 
     RGL_HIP_LIBRARY=relationalgraphlearning_amd/lib/librgl_hip_timing.so python tools/phase_timing.py
+    ... python tools/phase_timing.py prologue [roots]     the level prologue of the fused children kernel (bf16x6 searches), per level
 """
 import ctypes as C
 import os
@@ -25,8 +26,48 @@ DEEP_NAMES = ["loop top (end barrier)", "phase A: embeddings", "barrier", "phase
               "barrier + E load", "(unused)", "phase C: row scalars a, b + robot row", "per-child loop"]
 
 
+PROLOGUE_NAMES = ["image + fragment loads, first barrier", "embeddings (+ fill of the wave's node rows)", "scene graph",
+                  "reward / next-state pairs", "chunk barriers + closing barrier"]
+
+
+def prologue_main(roots):
+    """The level prologue's phases (children_fused_kernel's PRO block; counters 10..14), per wave and launch, of a depth-2 width-2
+    bf16x6 search: its first level (`roots` parents, a crowd per parent) from a depth-1 search -- the same launch plan: 8 parents per
+    workgroup either way at 2048 roots -- and its second level (2 x roots parents, two siblings per crowd) as depth 2 minus depth 1.
+    A mark is an s_memtime round trip, ~400 cycles: two per scene, two per chunk, three per launch."""
+    dev = torch.device("cuda:0")
+    raw = C.CDLL(nat.LIB_PATH)
+    read = raw.rgl_debug_read_fused_phase_cycles
+    buf = (C.c_ulonglong * 16)()
+    A.contraction = "bf16x6"
+    reps, per_depth = 5, {}
+    for depth in (1, 2):
+        A.depth = depth
+        pol = bench.make_policy(A, dev)
+        ts = pol.tree_search()
+        robot, humans = bench.synth_scenes(5, roots, A.humans)
+        r, h = robot.to(dev), humans.to(dev)
+        ts.search(r, h, roots_are_joint_states=False, want_root_values=False)
+        read(buf, 1)
+        for _ in range(reps):
+            ts.search(r, h, roots_are_joint_states=False, want_root_values=False)
+        read(buf, 1)
+        per_depth[depth] = [buf[10 + i] / reps for i in range(5)]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    levels = [("level of %d parents (crowds_per 1)" % roots, per_depth[1], roots),
+              ("level of %d parents (crowds_per 2)" % (2 * roots), [b - a for a, b in zip(per_depth[1], per_depth[2])], 2 * roots)]
+    for name, cyc, parents in levels:
+        waves = 8 * min(cus, parents)              # one 8-wave workgroup per CU
+        print("%s: cycles per wave and launch" % name)
+        for nm, c in zip(PROLOGUE_NAMES, cyc):
+            print("  %-46s %9.0f   %5.1f %%" % (nm, c / waves, 100.0 * c / max(sum(cyc), 1)))
+        print("  %-46s %9.0f" % ("total", sum(cyc) / waves))
+
+
 def main():
     """usage: phase_timing.py [parents] [humans layers contraction]   (N > 32 or 3 layers -> the deep kernel's phases)"""
+    if len(sys.argv) > 1 and sys.argv[1] == "prologue":
+        return prologue_main(int(sys.argv[2]) if len(sys.argv) > 2 else 2048)
     P = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     if len(sys.argv) > 4:
         A.humans, A.layers, A.contraction = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]

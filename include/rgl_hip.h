@@ -579,6 +579,60 @@ typedef struct CrowdSceneConfig {
 
 int crowd_generate_scenes_f64(const CrowdSceneConfig* cfg, const unsigned* seeds, int B, int H, double* robot, double* humans, double* goals, double* vpref, int* status, int* draws, rgl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Replay memory filled on device (ABI 8, additive): Explorer.update_memory (crowd_nav/utils/explorer.py:113-140) and
+ * ReplayMemory.push (crowd_nav/utils/memory.py) for a whole batch of finished episodes in one call of three launches.
+ *   robot [T][B][9], humans [T][B][H][5], rewards [T][B] float32, info [T][B] int32 (CROWD_INFO_*): row t is the state the
+ *   policy saw at step t of the B lock-step episodes and the reward / info that step returned.  Episode b has L_b steps with
+ *   info != CROWD_INFO_DONE (a prefix of its column); it is stored when its last code in COLLISION..TIMEOUT is COLLISION or
+ *   REACH_GOAL and then gives the L_b - 1 tuples (state i, value i, rewards[i][b], state i + 1), numbered episode-major:
+ *   j = (tuples of the stored episodes before b) + i.  No row of a step t >= L_b is read.
+ *   value i = imitation_learning ? (float)togo[i], togo[t] = rewards[t] + step_discount * togo[t + 1] in float64 from
+ *   t = L_b - 1 down, product and sum rounded on their own : 0.
+ *   layout RGL_REPLAY_MPRL: fields = robot [capacity][9], humans [capacity][H][5], value [capacity], reward [capacity],
+ *   next robot, next humans.  RGL_REPLAY_GCN: fields = state [capacity][H][13], value, reward, next state, a state being the
+ *   H rows gcn_rotate_f32 makes of [robot | human h] under `kinematics` (the same bits).
+ *   runs: where the tuples go.  Tuple j with first <= j < first + count is stored in slot `slot + (j - first)`; a tuple no
+ *   run names is skipped.  The caller derives them from ReplayMemory.push's ring arithmetic for the N pushes of the call
+ *   and trims them so that no slot is named twice (a tuple overwritten later in the same call is skipped): an append run
+ *   after clear() with the write position ahead of the length, and the ring run from the write position, wrapping at most
+ *   once after the trim.  The ring run that follows an append run starts at slot 0 and, if it wraps, has overwritten the
+ *   append run entirely, so at most RGL_REPLAY_MAX_RUNS = 2 runs survive.  n_runs = 0: nothing is stored, nothing launched.
+ *   workspace device, >= rgl_replay_push_workspace_bytes(T, B) bytes (0 for T, B < 1 or T * B > INT_MAX).
+ * Errors, checked on the host before any launch: RGL_ERR_NULL; RGL_ERR_BAD_SHAPE for T, B, H < 1, H + 1 > RGL_MAX_NODES,
+ * capacity < 1, T * B > INT_MAX, n_runs outside [0, RGL_REPLAY_MAX_RUNS] or a run that leaves [0, capacity);
+ * RGL_ERR_BAD_MODE for an unknown layout or kinematics; RGL_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+#define RGL_REPLAY_MAX_RUNS 2
+#define RGL_REPLAY_MAX_FIELDS 6
+enum { RGL_REPLAY_MPRL = 0, RGL_REPLAY_GCN = 1 };
+
+typedef struct RglReplayRun {
+    long long first, slot, count;
+} RglReplayRun;
+
+typedef struct RglReplayPushJob {
+    const float* robot;         /* device [T][B][9]                                                           */
+    const float* humans;        /* device [T][B][H][5]                                                        */
+    const float* rewards;       /* device [T][B]                                                              */
+    const int* info;            /* device [T][B]                                                              */
+    int T, B, H;
+    int layout;                 /* RGL_REPLAY_*                                                               */
+    int kinematics;             /* RGL_HOLONOMIC | RGL_UNICYCLE (RGL_REPLAY_GCN: the rotation's)              */
+    int imitation_learning;
+    double step_discount;       /* gamma^(time_step * v_pref)                                                 */
+    long long capacity;
+    float* fields[RGL_REPLAY_MAX_FIELDS];   /* device, the memory's stacked fields (4 for RGL_REPLAY_GCN)     */
+    int n_runs, reserved;
+    RglReplayRun runs[RGL_REPLAY_MAX_RUNS];
+    void* workspace;
+    size_t workspace_bytes;
+    rgl_stream_t stream;
+} RglReplayPushJob;
+
+size_t rgl_replay_push_workspace_bytes(int T, int B);
+int rgl_replay_push_f32(const RglReplayPushJob* job);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

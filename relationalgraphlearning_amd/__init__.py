@@ -8,10 +8,10 @@ from .nets import mlp, RGL, ValueEstimator, StatePredictor, LinearStatePredictor
 from .policy import Policy, ModelPredictiveRL, GCN, register
 from .state import FullState, ObservableState, JointState, tensor_to_joint_state
 from .rollout import TreeSearch, GcnSearch, ShardedRollout, rotate, shard_bounds
-from .vector_explorer import VectorExplorer, ReplayMemory
+from .vector_explorer import VectorExplorer, ReplayMemory, DeviceReplayMemory, replay_slot_runs
 from .trainer import MPRLTrainer, VNRLTrainer, register_trainers
 
 __all__ = ["ActionXY", "ActionRot", "mlp", "RGL", "ValueEstimator", "StatePredictor", "LinearStatePredictor",
            "ValueNetwork", "invalidate_packed_weights", "Policy", "ModelPredictiveRL", "GCN", "register", "TreeSearch", "GcnSearch",
            "ShardedRollout", "rotate", "shard_bounds", "FullState", "ObservableState", "JointState",
-           "tensor_to_joint_state", "VectorExplorer", "ReplayMemory", "MPRLTrainer", "VNRLTrainer", "register_trainers"]
+           "tensor_to_joint_state", "VectorExplorer", "ReplayMemory", "DeviceReplayMemory", "replay_slot_runs", "MPRLTrainer", "VNRLTrainer", "register_trainers"]

@@ -113,6 +113,24 @@ class MprlLevelView(C.Structure):
                  "child_value_off", "value1_off", "keep_off", "backup_off", "best_slot_off", "reward_clip_off")]
 
 
+REPLAY_MAX_RUNS = 2
+REPLAY_MAX_FIELDS = 6
+REPLAY_LAYOUTS = {"mprl": 0, "gcn": 1}
+
+
+class RglReplayRun(C.Structure):
+    _fields_ = [("first", C.c_longlong), ("slot", C.c_longlong), ("count", C.c_longlong)]
+
+
+class RglReplayPushJob(C.Structure):
+    _fields_ = [("robot", C.c_void_p), ("humans", C.c_void_p), ("rewards", C.c_void_p), ("info", C.c_void_p),
+                ("T", C.c_int), ("B", C.c_int), ("H", C.c_int), ("layout", C.c_int), ("kinematics", C.c_int),
+                ("imitation_learning", C.c_int), ("step_discount", C.c_double), ("capacity", C.c_longlong),
+                ("fields", C.c_void_p * REPLAY_MAX_FIELDS), ("n_runs", C.c_int), ("reserved", C.c_int),
+                ("runs", RglReplayRun * REPLAY_MAX_RUNS), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/rgl_hip.h declares
 SIGNATURES = {
     "rgl_graph_forward_workspace_bytes": (C.c_size_t, [C.POINTER(RglGraph), C.POINTER(RglMlp), C.POINTER(RglMlp), C.c_int,
@@ -171,13 +189,15 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "crowd_generate_scenes_f64": (C.c_int, [C.POINTER(CrowdSceneConfig), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rgl_replay_push_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "rgl_replay_push_f32": (C.c_int, [C.POINTER(RglReplayPushJob)]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
 
-# Host-only planner exports added within an ABI version: an older build of the same version (RGL_HIP_LIBRARY: the A/B of two
-# builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
-ADDITIVE = {"rgl_plan_prologue_embedding"}
+# Exports added within an ABI version (host-only planners, the replay push): an older build of the same version (RGL_HIP_LIBRARY:
+# the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
+ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32"}
 
 _lib = None
 

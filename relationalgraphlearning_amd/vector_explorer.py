@@ -11,17 +11,25 @@ of the phase (the reference draws them one after another from the same counter, 
 inside the replay memory is episode-major here as well); epsilon-greedy exploration draws its random numbers per
 time step for all environments at once, so the random stream differs from k sequential episodes.
 
+`DeviceReplayMemory` keeps the experience as the stacked (capacity, ...) tensors alone and is filled by ONE library call per chunk
+of episodes (`push_episodes`, rgl_replay_push_f32): the explorer then records a chunk's states, rewards and info codes into
+preallocated (T, B, ...) tensors instead of per-step clones, and the per-tuple loop of `update_memory` does not run.  It stores
+the same bits in the same slots as `ReplayMemory` filled by `update_memory` (tests/test_replay_push.py).
+
 A policy with `acts_in_velocity = True` (orca.OrcaPolicy, the imitation-learning expert of train.py:143-154) returns (B,2)
 velocities from `predict_batch(robot, humans, done=...)`, given the simulator's float64 state; they go to the simulator as
 they are and `last_run["actions"]` holds them as (vx, vy) pairs.  Index-returning policies are unaffected.
 """
+import ctypes as C
 import logging
 
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from . import _native as nat
 from .actions import as_array
+from .nets import _require_device_tensor, _stream
 from .rollout import rotate
 
 COLLISION, SUCCESS, TIMEOUT = 2, 3, 4          # BatchedCrowdSim info codes
@@ -107,6 +115,200 @@ class ReplayMemory(Dataset):
         return list(self._mirror)
 
 
+def replay_slot_runs(position, length, capacity, n):
+    """Where `n` successive `ReplayMemory.push` calls put their items, given the memory's (position, length, capacity) before the
+    first: (runs, position', length').  A run (first, slot, count) says that pushes first .. first + count - 1 land in slots
+    slot .. slot + count - 1; the runs are TRIMMED to the pushes that are still there after the last one, so they name disjoint
+    slots and a push that a later push of the same n overwrites is in no run.
+
+    push writes at `position` while position < length and appends at index `length` otherwise, then advances position modulo
+    capacity.  So n pushes are (a) while the write position is AHEAD of the length (only after clear()): capacity - position
+    appends at length, length + 1, ..., until the position wraps to 0; then (b) a ring: slot = position, overwriting below the
+    length and appending at it, where the two indices coincide.  With position <= length there is only (b).  Of the ring the
+    last min(m, capacity) pushes survive, one run or two when they wrap; the ring after (a) starts at slot 0, so it either does
+    not wrap (one run, and the appends of (a) survive from slot max(length, m) on) or has overwritten all of (a): never more
+    than nat.REPLAY_MAX_RUNS = 2 runs."""
+    position, length, capacity, n = int(position), int(length), int(capacity), int(n)
+    if capacity < 1 or not 0 <= position < capacity or not 0 <= length <= capacity or n < 0:
+        raise ValueError("no replay memory is in the state (position %d, length %d, capacity %d)" % (position, length, capacity))
+    runs = []
+    if position > length:
+        ahead = min(n, capacity - position)               # (a): appended at length + j
+        ring, ring_slot, ring_first = n - ahead, 0, ahead
+        lo = max(length, min(ring, capacity))             # the ring that follows covers slots [0, min(ring, capacity))
+        if lo < length + ahead:
+            runs.append((lo - length, lo, length + ahead - lo))
+        new_length = max(length + ahead, min(capacity, ring))
+    else:
+        ring, ring_slot, ring_first = n, position, 0
+        new_length = max(length, min(capacity, position + n))
+    kept = min(ring, capacity)                            # (b): the last `kept` pushes of the ring
+    first = ring_first + ring - kept
+    slot = (ring_slot + ring - kept) % capacity
+    head = min(kept, capacity - slot)
+    if head:
+        runs.append((first, slot, head))
+    if kept - head:
+        runs.append((first + head, 0, kept - head))
+    return runs, (position + n) % capacity, new_length
+
+
+REPLAY_FIELD_SHAPES = {"mprl": lambda H: ((1, 9), (H, 5), (1,), (1,), (1, 9), (H, 5)),
+                       "gcn": lambda H: ((H, 13), (1,), (1,), (H, 13))}
+
+
+class DeviceReplayMemory(Dataset):
+    """`ReplayMemory` for tuples of equally shaped tensors, stored as one (capacity, *shape) tensor per tuple field and nothing
+    else: item i is the tuple of row views `field[i]`, `as_tensors()` the [:len] views, `stacked_capacity_fields()` the tensors
+    themselves -- allocated by the first push and never replaced, so a captured trainer step keeps gathering from them.  Same
+    ring as ReplayMemory (clear() keeps the write position; while it is at or ahead of the length, items are appended): item i
+    always holds what item i of a ReplayMemory holds after the same pushes and clears.  The first push fixes shapes, dtype and
+    device; anything else afterwards is a ValueError (ReplayMemory remains for ragged items).
+
+    `push(item)` copies one item into its slot on any torch device.  `push_episodes(...)` stores every transition of a batch of
+    recorded episodes with one library call (rgl_replay_push_f32: device tensors only)."""
+
+    def __init__(self, capacity):
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity must be at least 1")
+        self.position = 0
+        self._length = 0
+        self._fields = None           # per field: (capacity, *item shape)
+        self._workspace = None
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    def _allocate(self, shapes, dtype, device):
+        self._fields = [torch.empty((self.capacity,) + tuple(shape), dtype=dtype, device=device) for shape in shapes]
+
+    def _check(self, shapes, dtype, device):
+        have = [tuple(f.shape[1:]) for f in self._fields]
+        if have != [tuple(x) for x in shapes] or any(f.dtype != dtype or f.device != device for f in self._fields):
+            raise ValueError("this memory holds items of shapes %s (%s on %s), not %s (%s on %s)"
+                             % (have, self._fields[0].dtype, self._fields[0].device, [tuple(x) for x in shapes], dtype, device))
+
+    def push(self, item):
+        if not (isinstance(item, tuple) and item and all(torch.is_tensor(x) for x in item)):
+            raise ValueError("DeviceReplayMemory stores tuples of tensors (ReplayMemory takes anything)")
+        shapes, dtype, device = [tuple(x.shape) for x in item], item[0].dtype, item[0].device
+        if any(x.dtype != dtype or x.device != device for x in item):
+            raise ValueError("the fields of an item must share dtype and device")
+        if self._fields is None:
+            self._allocate(shapes, dtype, device)
+        else:
+            self._check(shapes, dtype, device)
+        if self.position < self._length:
+            slot = self.position
+        else:
+            slot = self._length                    # (after clear() the write position is ahead of the length: upstream's ring)
+            self._length += 1
+        for field, x in zip(self._fields, item):
+            field[slot].copy_(x)
+        self.position = (self.position + 1) % self.capacity
+
+    def is_full(self):
+        return self._length == self.capacity
+
+    def clear(self):
+        self._length = 0              # the write position is kept, as upstream does; so are the tensors
+
+    def __getitem__(self, index):
+        i = int(index)
+        if i < 0:
+            i += self._length
+        if not 0 <= i < self._length:
+            raise IndexError("replay memory index out of range")
+        return tuple(field[i] for field in self._fields)
+
+    def __len__(self):
+        return self._length
+
+    def as_tensors(self):
+        """[field 0 of every item (n, ...), field 1 ..., ...] in item order: views, nothing is copied.  None while empty."""
+        if self._length == 0:
+            return None
+        return [field[:self._length] for field in self._fields]
+
+    def stacked_capacity_fields(self):
+        """The stored tensors at their full (capacity, ...) extent -- rows >= len(self) are unwritten.  None while empty."""
+        if self._length == 0:
+            return None
+        return list(self._fields)
+
+    # -- a batch of episodes ---------------------------------------------------------------------------------------
+    def push_episodes(self, robot, humans, rewards, info, layout, kinematics, step_discount, imitation_learning,
+                      lengths=None, outcomes=None):
+        """Every transition of B recorded lock-step episodes, as `VectorExplorer.update_memory` pushes them episode by episode.
+        robot (T,B,9), humans (T,B,H,5), rewards (T,B) float32 and info (T,B) int32 device tensors: row t is the state the policy
+        saw at step t and the reward / BatchedCrowdSim info code that step returned (5 = finished earlier).  layout "mprl":
+        items (robot (1,9), humans (H,5), value (1,), reward (1,), next robot, next humans); "gcn": (state (H,13), value, reward,
+        next state) with the rows `rotate` makes under `kinematics`.  Episodes that ended in a collision or at the goal are
+        stored, L - 1 tuples each, episode-major; value = the float64 discounted return-to-go rounded to float32 (imitation
+        learning) or 0.
+
+        lengths / outcomes: per episode the number of steps with info != 5 and the last end code, as host arrays -- the explorer
+        has them for its statistics; they only move `position` and `len` and size the slot map.  Without them they are read back
+        from `info`, which waits for the device.  Otherwise the call synchronises nothing: three launches on the current stream.
+        Returns the number of tuples pushed."""
+        if layout not in nat.REPLAY_LAYOUTS:
+            raise ValueError("unknown layout %r" % (layout,))
+        if kinematics not in nat.KINEMATICS:
+            raise ValueError("unknown kinematics %r" % (kinematics,))
+        robot = _require_device_tensor(robot, "recorded robot states")
+        humans = _require_device_tensor(humans, "recorded human states")
+        rewards = _require_device_tensor(rewards, "recorded rewards")
+        if not (torch.is_tensor(info) and info.dtype == torch.int32 and info.device == robot.device):
+            raise TypeError("info must be an int32 tensor on the states' device")
+        info = info.contiguous()
+        if robot.dim() != 3 or humans.dim() != 4:
+            raise ValueError("robot must be (T, B, 9) and humans (T, B, H, 5)")
+        T, B, H = int(humans.shape[0]), int(humans.shape[1]), int(humans.shape[2])
+        if (tuple(robot.shape) != (T, B, 9) or tuple(humans.shape) != (T, B, H, 5) or tuple(rewards.shape) != (T, B)
+                or tuple(info.shape) != (T, B) or humans.device != robot.device or rewards.device != robot.device):
+            raise ValueError("robot (T,B,9), humans (T,B,H,5), rewards (T,B) and info (T,B) must agree and share a device")
+        if lengths is None or outcomes is None:
+            host = info.cpu().numpy()
+            lengths = (host != 5).sum(0)
+            outcomes = np.zeros(B, np.int64)
+            for t in range(T):
+                ended = (host[t] >= COLLISION) & (host[t] <= TIMEOUT)
+                outcomes = np.where(ended, host[t], outcomes)
+        lengths, outcomes = np.asarray(lengths).astype(np.int64), np.asarray(outcomes).astype(np.int64)
+        if lengths.shape != (B,) or outcomes.shape != (B,):
+            raise ValueError("lengths and outcomes must have one entry per episode")
+        stored = ((outcomes == COLLISION) | (outcomes == SUCCESS)) & (lengths > 1)
+        n = int((lengths[stored] - 1).sum())
+        shapes = REPLAY_FIELD_SHAPES[layout](H)
+        if self._fields is None:
+            self._allocate(shapes, torch.float32, robot.device)
+        else:
+            self._check(shapes, torch.float32, robot.device)
+        runs, position, length = replay_slot_runs(self.position, self._length, self.capacity, n)
+        lib = nat.lib()
+        nbytes = int(lib.rgl_replay_push_workspace_bytes(T, B))
+        if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != robot.device:
+            self._workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=robot.device)
+        if nat.poison_workspaces():
+            self._workspace.fill_(255)               # tests: NaN bit patterns wherever a kernel reads what this call did not write
+        job = nat.RglReplayPushJob()
+        job.robot, job.humans, job.rewards, job.info = robot.data_ptr(), humans.data_ptr(), rewards.data_ptr(), info.data_ptr()
+        job.T, job.B, job.H = T, B, H
+        job.layout, job.kinematics = nat.REPLAY_LAYOUTS[layout], nat.KINEMATICS[kinematics]
+        job.imitation_learning, job.step_discount, job.capacity = int(bool(imitation_learning)), float(step_discount), self.capacity
+        for f, field in enumerate(self._fields):
+            job.fields[f] = field.data_ptr()
+        job.n_runs = len(runs)
+        for r, (first, slot, count) in enumerate(runs):
+            job.runs[r].first, job.runs[r].slot, job.runs[r].count = first, slot, count
+        job.workspace, job.workspace_bytes = self._workspace.data_ptr(), self._workspace.numel()
+        with torch.cuda.device(robot.device):
+            job.stream = _stream()
+            rc = lib.rgl_replay_push_f32(C.byref(job))
+        nat.check(rc, "rgl_replay_push_f32")
+        self.position, self._length = position, length
+        return n
+
+
 def discounted_statistics(rewards, lengths, step_discount):
     """rewards (T,B) (zeros after an episode's end), lengths (B,) -> per episode (cumulative discounted reward,
     mean over its steps of the discounted return-to-go), as explorer.py:78-85 computes them.
@@ -177,13 +379,27 @@ class VectorExplorer(object):
         max_steps = int(round(sim.cfg.time_limit / sim.cfg.time_step)) + 2
         outcome = torch.zeros(B, dtype=torch.int32, device=sim.device)
         rewards, infos, dmins, states, actions = [], [], [], [], []
+        # a memory that takes whole chunks (DeviceReplayMemory.push_episodes): the states, rewards and info codes are recorded
+        # into (max_steps, B, ...) tensors -- the simulator writes rewards / info / dmin in place -- instead of per-step clones
+        record = None
+        if keep_states and hasattr(self.memory, "push_episodes"):
+            record = (torch.empty((max_steps,) + tuple(robot32.shape), dtype=torch.float32, device=sim.device),
+                      torch.empty((max_steps,) + tuple(humans32.shape), dtype=torch.float32, device=sim.device),
+                      torch.empty(max_steps, B, dtype=torch.float32, device=sim.device),
+                      torch.empty(max_steps, B, dtype=torch.int32, device=sim.device),
+                      torch.empty(max_steps, B, dtype=torch.float64, device=sim.device))
         for _ in range(max_steps):
             if not bool((sim.done == 0).any()):
                 break
-            if keep_states:
+            t = len(infos)
+            if record is not None:
+                record[0][t].copy_(robot32)
+                record[1][t].copy_(humans32)
+            elif keep_states:
                 states.append((robot32.clone(), humans32.clone()))
             idx = self._act(robot32, humans32, phase, None if velocity else table.shape[0])
-            (robot32, humans32), reward, _, info = sim.step(idx if velocity else table[idx])
+            (robot32, humans32), reward, _, info = sim.step(idx if velocity else table[idx],
+                                                            out=None if record is None else tuple(r[t] for r in record[2:]))
             if velocity:
                 idx = idx.clone()                        # the policy may hand out one buffer per call
             actions.append(idx)
@@ -198,7 +414,8 @@ class VectorExplorer(object):
         reward_t = np.where(live, torch.stack(rewards).cpu().numpy().astype(np.float64), 0.0)
         return {"outcome": outcome.cpu().numpy(), "time": sim.time.cpu().numpy().copy(), "lengths": lengths,
                 "rewards": reward_t, "info": info_t, "dmin": torch.stack(dmins).cpu().numpy(),
-                "states": states, "actions": actions}
+                "states": states, "actions": actions,
+                "recorded": None if record is None else tuple(r[:len(infos)] for r in record[:4])}
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None, epoch=None,
                        print_failure=False):
@@ -244,7 +461,9 @@ class VectorExplorer(object):
             danger = run["info"] == 1
             discomfort += int(danger.sum())
             min_dist.extend(run["dmin"][danger].tolist())
-            if update_memory:
+            if update_memory and run["recorded"] is not None:
+                self._push_chunk(run, imitation_learning)
+            elif update_memory:
                 for b in range(len(chunk)):
                     if int(run["outcome"][b]) in (SUCCESS, COLLISION):       # positive or negative experience only
                         T = int(run["lengths"][b])
@@ -282,6 +501,17 @@ class VectorExplorer(object):
         robot, humans = state
         joint = torch.cat([robot.expand(humans.shape[0], 9), humans], dim=1).contiguous()
         return rotate(joint, self.target_policy.kinematics)
+
+    def _push_chunk(self, run, imitation_learning):
+        """What the update_memory loop of run_k_episodes stores for one chunk, as one `memory.push_episodes` call."""
+        if self.memory is None or self.gamma is None:
+            raise ValueError('Memory or gamma value is not set!')
+        step_discount = pow(self.gamma, self.sim.cfg.time_step * self.sim.cfg.robot_v_pref)
+        mprl = self.target_policy.name == 'ModelPredictiveRL'
+        robot, humans, rewards, info = run["recorded"]
+        self.memory.push_episodes(robot, humans, rewards, info, "mprl" if mprl else "gcn",
+                                  getattr(self.target_policy, "kinematics", None) or "holonomic", step_discount,
+                                  imitation_learning, lengths=run["lengths"], outcomes=run["outcome"])
 
     def update_memory(self, states, actions, rewards, imitation_learning=False):
         """One finished episode: states[i] = (robot (1,9), humans (H,5)) fp32 device tensors (`policy.last_state`)."""

@@ -633,6 +633,49 @@ typedef struct RglReplayPushJob {
 size_t rgl_replay_push_workspace_bytes(int T, int B);
 int rgl_replay_push_f32(const RglReplayPushJob* job);
 
+/* ---------------------------------------------------------------------------------------------
+ * Epsilon-greedy exploration on device with each case's own numpy stream (ABI 8, additive).  Upstream seeds numpy per case in
+ * CrowdSim.reset (crowd_sim/envs/crowd_sim.py:185-191), generate_human consumes doubles, and every predict of the episode
+ * continues that stream: `probability = np.random.random()` and, when `probability < epsilon`,
+ * `np.random.choice(len(action_space))` (crowd_nav/policy/model_predictive_rl.py:208-210, multi_human_rl.py:34-36).
+ *   The stream rule.  Case b has seed s and its scene consumed d doubles (crowd_generate_scenes_f64's draws[b]), so the first
+ *   2 d 32-bit outputs of init_genrand(s) are spent.  Each decision of a LIVE environment (done[b] == 0):
+ *     u = random_sample() = ((a >> 5) * 2^26 + (b >> 6)) / 2^53 of two outputs a, b;  explored = u < epsilon (strict, float64);
+ *     explored, n = n_actions: n = 1 gives index 0 and consumes nothing; otherwise mask = the smallest 2^k - 1 >= n - 1 and one
+ *     output at a time, v = output & mask, until v <= n - 1: index = v (numpy's legacy masked rejection on 32-bit draws);
+ *     not explored: the policy's greedy index is kept.
+ *   A finished environment (done[b] != 0) draws nothing and its state is untouched: upstream no longer calls predict for it.
+ *   Upstream's reach_destination early return (no draw) is not implemented: it cannot occur for a live environment of a seeded
+ *   scene (step ends an episode whose next position is within the robot's radius of the goal; start and goal are 2R apart).
+ *   state device [B][CROWD_EXPLORE_STATE_WORDS]: the 624 MT19937 words, then the position of the next word (0..624; 624 = twist
+ *   first).
+ * crowd_explore_seed_u32: state[b] = init_genrand(seeds[b]) advanced past 2 * max(draws[b], 0) outputs: ceil(2 d / 624) twists and
+ *   position 2 d - 624 (twists - 1); d = 0: the seeded words and position 624.
+ * crowd_explore_select_f64: one decision for every environment.  chosen[b] = the index taken, action[b][0..1] = table[chosen[b]]
+ *   (the float64 bits copied), explored[b] = 0 | 1 (nullable), state[b] advanced in place.  A finished environment gets
+ *   chosen = greedy, its action row and explored = 0.  A chosen index outside [0, n_actions) -- only a greedy one can be -- gives
+ *   a NaN action row, like rgl_gather_rows_f32, and chosen = greedy; a live environment still draws.
+ * Both calls are asynchronous, allocate nothing and launch kernels only (safe under stream capture).
+ * Errors, decided on the host before any launch: RGL_ERR_NULL for a missing required pointer; RGL_ERR_BAD_SHAPE for B < 1,
+ * n_actions < 1 or n_actions > RGL_MAX_ACTIONS; RGL_ERR_BAD_MODE for an epsilon that is NaN or outside [0, 1].
+ * ------------------------------------------------------------------------------------------- */
+#define CROWD_EXPLORE_STATE_WORDS 625
+int crowd_explore_seed_u32(const unsigned* seeds, const int* draws, int B, unsigned* state, rgl_stream_t stream);
+
+typedef struct CrowdExploreJob {
+    const int* greedy;      /* device [B]: the policy's choice                         */
+    const int* done;        /* device [B]: crowd_step_f64's flags, != 0 = finished     */
+    const double* table;    /* device [n_actions][2]                                   */
+    unsigned* state;        /* device [B][625], advanced in place                      */
+    int* chosen;            /* device [B]                                              */
+    double* action;         /* device [B][2] = table[chosen]                           */
+    int* explored;          /* device [B] 0 | 1; nullable                              */
+    double epsilon;
+    int B, n_actions;
+    rgl_stream_t stream;
+} CrowdExploreJob;
+int crowd_explore_select_f64(const CrowdExploreJob* job);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

@@ -131,6 +131,15 @@ class RglReplayPushJob(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+EXPLORE_STATE_WORDS = 625
+
+
+class CrowdExploreJob(C.Structure):
+    _fields_ = [("greedy", C.c_void_p), ("done", C.c_void_p), ("table", C.c_void_p), ("state", C.c_void_p),
+                ("chosen", C.c_void_p), ("action", C.c_void_p), ("explored", C.c_void_p), ("epsilon", C.c_double),
+                ("B", C.c_int), ("n_actions", C.c_int), ("stream", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/rgl_hip.h declares
 SIGNATURES = {
     "rgl_graph_forward_workspace_bytes": (C.c_size_t, [C.POINTER(RglGraph), C.POINTER(RglMlp), C.POINTER(RglMlp), C.c_int,
@@ -191,13 +200,16 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rgl_replay_push_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "rgl_replay_push_f32": (C.c_int, [C.POINTER(RglReplayPushJob)]),
+    "crowd_explore_seed_u32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "crowd_explore_select_f64": (C.c_int, [C.POINTER(CrowdExploreJob)]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
 
-# Exports added within an ABI version (host-only planners, the replay push): an older build of the same version (RGL_HIP_LIBRARY:
+# Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
-ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32"}
+ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
+            "crowd_explore_seed_u32", "crowd_explore_select_f64"}
 
 _lib = None
 

@@ -18,58 +18,14 @@
 // Bounded: a human that has not been placed after cfg.max_attempts attempts ends its case with status 1 (upstream's loop has no
 // exit; with randomize_attributes on a crowded circle it may never find room).
 #include "rgl_common.h"
+#include "rgl_mt19937.h"
 
 namespace {
-
-constexpr int kMtN = 624, kMtM = 397;
-constexpr int kWave = 64;
 
 struct SceneLds {
     unsigned mt[kMtN];
     double px[RGL_MAX_NODES], py[RGL_MAX_NODES], gx[RGL_MAX_NODES], gy[RGL_MAX_NODES], rad[RGL_MAX_NODES];
 };
-
-__device__ __forceinline__ unsigned temper(unsigned y) {
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9D2C5680u;
-    y ^= (y << 15) & 0xEFC60000u;
-    y ^= y >> 18;
-    return y;
-}
-
-// random_sample() of two successive tempered outputs: every operation exact in float64
-__device__ __forceinline__ double to_double(unsigned a, unsigned b) {
-#pragma clang fp contract(off)
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
-}
-
-// init_genrand: mt[i] = 1812433253 * (mt[i-1] ^ (mt[i-1] >> 30)) + i.  Sequential; every lane runs it, lane i % 64 stores word i.
-__device__ void mt_seed(SceneLds& s, unsigned seed, int lane) {
-    unsigned x = seed;
-    if (lane == 0) s.mt[0] = x;
-    for (int i = 1; i < kMtN; ++i) {
-        x = 1812433253u * (x ^ (x >> 30)) + (unsigned)i;
-        if ((i & (kWave - 1)) == lane) s.mt[i] = x;
-    }
-    __syncthreads();
-}
-
-// The twist, 64 words per pass in ascending order.  Word k needs the OLD words k, k + 1 and (k < 227) k + 397, and (k >= 227) the
-// NEW word k - 227, written at least three passes earlier; word 623 needs the new words 0 and 396.  Within a pass every lane's
-// store depends on its loads, and the one word a pass reads from the next pass's range (k + 1 of its last lane) is still old.
-__device__ void mt_twist(SceneLds& s, int lane) {
-    for (int base = 0; base < kMtN; base += kWave) {
-        const int k = base + lane;
-        unsigned v = 0;
-        if (k < kMtN) {
-            const unsigned y = (s.mt[k] & 0x80000000u) | (s.mt[k + 1 < kMtN ? k + 1 : 0] & 0x7FFFFFFFu);
-            v = s.mt[k + kMtM < kMtN ? k + kMtM : k + kMtM - kMtN] ^ (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
-        }
-        __syncthreads();
-        if (k < kMtN) s.mt[k] = v;
-        __syncthreads();
-    }
-}
 
 struct Stream {
     int pos;        // next word of mt[] (624: twist first); the same in every lane
@@ -81,7 +37,7 @@ __device__ double draw(SceneLds& s, Stream& st, int lane) {
     unsigned w[2];
     for (int t = 0; t < 2; ++t) {
         if (st.pos == kMtN) {
-            mt_twist(s, lane);
+            mt_twist(s.mt, lane);
             st.pos = 0;
         }
         w[t] = temper(s.mt[st.pos++]);
@@ -113,7 +69,7 @@ __device__ bool place(const CrowdSceneConfig& cfg, SceneLds& s, Stream& st, Huma
     for (;;) {
         if (h.attempts >= cfg.max_attempts) return false;
         if (st.pos == kMtN) {
-            mt_twist(s, lane);
+            mt_twist(s.mt, lane);
             st.pos = 0;
         }
         const int left = cfg.max_attempts - h.attempts;
@@ -173,7 +129,7 @@ __global__ __launch_bounds__(kWave) void crowd_generate_scenes_kernel(const Crow
     __shared__ SceneLds s;
     const int lane = threadIdx.x;
     const long long b = blockIdx.x;
-    mt_seed(s, seeds[b], lane);
+    mt_seed(s.mt, seeds[b], lane);
     Stream st{kMtN, 0};
     const double R = cfg.circle_radius;
     if (lane == 0) {

@@ -70,6 +70,13 @@ class SimConfig(object):
 def generate_scene(cfg, phase, case):
     """Initial state of seeded case `case` of `phase`: (robot (9,), humans (H,5), human goals (H,2), human v_pref (H,)),
     float64.  Consumes the legacy numpy stream exactly like CrowdSim.reset/generate_human."""
+    return generate_scene_with_draws(cfg, phase, case)[:4]
+
+
+def generate_scene_with_draws(cfg, phase, case):
+    """generate_scene plus, as a fifth value, the number of doubles (random_sample / uniform calls) it took from the case's
+    stream: where the episode's exploration draws continue (vector_explorer, exploration="device")."""
+    draws = 0
     rs = np.random.RandomState(BASE_SEED[phase] + case)
     R = cfg.circle_radius
     robot = np.array([0.0, -R, 0.0, 0.0, cfg.robot_radius, 0.0, R, cfg.robot_v_pref, np.pi / 2])
@@ -89,8 +96,10 @@ def generate_scene(cfg, phase, case):
         if cfg.randomize_attributes:
             v_pref = rs.uniform(0.5, 1.5)
             radius = rs.uniform(0.3, 0.5)
+            draws += 2
         if cfg.scenario == "circle_crossing":
             while True:
+                draws += 3
                 angle = rs.random_sample() * np.pi * 2
                 px_noise = (rs.random_sample() - 0.5) * v_pref
                 py_noise = (rs.random_sample() - 0.5) * v_pref
@@ -101,12 +110,15 @@ def generate_scene(cfg, phase, case):
             gx, gy = -px, -py
         elif cfg.scenario == "square_crossing":
             sign = -1 if rs.random_sample() > 0.5 else 1
+            draws += 1
             while True:
+                draws += 2
                 px = rs.random_sample() * cfg.square_width * 0.5 * sign
                 py = (rs.random_sample() - 0.5) * cfg.square_width
                 if clear_of(px, py, ag[:n, 0], ag[:n, 1], radius):
                     break
             while True:
+                draws += 2
                 gx = rs.random_sample() * cfg.square_width * 0.5 * -sign
                 gy = (rs.random_sample() - 0.5) * cfg.square_width
                 if clear_of(gx, gy, ag[:n, 2], ag[:n, 3], radius):
@@ -118,7 +130,7 @@ def generate_scene(cfg, phase, case):
         humans.append([px, py, 0.0, 0.0, radius])
         goals.append([gx, gy])
         vprefs.append(v_pref)
-    return robot, np.array(humans), np.array(goals), np.array(vprefs, dtype=np.float64)
+    return robot, np.array(humans), np.array(goals), np.array(vprefs, dtype=np.float64), draws
 
 
 class UnplacedSceneError(RuntimeError):
@@ -141,14 +153,21 @@ def _scene_config(cfg):
     return c
 
 
+def _seed_tensor(phase, cases, device):
+    """The cases' numpy seeds BASE_SEED[phase] + case, as the int32 bit patterns of uint32 values on `device`."""
+    seeds = np.asarray([int(k) for k in cases], np.int64) + BASE_SEED[phase]
+    if len(seeds) == 0 or seeds.min() < 0 or seeds.max() > 0xFFFFFFFF:
+        raise ValueError("cases must be a non-empty list whose seeds (%d + case) fit 32 bits" % BASE_SEED[phase])
+    return torch.from_numpy(seeds.astype(np.uint32).view(np.int32)).to(device)
+
+
 def _launch_scene_generator(cfg, phase, cases, device):
     """crowd_generate_scenes_f64 for `cases`: (robot, humans, goals, v_pref, status, draws) on `device`, flagged cases and all."""
     device = torch.device(device)
-    seeds = np.asarray(cases, np.int64) + BASE_SEED[phase]
-    if len(cases) == 0 or seeds.min() < 0 or seeds.max() > 0xFFFFFFFF:
+    if len(cases) == 0:
         raise ValueError("cases must be a non-empty list whose seeds (%d + case) fit 32 bits" % BASE_SEED[phase])
     B, H = len(cases), int(cfg.human_num)
-    seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32)).to(device)
+    seeds_d = _seed_tensor(phase, cases, device)
     robot = torch.empty(B, 9, dtype=torch.float64, device=device)
     humans = torch.empty(B, H, 5, dtype=torch.float64, device=device)
     goals = torch.empty(B, H, 2, dtype=torch.float64, device=device)
@@ -170,7 +189,7 @@ def generate_scenes_device(cfg, phase, cases, device, on_unplaced="raise"):
     decisions as the host generator; circle_crossing positions differ from it by the device's sin / cos (a few ulp).
     A case in which some human is not placed within cfg.scene_max_attempts attempts has status 1: on_unplaced="raise" raises
     UnplacedSceneError naming those cases, "host" fills them in with generate_scene (which has no cap: like upstream, it does
-    not return when there is no room for the human)."""
+    not return when there is no room for the human) and writes the host's draw count into draws[b]."""
     if on_unplaced not in ("raise", "host"):
         raise ValueError("on_unplaced must be 'raise' or 'host', not %r" % (on_unplaced,))
     cases = [int(k) for k in cases]
@@ -186,8 +205,9 @@ def generate_scenes_device(cfg, phase, cases, device, on_unplaced="raise"):
                                      "scene_on_unplaced) to hand them to the host generator, which has no cap and may never "
                                      "return.", [(phase, cases[b]) for b in unplaced])
         for b in unplaced:
-            r, h, g, v = generate_scene(cfg, phase, cases[b])
+            r, h, g, v, d = generate_scene_with_draws(cfg, phase, cases[b])
             robot[b], humans[b], goals[b], vpref[b] = (torch.as_tensor(a, dtype=torch.float64).to(robot.device) for a in (r, h, g, v))
+            draws[b] = d
     return robot, humans, goals, vpref, status, draws
 
 
@@ -212,16 +232,21 @@ class BatchedCrowdSim(object):
         self.kinematics = kinematics
         self.B = 0
         self._scene_cache = {}
+        self.scene_seeds = self.scene_draws = None
 
     # -- state ---------------------------------------------------------------------------------------------------
     def reset(self, phase, cases, generator=None):
         """Load seeded cases (one environment each).  Returns the fp32 observation (robot (B,9), humans (B,H,5)).
         generator: "host" (generate_scene per case, memoised), "device" (generate_scenes_device: one launch, nothing memoised,
-        no copy through the host; an unplaced case raises or goes to the host generator, cfg.scene_on_unplaced), None: cfg.scene_generator."""
+        no copy through the host; an unplaced case raises or goes to the host generator, cfg.scene_on_unplaced), None: cfg.scene_generator.
+        After a seeded reset `scene_seeds` and `scene_draws` hold, per environment, the case's numpy seed (the uint32 bits) and
+        the number of doubles its scene took from that stream, as int32 device tensors; load() clears them."""
         generator = self.cfg.scene_generator if generator is None else generator
         if generator == "device":
-            robot, humans, goals, vpref, _, _ = generate_scenes_device(self.cfg, phase, cases, self.device, self.cfg.scene_on_unplaced)
-            return self._load_tensors(robot, humans, goals, vpref)
+            robot, humans, goals, vpref, _, draws = generate_scenes_device(self.cfg, phase, cases, self.device, self.cfg.scene_on_unplaced)
+            obs = self._load_tensors(robot, humans, goals, vpref)
+            self.scene_seeds, self.scene_draws = _seed_tensor(phase, cases, self.device), draws
+            return obs
         if generator != "host":
             raise ValueError("unknown scene generator %r" % (generator,))
         scenes = []
@@ -229,10 +254,13 @@ class BatchedCrowdSim(object):
             key = (phase, int(k), self.cfg.scenario, self.cfg.human_num, self.cfg.randomize_attributes, self.cfg.circle_radius,
                    self.cfg.square_width)
             if key not in self._scene_cache:
-                self._scene_cache[key] = generate_scene(self.cfg, phase, int(k))
+                self._scene_cache[key] = generate_scene_with_draws(self.cfg, phase, int(k))
             scenes.append(self._scene_cache[key])
-        return self.load(np.stack([s[0] for s in scenes]), np.stack([s[1] for s in scenes]),
-                         np.stack([s[2] for s in scenes]), np.stack([s[3] for s in scenes]))
+        obs = self.load(np.stack([s[0] for s in scenes]), np.stack([s[1] for s in scenes]),
+                        np.stack([s[2] for s in scenes]), np.stack([s[3] for s in scenes]))
+        self.scene_seeds = _seed_tensor(phase, cases, self.device)
+        self.scene_draws = torch.tensor([s[4] for s in scenes], dtype=torch.int32).to(self.device)
+        return obs
 
     def load(self, robot, humans, human_goals=None, human_vpref=None):
         dev = self.device
@@ -256,6 +284,7 @@ class BatchedCrowdSim(object):
         Optional caller-owned buffers, which the simulator then keeps as well: time (B,) float64 and done (B,) int32 (both
         zeroed here), obs = (robot (B, 9), humans (B, H, 5)) float32 for the observation."""
         self.robot, self.humans, self.human_goals, self.human_vpref = robot, humans, human_goals, human_vpref
+        self.scene_seeds = self.scene_draws = None           # reset() sets them afterwards; loaded states have no stream to continue
         self.B, self.H = self.robot.shape[0], self.humans.shape[1]
         dev = self.device
         self.time = self._owned(time, (self.B,), torch.float64, "time").zero_()

@@ -19,6 +19,15 @@ the same bits in the same slots as `ReplayMemory` filled by `update_memory` (tes
 A policy with `acts_in_velocity = True` (orca.OrcaPolicy, the imitation-learning expert of train.py:143-154) returns (B,2)
 velocities from `predict_batch(robot, humans, done=...)`, given the simulator's float64 state; they go to the simulator as
 they are and `last_run["actions"]` holds them as (vx, vy) pairs.  Index-returning policies are unaffected.
+
+`exploration="device"` (default "host", the paragraph above) makes a training episode explore with upstream's own stream: numpy
+is seeded per case in CrowdSim.reset (crowd_sim.py:185-191), scene generation consumes doubles, and every `predict` continues
+that stream with `np.random.random()` and, when it explores, `np.random.choice(n)` (model_predictive_rl.py:208-210,
+multi_human_rl.py:34-36).  Every environment then carries its case's MT19937 state on the device, seeded after `reset` from
+`sim.scene_seeds` / `sim.scene_draws` (crowd_explore_seed_u32), and one kernel per step makes the draw for every live
+environment, picks the action and writes the action row the simulator steps with (crowd_explore_select_f64, csrc/rgl_explore.hip):
+an exploring episode of training case k is a function of k, epsilon and the weights, as upstream's is with ORCA or linear humans.
+"host" exploration is NOT upstream's stream and not reproducible from the cases.
 """
 import ctypes as C
 import logging
@@ -331,7 +340,11 @@ def _mean(values):
 
 class VectorExplorer(object):
     def __init__(self, sim, policy, device=None, writer=None, memory=None, gamma=None, target_policy=None,
-                 case_size=None, max_batch=4096):
+                 case_size=None, max_batch=4096, exploration="host"):
+        if exploration not in ("host", "device"):
+            raise ValueError("exploration must be 'host' or 'device', not %r" % (exploration,))
+        self.exploration = exploration
+        self._explore = None                    # exploration="device", train phase: the chunk's stream states and outputs
         self.sim = sim
         self.policy = policy                    # the acting policy (needs predict_batch)
         self.device = device or sim.device
@@ -355,6 +368,8 @@ class VectorExplorer(object):
         if getattr(self.policy, "acts_in_velocity", False):
             return self.policy.predict_batch(self.sim.robot, self.sim.humans, roots_are_joint_states=True, done=self.sim.done)
         idx, _ = self.policy.predict_batch(robot32, humans32, roots_are_joint_states=True)
+        if self._explore is not None:
+            return self._select_on_device(idx, n_actions)
         idx = idx.long()
         eps = getattr(self.policy, "epsilon", None)
         if phase == "train" and eps:
@@ -364,10 +379,44 @@ class VectorExplorer(object):
             idx = torch.where(explore, rand_idx, idx)
         return idx
 
+    def _seed_exploration(self, table):
+        """The chunk's stream states, continued from where scene generation left each case's stream, and the select kernel's
+        outputs (one buffer per chunk; `explored` is recorded per step)."""
+        sim = self.sim
+        if sim.scene_seeds is None or sim.scene_draws is None:
+            raise ValueError("exploration='device' needs a simulator reset from seeded cases: loaded states carry no stream")
+        B, dev = sim.B, sim.device
+        state = torch.empty(B, nat.EXPLORE_STATE_WORDS, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = nat.lib().crowd_explore_seed_u32(sim.scene_seeds.data_ptr(), sim.scene_draws.data_ptr(), B, state.data_ptr(), _stream())
+        nat.check(rc, "crowd_explore_seed_u32")
+        eps = getattr(self.policy, "epsilon", None)
+        return {"state": state, "table": table, "epsilon": 0.0 if eps is None else float(eps), "explored": [],
+                "action": torch.empty(B, 2, dtype=torch.float64, device=dev)}
+
+    def _select_on_device(self, greedy, n_actions):
+        """One decision of every live environment on its own stream (crowd_explore_select_f64): the chosen indices; the action
+        rows are left in self._explore["action"] for the step."""
+        ex, sim = self._explore, self.sim
+        greedy = greedy.to(torch.int32).contiguous()
+        chosen = torch.empty_like(greedy)
+        explored = torch.empty_like(greedy)
+        job = nat.CrowdExploreJob()
+        job.greedy, job.done, job.table, job.state = greedy.data_ptr(), sim.done.data_ptr(), ex["table"].data_ptr(), ex["state"].data_ptr()
+        job.chosen, job.action, job.explored = chosen.data_ptr(), ex["action"].data_ptr(), explored.data_ptr()
+        job.epsilon, job.B, job.n_actions = ex["epsilon"], sim.B, int(n_actions)
+        with torch.cuda.device(sim.device):
+            job.stream = _stream()
+            rc = nat.lib().crowd_explore_select_f64(C.byref(job))
+        nat.check(rc, "crowd_explore_select_f64")
+        ex["explored"].append(explored)
+        return chosen
+
     def _run_chunk(self, phase, cases, keep_states):
         sim, policy = self.sim, self.policy
         robot32, humans32 = sim.reset(phase, cases)
         B = sim.B
+        self._explore = None
         velocity = bool(getattr(policy, "acts_in_velocity", False))
         if velocity:
             policy.check_kinematics(sim.kinematics)
@@ -376,6 +425,8 @@ class VectorExplorer(object):
             if policy.action_space is None:
                 policy.build_action_space(sim.cfg.robot_v_pref)
             table = torch.tensor(as_array(policy.action_space), dtype=torch.float64, device=sim.device)
+            if self.exploration == "device" and phase == "train":      # val / test: no draw is observable, no kernel runs
+                self._explore = self._seed_exploration(table)
         max_steps = int(round(sim.cfg.time_limit / sim.cfg.time_step)) + 2
         outcome = torch.zeros(B, dtype=torch.int32, device=sim.device)
         rewards, infos, dmins, states, actions = [], [], [], [], []
@@ -398,7 +449,13 @@ class VectorExplorer(object):
             elif keep_states:
                 states.append((robot32.clone(), humans32.clone()))
             idx = self._act(robot32, humans32, phase, None if velocity else table.shape[0])
-            (robot32, humans32), reward, _, info = sim.step(idx if velocity else table[idx],
+            if velocity:
+                act = idx
+            elif self._explore is not None:
+                act = self._explore["action"]                # the select kernel's rows: table[idx], bit for bit
+            else:
+                act = table[idx]
+            (robot32, humans32), reward, _, info = sim.step(act,
                                                             out=None if record is None else tuple(r[t] for r in record[2:]))
             if velocity:
                 idx = idx.clone()                        # the policy may hand out one buffer per call
@@ -415,6 +472,7 @@ class VectorExplorer(object):
         return {"outcome": outcome.cpu().numpy(), "time": sim.time.cpu().numpy().copy(), "lengths": lengths,
                 "rewards": reward_t, "info": info_t, "dmin": torch.stack(dmins).cpu().numpy(),
                 "states": states, "actions": actions,
+                "explored": None if self._explore is None else self._explore["explored"],
                 "recorded": None if record is None else tuple(r[:len(infos)] for r in record[:4])}
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None, epoch=None,
@@ -429,6 +487,8 @@ class VectorExplorer(object):
         cumulative_rewards, average_returns = [], []
         discomfort = 0
         per_episode = {"case": [], "outcome": [], "time": [], "length": [], "actions": []}
+        if self.exploration == "device":
+            per_episode["explored"] = []                 # per episode: 0 / 1 per decision (all 0 where no stream is drawn from)
         for lo in range(0, k, self.max_batch):
             chunk = cases[lo:lo + self.max_batch]
             run = self._run_chunk(phase, chunk, keep_states=update_memory)
@@ -437,6 +497,7 @@ class VectorExplorer(object):
             cum, avg_ret = discounted_statistics(run["rewards"], run["lengths"], step_discount)
             velocity = bool(getattr(self.policy, "acts_in_velocity", False))
             acts = torch.stack(run["actions"]).cpu().numpy() if run["actions"] else np.zeros((0, len(chunk)), np.int64)
+            took = torch.stack(run["explored"]).cpu().numpy() if run["explored"] else None
             for b in range(len(chunk)):
                 i = lo + b
                 code = int(run["outcome"][b])
@@ -458,6 +519,9 @@ class VectorExplorer(object):
                     per_episode["actions"].append([(float(a[0]), float(a[1])) for a in acts[:int(run["lengths"][b]), b]])
                 else:
                     per_episode["actions"].append([int(a) for a in acts[:int(run["lengths"][b]), b]])
+                if "explored" in per_episode:
+                    n = int(run["lengths"][b])
+                    per_episode["explored"].append([0] * n if took is None else [int(x) for x in took[:n, b]])
             danger = run["info"] == 1
             discomfort += int(danger.sum())
             min_dist.extend(run["dmin"][danger].tolist())

@@ -5,28 +5,9 @@
 #include "rgl_common.h"
 #include "rgl_mfma.h"
 
-namespace {
+using rgl::ChildrenArgs;      // rgl_search_args.h
 
-struct ChildrenArgs {
-    const float* robot;        // [P][9]
-    const float* humans;       // [P / humans_per][H][5]
-    int humans_per;
-    const double* actions;     // [A][2]
-    int P, H, A, kinematics;
-    double dt;
-    int joint;                 // 1: position differences in float64 (JointState roots), 0: rounded to fp32 first
-    float* child_robot;        // [P][A][9]
-    float* reward;             // [P][A]
-    const double* robot64;     // null, or the float64 states robot / humans were rounded from (joint roots): the reward reads these
-    const double* humans64;
-    float* reward_clip;        // null, or [P][A]: the same rewards read as a TENSOR-BORN state (joint = 0 on the fp32 rows) -- what
-                               // upstream's root action_clip sees of a joint-state root (model_predictive_rl.py:216-218,246-248)
-    int p_base, c_base;        // `robot` / `humans` start at parent p_base / crowd c_base (0 for whole-level arrays; a workgroup that staged
-                               // its own parents' rows in LDS hands in its sub-range -- no pointer is ever rebased below its buffer:
-                               // a flat LDS address that leaves the aperture faults, HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION)
-    float v_max;               // > 0: an upper bound of the table's speeds (MprlPlanner::action_speed_bound, ABI 8); 0: every wave derives
-                               // it from the table (two dependent float64 loads + a square root + a wave reduction: ~1.5 us of latency)
-};
+namespace {
 
 __device__ __forceinline__ double seg_point_dist_origin(double px, double py, double ex, double ey, bool f32_degenerate,
                                                         float fpx, float fpy) {

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "rgl_hip.h"
+#include "rgl_search_args.h"
 
 #define RGL_HIP_TRY(expr)                          \
     do {                                           \
@@ -69,58 +70,38 @@ int launch_scene_forward(const RglGraph* g, const RglMlp* value_head, const RglM
 int launch_generic_forward(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head,
                            const float* robot, const float* humans, int n_scenes, int scenes_per_crowd, int H,
                            float* H_out, float* A_out, float* value_out, float* humans_next, hipStream_t stream);   // rgl_generic.hip
-// `image` (both launchers of the two-stage pair): null, or the packed weight image of these weights (FusedLds layout,
+// ---- value of the sibling children: one ChildrenCall (rgl_search_args.h) from launch_value_children to the kernel it chooses ------
+// `c.image` (the two-stage pair and the stage-2 head): null, or the packed weight image of these weights (FusedLds layout,
 // pack_images_kernel) -- the kernels then copy their weight images instead of building them from the raw matrices
-int launch_rank1_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                          float* rows_out, hipStream_t stream, const float* image = nullptr);                       // rgl_rank1.hip
-int launch_deep_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                         float* rows_out, int f16, hipStream_t stream, const RglMlp* head = nullptr, float* value = nullptr,
-                         const float* image = nullptr, const void* tail = nullptr, size_t tail_bytes = 0, int* tail_done = nullptr,
-                         int* head_done = nullptr);                                                                 // rgl_deep.hip
-int launch_tile_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                         float* rows_out, hipStream_t stream);                                                      // rgl_tile.hip
-// `tail` (a TailArgs, opaque) with A = rows per parent: the head kernel's workgroups own whole parents and run the search's select /
-// back-up / root steps for them in its tail (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
-int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value,
-                     hipStream_t stream, const float* image = nullptr, const void* tail = nullptr, size_t tail_bytes = 0,
-                     int* tail_done = nullptr, int A = 0);                                                          // rgl_head.hip
+int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_out);                               // rgl_rank1.hip
+int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_out, int f16, const RglMlp* head,
+                         int* head_done);                                                                           // rgl_deep.hip
+int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_out);                                // rgl_tile.hip
+// stage 2, rows [M][64] -> value; for the rows of a call's P * A children (launch_head_children) the head kernel's workgroups own
+// whole parents and run the call's tail for them (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
+int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value, hipStream_t stream);   // rgl_head.hip
+int launch_head_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, const float* rows);         // rgl_head.hip
 // the fused tile kernel (rgl_fused.hip).  Its weight image is prepared in global memory by pack_images_kernel: by the caller once per
-// parameter state (caller_image = MprlPlanner::children_image), else once per tree search (image_ready = 1 on the per-level calls)
+// parameter state (c.image = MprlPlanner::children_image), else once per tree search (c.image_ready = 1 on the per-level calls)
 // or by the call itself, at the END of the workspace it is given.
-// `tail` (optional): a TailArgs (rgl_tail.h, passed opaquely with its size) -- the search's select / back-up / root steps for the
-// parents of this launch; the kernel runs them in its tail and reports *tail_done = 1 (selection done) or 2 (the deepest level:
-// back-up steps and root decision done as well).  0 = the caller launches the stand-alone kernels.
-int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, int H, const float* child_robot,
-                          const float* humans_next, float* child_value, void* workspace, size_t workspace_bytes,
-                          int image_ready, hipStream_t stream, const float* caller_image = nullptr,
-                          const void* tail = nullptr, size_t tail_bytes = 0, int* tail_done = nullptr, int mode = 0,
-                          const void* prologue = nullptr, size_t prologue_bytes = 0);
-// `prologue` (optional, launch_fused_children and launch_value_children): a LevelPrologue -- the launch also runs the level's state
-// predictor and reward / next-state pairs (fused_prologue_fits must hold; it is an error otherwise)
-// mode 2: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
+// kModeBx: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode);
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, int mode = 0);   // P = the largest launch; 1 = the fused kernel does not apply
+                         hipStream_t stream, FusedImageMode mode);   // P = the largest launch; 1 = the fused kernel does not apply
 size_t fused_children_workspace_bytes(int P, int A, int H);
 const float* fused_workspace_image(const void* workspace, size_t workspace_bytes);   // where pack_children_images put the image
-int launch_value_children(const MprlPlanner* pl, const float* child_robot, const float* humans_next, int P, int H,
-                          float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                          int image_ready = 0, const void* tail = nullptr, size_t tail_bytes = 0,
-                          int* tail_done = nullptr, const void* prologue = nullptr, size_t prologue_bytes = 0);   // rgl_fast.hip
+int launch_value_children(const MprlPlanner* pl, ChildrenCall c);                                                  // rgl_fast.hip
 size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);                                        // rgl_fast.hip
-// `children` (optional): a ChildrenArgs (rgl_children.h, passed opaquely with its size) describing the level's independent
-// next-state / reward work; when the MFMA scene kernel runs, it executes that work on extra workgroups of the same launch
-// and sets *children_done.
+// `level`: the parents and crowds, and their independent next-state / reward work; when the MFMA scene kernel runs, it executes that
+// work on extra workgroups of the same launch and sets *children_done.
 // `sp_image`: the three-piece bf16 weight image of the scene kernel (scene_image_bytes, pack_scene_image) when the planner's mode is
 // RGL_CONTRACT_BF16X6; without one the f32 form of the kernel runs
-int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
-                          float* humans_next, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                          const void* children = nullptr, size_t children_bytes = 0, int* children_done = nullptr,
-                          const float* sp_image = nullptr);                                                           // rgl_scene.hip
-// the level prologue of the fused children kernel (RGL_LEVEL_PROLOGUE): `children` is the level's ChildrenArgs, `out` a LevelPrologue
-// (rgl_scene_body.h; both opaque here, passed with their sizes); 1 = the state predictor is outside the prologue's form
-int level_prologue_args(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
-                        float* humans_next, const float* sp_image, const void* children, size_t children_bytes, void* out,
-                        size_t out_bytes);                                                                          // rgl_scene.hip
+int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, float* humans_next, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream, int* children_done, const float* sp_image);   // rgl_scene.hip
+// the level prologue of the fused children kernel (RGL_LEVEL_PROLOGUE) for the parents, crowds and reward work of `children`;
+// 1 = the state predictor is outside the prologue's form
+int level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& children, float* humans_next, const float* sp_image,
+                        LevelPrologue* out);                                                                        // rgl_scene.hip
 // its form check and LDS layout alone (host only, no array): the scene region's floats, the crowds a chunk's row buffer holds
 int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds);   // rgl_scene.hip
 int fused_prologue_region_floats();      // LDS floats the prologue's scene region may take in the fused children kernel   // rgl_fused.hip
@@ -132,8 +113,7 @@ int pack_scene_image(const MprlPlanner* pl, float* image, hipStream_t stream);
 size_t scene_image_bytes_for(const RglGraph& g, const RglMlp* motion_head);          // the same for a graph (+ optional motion head)
 int pack_scene_image_for(const RglGraph& g, const RglMlp* motion_head, float* image, hipStream_t stream);
 
-int launch_scene_children(const MprlPlanner* pl, const float* child_robot, const float* humans_next, int P, int H,
-                          float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream);         // rgl_scene.hip
+int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c);                                           // rgl_scene.hip
 size_t scene_children_workspace_bytes(int P, int A, int H);                                                        // rgl_scene.hip
 
 // the backward pass of large batches as MFMA tile kernels; 1 = outside its envelope / below its batch threshold
@@ -150,6 +130,17 @@ int launch_tiles_forward(const RglGraph* g, const RglMlp* value_head, const RglM
                          const float* humans, int S, int crowds_per, int H, float* H_out, float* value_out, float* humans_next,
                          void* workspace, size_t workspace_bytes, hipStream_t stream);                               // rgl_tile_pipeline.hip
 
+#ifdef RGL_PHASE_TIMING
+// what a unit's rgl_debug_read_*_phase_cycles export does: its 16 counters (HIP_SYMBOL(g_phase_cycles)) out, zeroed on request
+inline int read_phase_cycles(const void* symbol, unsigned long long* out16, int reset) {
+    const unsigned long long z[16] = {0};
+    RGL_HIP_TRY(hipDeviceSynchronize());
+    RGL_HIP_TRY(hipMemcpyFromSymbol(out16, symbol, sizeof(z)));
+    if (reset) RGL_HIP_TRY(hipMemcpyToSymbol(symbol, z, sizeof(z)));
+    return 0;
+}
+#endif
+
 inline int mlp_max_hidden(const RglMlp& m) {
     int w = 0;
     for (int l = 1; l < m.n_layers; ++l) w = m.dims[l] > w ? m.dims[l] : w;
@@ -164,6 +155,19 @@ namespace {
 inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return (e && e[0]) ? atoi(e) : dflt;
+}
+// The switches more than one function asks for, one reader each ("Environment switches").  Read on every call:
+inline bool require_mfma_forward() { const char* e = getenv("RGL_REQUIRE_MFMA_FORWARD"); return e && e[0] == '1'; }
+inline int tiles_forward_mode() { return env_int("RGL_TILES_FORWARD", 1); }      // 0: never the tile kernels, 2: the tile kernels first
+inline int backward_mfma_mode() { return env_int("RGL_BACKWARD_MFMA", -1); }
+// ... and once per process:
+inline bool level_prologue_enabled() {               // off only when it starts with 0
+    static const bool on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+inline bool fused_tail_disabled() {                  // select, back-up and root as stand-alone kernels
+    static const bool off = env_int("RGL_FUSED_NO_TAIL", 0) != 0;
+    return off;
 }
 
 // One operation, rounded on its own.  The search's bookkeeping, the rewards and path G's features follow the reference's chains of

@@ -870,13 +870,7 @@ int launch_deep_nt(const DeepPlan& pl, const HeadArgs& ha, bool f16, bool skip, 
 
 #ifdef RGL_PHASE_TIMING
 extern "C" int rgl_debug_read_deep_phase_cycles(unsigned long long* out16, int reset) {
-    RGL_HIP_TRY(hipDeviceSynchronize());
-    RGL_HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_cycles), 16 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[16] = {0};
-        RGL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)));
-    }
-    return 0;
+    return rgl::read_phase_cycles(HIP_SYMBOL(g_phase_cycles), out16, reset);
 }
 #endif
 
@@ -884,27 +878,26 @@ namespace rgl {
 
 // Returns RGL_OK after launching, a negative / hip error code on failure, or 1 when the request is outside this
 // kernel's envelope (the caller then picks another kernel).
-// `head` .. `head_done` (optional): with the shipped value head and its packed image at hand the kernel also runs stage 2 -- and the
-// search's tail steps, `tail` / `tail_done` as in launch_head_rows -- over the rows of the parents each workgroup owns; *head_done = 1
-// then, and `value` holds the children's values (RGL_DEEP_FUSE_HEAD=0: never, the caller launches robot_head_kernel as before).
-int launch_deep_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                         float* rows_out, int f16, hipStream_t stream, const RglMlp* head, float* value, const float* image,
-                         const void* tail, size_t tail_bytes, int* tail_done, int* head_done) {
+// `head` / `head_done` (optional): with the shipped value head and the call's packed image at hand the kernel also runs stage 2 -- and
+// the search's tail steps, c.tail / c.tail_done as in launch_head_children -- over the rows of the parents each workgroup owns; *head_done
+// = 1 then, and c.child_value holds the children's values (RGL_DEEP_FUSE_HEAD=0: never, the caller launches robot_head_kernel as before).
+int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_out, int f16, const RglMlp* head, int* head_done) {
+    const int P = c.P, A = c.A;
     if (head_done) *head_done = 0;
-    DeepPlan pl = plan_deep(*g, P, A, H);
+    DeepPlan pl = plan_deep(*g, P, A, c.H);
     if (!pl.ok) return 1;
-    pl.a.child_robot = child_robot;
-    pl.a.humans = humans_next;
+    pl.a.child_robot = c.child_robot;
+    pl.a.humans = c.humans_next;
     pl.a.rows_out = rows_out;
     pl.a.fuse_head = 0;
     pl.a.parents_per_wg = 1;
     HeadArgs ha{};
     static const bool fuse_off = [] { const char* e = getenv("RGL_DEEP_FUSE_HEAD"); return e && e[0] == '0'; }();
     const size_t head_lds = (size_t)HeadLds<32, 100, 100>::total * sizeof(float);
-    if (head && head_done && value && image && !fuse_off && head_variant(*head) == 0) {
+    if (head && head_done && c.child_value && c.image && !fuse_off && head_variant(*head) == 0) {
         const size_t lds = pl.lds_bytes > head_lds ? pl.lds_bytes : head_lds;
         int chain = 0;
-        head_args_for(g, head, 0, rows_out, P * A, value, image, tail, tail_bytes, A, 256 * deep_workgroups_per_cu(lds), &ha, &chain);
+        head_args_for(g, head, 0, rows_out, P * A, c.child_value, c.image, c.tail, A, 256 * deep_workgroups_per_cu(lds), &ha, &chain);
         if (!ha.tail.enabled) {                   // stand-alone call: no tail, the same ownership of rows
             const int slots = 256 * deep_workgroups_per_cu(lds);
             ha.parents_per_wg = (P + slots - 1) / slots;
@@ -913,15 +906,15 @@ int launch_deep_children(const RglGraph* g, int P, int A, int H, const float* ch
         pl.lds_bytes = lds;
         pl.a.fuse_head = 1;
         pl.a.parents_per_wg = ha.parents_per_wg;
-        if (tail_done) *tail_done = ha.tail.enabled ? (chain ? 2 : 1) : 0;
+        if (c.tail_done) *c.tail_done = ha.tail.enabled ? (chain ? 2 : 1) : 0;
         *head_done = 1;
     }
     const bool skip = g->skip_connection != 0;
     switch (pl.NT) {
-        case 1: return launch_deep_nt<1>(pl, ha, f16 != 0, skip, stream);
-        case 2: return launch_deep_nt<2>(pl, ha, f16 != 0, skip, stream);
-        case 3: return launch_deep_nt<3>(pl, ha, f16 != 0, skip, stream);
-        default: return launch_deep_nt<4>(pl, ha, f16 != 0, skip, stream);
+        case 1: return launch_deep_nt<1>(pl, ha, f16 != 0, skip, c.stream);
+        case 2: return launch_deep_nt<2>(pl, ha, f16 != 0, skip, c.stream);
+        case 3: return launch_deep_nt<3>(pl, ha, f16 != 0, skip, c.stream);
+        default: return launch_deep_nt<4>(pl, ha, f16 != 0, skip, c.stream);
     }
 }
 

@@ -29,72 +29,64 @@ size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H) {
 }
 
 // V(child) for the A children of each of P parents; children of one parent share humans_next[p].
-int launch_value_children(const MprlPlanner* pl, const float* child_robot, const float* humans_next, int P, int H,
-                          float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream, int image_ready,
-                          const void* tail, size_t tail_bytes, int* tail_done, const void* prologue, size_t prologue_bytes) {
-    if (tail_done) *tail_done = 0;
-    const int A = pl->num_actions;
+int launch_value_children(const MprlPlanner* pl, ChildrenCall c) {
+    if (c.tail_done) *c.tail_done = 0;
+    const int P = c.P, A = c.A, H = c.H;
     const int hv = head_variant(pl->value_head);
     const bool want_f16 = pl->contraction_dtype == RGL_CONTRACT_F16;
     // RGL_CONTRACT_BF16X6 (round 5): f32-WIDTH products (three bf16 pieces per operand, six terms) on the matrix pipe where a kernel
     // offers them -- the first 64 input features of the fused kernel's last head matrix; plain f32 everywhere else
     const bool want_b6 = pl->contraction_dtype == RGL_CONTRACT_BF16X6;
-    const int fused_mode = want_b6 ? 2 : 0;           // kModeBx / kModeF32 (rgl_fused.hip)
     if (pl->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return RGL_ERR_BAD_MODE;      // (2, the split-f16 mode of ABI 4..7, is gone)
-    const bool staged = hv >= 0 && workspace && workspace_bytes >= value_children_workspace_bytes(pl, P, H);
+    const bool staged = hv >= 0 && c.workspace && c.workspace_bytes >= value_children_workspace_bytes(pl, P, H);
     // stage 1, in order of preference: rank-1 (L = 2, N <= 32), shared-crowd deep (L in {2,3}, N <= 60), tiles (softmax
     // similarities, any depth, N <= 64); everything else, or a head without a stage-2 kernel: the general kernel
     int rc = 1;                                            // 1 = no stage-1 kernel launched yet
     if (staged && !want_f16) {
         // one fused kernel over 16-child tiles (L = 2, N <= 32, default head): values come out directly, no stage 2
-        rc = launch_fused_children(&pl->value_graph, &pl->value_head, P, A, H, child_robot, humans_next, child_value, workspace,
-                                   workspace_bytes, image_ready, stream, pl->children_image, tail, tail_bytes, tail_done, fused_mode,
-                                   prologue, prologue_bytes);
+        rc = launch_fused_children(&pl->value_graph, &pl->value_head, c, want_b6 ? kModeBx : kModeF32);
         if (rc != 1) return rc;
     }
-    if (prologue) return RGL_ERR_BAD_MODE;                 // the caller skipped the level's other launches: fused_prologue_fits did not hold
+    if (c.prologue) return RGL_ERR_BAD_MODE;               // the caller skipped the level's other launches: fused_prologue_fits did not hold
     // packed weight image of the value estimator (the caller's, or this search's at the end of the workspace): the two-stage pair
     // copies its weight images from it instead of building them from the raw matrices (most of a small launch)
-    const float* image = (!staged || want_b6) ? nullptr          // (a three-piece bf16 image is in the fused kernel's layout only)
-                         : pl->children_image ? pl->children_image
-                         : image_ready ? fused_workspace_image(workspace, workspace_bytes) : nullptr;
+    c.image = (!staged || want_b6) ? nullptr                     // (a three-piece bf16 image is in the fused kernel's layout only)
+              : c.image ? c.image
+              : c.image_ready ? fused_workspace_image(c.workspace, c.workspace_bytes) : nullptr;
     if (staged) {
         const RglGraph* g = &pl->value_graph;
-        float* rows = (float*)workspace;
-        if (!want_f16) rc = launch_rank1_children(g, P, A, H, child_robot, humans_next, rows, stream, image);
+        float* rows = (float*)c.workspace;
+        if (!want_f16) rc = launch_rank1_children(g, c, rows);
         if (rc == 1) {
             int head_done = 0;
-            rc = launch_deep_children(g, P, A, H, child_robot, humans_next, rows, want_f16 && g->num_layer == 3, stream,
-                                      &pl->value_head, child_value, image, tail, tail_bytes, tail_done, &head_done);
+            rc = launch_deep_children(g, c, rows, want_f16 && g->num_layer == 3, &pl->value_head, &head_done);
             if (want_f16 && (rc == 1 || g->num_layer != 3)) return RGL_ERR_BAD_MODE;
             if (rc != 1 && head_done) return rc;           // stage 2 (and the tail) ran inside the launch
-            if (rc == 1 && tail_done) *tail_done = 0;
+            if (rc == 1 && c.tail_done) *c.tail_done = 0;
         }
-        if (rc == 1) rc = launch_tile_children(g, P, A, H, child_robot, humans_next, rows, stream);
+        if (rc == 1) rc = launch_tile_children(g, c, rows);
         if (rc == 1 && !want_f16) {
             // every child's graph in full, one wave per child: the remaining similarity functions and layerwise graphs
-            rc = launch_scene_children(pl, child_robot, humans_next, P, H, child_value, workspace, workspace_bytes, stream);
+            rc = launch_scene_children(pl, c);
             if (rc != 1) return rc;
         }
     }
     if (want_f16 && rc == 1) return RGL_ERR_BAD_MODE;
     if (rc == 1) {
         // outside the shipped shapes (other embedding MLPs, x_dim = 64): the tile kernels, the children of a parent sharing its crowd's rows
-        rc = launch_tiles_forward(&pl->value_graph, &pl->value_head, nullptr, child_robot, humans_next, P * A, A, H, nullptr, child_value,
-                                  nullptr, workspace, workspace_bytes, stream);
+        rc = launch_tiles_forward(&pl->value_graph, &pl->value_head, nullptr, c.child_robot, c.humans_next, P * A, A, H, nullptr,
+                                  c.child_value, nullptr, c.workspace, c.workspace_bytes, c.stream);
         if (rc != 1) return rc;
     }
     if (rc == 1) {
         // RGL_REQUIRE_MFMA_CHILDREN=1 (tests): refuse instead of running the general VALU kernel
         static const bool require = [] { const char* e = getenv("RGL_REQUIRE_MFMA_CHILDREN"); return e && e[0] == '1'; }();
         if (require) return RGL_ERR_BAD_MODE;
+        return launch_generic_forward(&pl->value_graph, &pl->value_head, nullptr, c.child_robot, c.humans_next, P * A, A, H,
+                                      nullptr, nullptr, c.child_value, nullptr, c.stream);
     }
-    if (rc == 1)
-        return launch_generic_forward(&pl->value_graph, &pl->value_head, nullptr, child_robot, humans_next, P * A, A, H,
-                                      nullptr, nullptr, child_value, nullptr, stream);
     if (rc) return rc;
-    return launch_head_rows(&pl->value_graph, &pl->value_head, (const float*)workspace, P * A, child_value, stream, image,
-                            tail, tail_bytes, tail_done, A);
+    return launch_head_children(&pl->value_graph, &pl->value_head, c, (const float*)c.workspace);
 }
 
 }  // namespace rgl

@@ -1107,9 +1107,10 @@ __global__ __launch_bounds__(kPackThreads) void pack_images_kernel(const FusedAr
     img[e] = v;
 }
 
-// one packed image, in the layout of the kernel that will read it (mode 2: the bf16 /
+// one packed image, in the layout of the kernel that will read it (kModeBx: the bf16 /
 // f32 hybrid of the last head matrix)
-enum { kModeF32 = 0, kModeBx = 2 };      // (1 was the split-f16 mode of ABI 4..7)
+using rgl::kModeBx;      // rgl_search_args.h
+using rgl::kModeF32;
 inline int launch_pack_image(const FusedArgs& a, float* img, int mode, hipStream_t stream) {
     if (mode == kModeBx) {
         using LO = FusedLds<32, 100, 100, true>;
@@ -1235,6 +1236,16 @@ inline ItemPlan plan_items(int P, int n_full, int rem, int unit) {
     return best;
 }
 
+// the matrices the kernel and its packed image read (w_last = the graph's last layer: Ws[1] inside the fused kernel's envelope)
+inline void set_weights(FusedArgs& a, const RglGraph& g, const RglMlp& head) {
+    a.wr1 = g.w_r.weight[0]; a.br1 = g.w_r.bias[0]; a.wr2 = g.w_r.weight[1]; a.br2 = g.w_r.bias[1];
+    a.wa = bilinear_wa(g); a.w1 = g.Ws[0];
+    a.w_last = g.Ws[g.num_layer - 1];
+    a.hw1 = head.weight[0]; a.hb1 = head.bias[0]; a.hw2 = head.weight[1]; a.hb2 = head.bias[1];
+    a.hw3 = head.weight[2]; a.hb3 = head.bias[2]; a.hw4 = head.weight[3]; a.hb4 = head.bias[3];
+    a.wh1 = g.w_h.weight[0]; a.bh1 = g.w_h.bias[0]; a.wh2 = g.w_h.weight[1]; a.bh2 = g.w_h.bias[1];
+}
+
 // mode kModeBx: the six-term bf16 products are wanted (RGL_CONTRACT_BF16X6): such a plan takes every launch size (the two-stage pair
 // has no such head, and the packed image is in this kernel's layout only).
 inline FusedPlan plan_fused(const RglGraph& g, const RglMlp& head, int P, int A, int H, int unit = 1, int mode = kModeF32) {
@@ -1270,12 +1281,7 @@ inline FusedPlan plan_fused(const RglGraph& g, const RglMlp& head, int P, int A,
     pl.lds_bytes = (size_t)((pl.bx ? FusedLds<32, 100, 100, true>::scratch : FusedLds<32, 100, 100, false>::scratch) +
                             kFusedWaves * fused_scratch_floats(pl.hr, pl.nt, a.sim == SIM_SOFTMAX) + 4) * sizeof(float);   // + the arrival counter of the image
     if (pl.lds_bytes > (size_t)rgl::kLdsBytesPerCu) return pl;
-    a.wr1 = g.w_r.weight[0]; a.br1 = g.w_r.bias[0]; a.wr2 = g.w_r.weight[1]; a.br2 = g.w_r.bias[1];
-    a.wa = bilinear_wa(g); a.w1 = g.Ws[0];
-    a.w_last = g.Ws[1];
-    a.hw1 = head.weight[0]; a.hb1 = head.bias[0]; a.hw2 = head.weight[1]; a.hb2 = head.bias[1];
-    a.hw3 = head.weight[2]; a.hb3 = head.bias[2]; a.hw4 = head.weight[3]; a.hb4 = head.bias[3];
-    a.wh1 = g.w_h.weight[0]; a.bh1 = g.w_h.bias[0]; a.wh2 = g.w_h.weight[1]; a.bh2 = g.w_h.bias[1];
+    set_weights(a, g, head);
     pl.ok = true;
     return pl;
 }
@@ -1324,13 +1330,7 @@ inline int launch_fused(const FusedPlan& pl, bool skip, hipStream_t st) {
 
 #ifdef RGL_PHASE_TIMING
 extern "C" int rgl_debug_read_fused_phase_cycles(unsigned long long* out16, int reset) {
-    RGL_HIP_TRY(hipDeviceSynchronize());
-    RGL_HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_cycles), 16 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[16] = {0};
-        RGL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)));
-    }
-    return 0;
+    return rgl::read_phase_cycles(HIP_SYMBOL(g_phase_cycles), out16, reset);
 }
 #endif
 
@@ -1353,40 +1353,25 @@ const float* fused_workspace_image(const void* workspace, size_t workspace_bytes
 
 // 1 = the fused kernel does not apply (or the workspace cannot hold its images)
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, int mode) {
-    FusedPlan fp = plan_fused(*g, *head, P, A, H, 1, mode);                    // kModeF32 / kModeBx
+                         hipStream_t stream, FusedImageMode mode) {
+    FusedPlan fp = plan_fused(*g, *head, P, A, H, 1, mode);
     if (!fp.ok || !workspace || workspace_bytes < fused_children_workspace_bytes(P, A, H)) return 1;
     return launch_pack_image(fp.a, image_of(workspace, workspace_bytes), fp.mode(), stream);
 }
 
 // 1 = outside this kernel's envelope
-int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, int H, const float* child_robot,
-                          const float* humans_next, float* child_value, void* workspace, size_t workspace_bytes,
-                          int image_ready, hipStream_t stream, const float* caller_image, const void* tail, size_t tail_bytes,
-                          int* tail_done, int mode, const void* prologue, size_t prologue_bytes) {
-    if (tail_done) *tail_done = 0;
-    const LevelPrologue* lp = (prologue && prologue_bytes == sizeof(LevelPrologue)) ? (const LevelPrologue*)prologue : nullptr;
-    if (prologue && !lp) return RGL_ERR_BAD_MODE;
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode) {
+    const int P = c.P, A = c.A, H = c.H;
+    if (c.tail_done) *c.tail_done = 0;
     // the search's tail: selection always; the back-up chain + root step at the deepest level when handing whole roots to
     // workgroups does not starve the GPU (few roots with many parents each -- unclipped deep searches -- keep unit = 1)
-    const TailArgs* ta = (tail && tail_bytes == sizeof(TailArgs) && ((const TailArgs*)tail)->enabled) ? (const TailArgs*)tail : nullptr;
-    static const bool tail_off = env_int("RGL_FUSED_NO_TAIL", 0) != 0;          // measurements / tests: stand-alone kernels
-    if (tail_off) ta = nullptr;
-    int unit = 1, chain = 0;
-    if (ta && ta->chain) {
-        long u = 1;
-        for (int l = 0; l < ta->level && u <= P; ++l) u *= ta->W;
-        if (u <= P && P % u == 0 && P / u >= fused_cu_count() / 2) {
-            unit = (int)u;
-            chain = 1;
-        } else if (u == 1) {
-            chain = 1;
-        }
-    }
+    const TailArgs* ta = (c.tail && c.tail->enabled && !fused_tail_disabled()) ? c.tail : nullptr;
+    int chain = 0;
+    const int unit = ta ? tail_ownership(*ta, P, fused_cu_count() / 2, &chain) : 1;
     FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);
-    if (lp) {
-        if (!prologue_form(fp, lp->scene_floats)) return RGL_ERR_BAD_MODE;      // fused_prologue_fits was not asked
-        fp.pro = lp;
+    if (c.prologue) {
+        if (!prologue_form(fp, c.prologue->scene_floats)) return RGL_ERR_BAD_MODE;      // fused_prologue_fits was not asked
+        fp.pro = c.prologue;
     }
     // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch), and of 17..20 with a
     // plain-weight similarity (unpacked row pass: 172 944 bytes), do not fit a CU with it -- they run the f32 form of this kernel on
@@ -1397,16 +1382,16 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
         own_image = fp.ok;
     }
     if (!fp.ok) return 1;
-    if (!workspace || workspace_bytes < fused_children_workspace_bytes(P, A, H)) return 1;
-    if (own_image || (!image_ready && !caller_image)) {
-        int rc = launch_pack_image(fp.a, image_of(workspace, workspace_bytes), fp.mode(), stream);
+    if (!c.workspace || c.workspace_bytes < fused_children_workspace_bytes(P, A, H)) return 1;
+    if (own_image || (!c.image_ready && !c.image)) {
+        int rc = launch_pack_image(fp.a, image_of(c.workspace, c.workspace_bytes), fp.mode(), c.stream);
         if (rc) return rc;
     }
-    const float* image = (caller_image && !own_image) ? caller_image : image_of(workspace, workspace_bytes);
-    float* rows_left = (float*)workspace;
-    fp.a.child_robot = child_robot;
-    fp.a.humans = humans_next;
-    fp.a.value = child_value;
+    const float* image = (c.image && !own_image) ? c.image : image_of(c.workspace, c.workspace_bytes);
+    float* rows_left = (float*)c.workspace;
+    fp.a.child_robot = c.child_robot;
+    fp.a.humans = c.humans_next;
+    fp.a.value = c.child_value;
     fp.a.image = image;
     fp.a.rows_left = rows_left;
     static const int image_sync = env_int("RGL_FUSED_IMAGE_SYNC", 0);
@@ -1418,8 +1403,8 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, int P, int A, i
         fp.a.tail = *ta;
         fp.a.tail.chain = chain;
     }
-    const int rc = launch_fused(fp, g->skip_connection != 0, stream);
-    if (rc == RGL_OK && ta && tail_done) *tail_done = chain ? 2 : 1;
+    const int rc = launch_fused(fp, g->skip_connection != 0, c.stream);
+    if (rc == RGL_OK && ta && c.tail_done) *c.tail_done = chain ? 2 : 1;
     return rc;
 }
 
@@ -1448,9 +1433,8 @@ extern "C" int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, in
     if (!planner || !plan) return RGL_ERR_NULL;
     if (P < 1 || H < 1 || crowds_per < 1 || unit < 1 || P % crowds_per) return RGL_ERR_BAD_SHAPE;
     *plan = RglPrologueEmbeddingPlan{};
-    static const bool prologue_on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
     int scene_floats = 0, chunk_crowds = 0;
-    if (!prologue_on || rgl::level_prologue_layout(planner, crowds_per, P, H, &scene_floats, &chunk_crowds)) return RGL_OK;
+    if (!level_prologue_enabled() || rgl::level_prologue_layout(planner, crowds_per, P, H, &scene_floats, &chunk_crowds)) return RGL_OK;
     if (!rgl::fused_prologue_fits(planner, P, H, ~(size_t)0, scene_floats)) return RGL_OK;
     const FusedPlan fp = plan_fused(planner->value_graph, planner->value_head, P, planner->num_actions, H, unit, kModeBx);
     const int k = fp.a.parents_per_wg;
@@ -1476,12 +1460,7 @@ static bool head_image_args(const RglGraph& g, const RglMlp& head, FusedArgs& a)
     if (!fast_path_enabled() || g.x_dim != XD || g.num_layer < 2 || g.num_layer > RGL_MAX_GCN_LAYERS) return false;
     if (!mlp_is(g.w_r, 9, HID, XD, true) || !mlp_is(g.w_h, 5, HID, XD, true) || head_variant(head) != 0) return false;
     a = FusedArgs{};
-    a.wr1 = g.w_r.weight[0]; a.br1 = g.w_r.bias[0]; a.wr2 = g.w_r.weight[1]; a.br2 = g.w_r.bias[1];
-    a.wa = bilinear_wa(g); a.w1 = g.Ws[0];
-    a.w_last = g.Ws[g.num_layer - 1];
-    a.hw1 = head.weight[0]; a.hb1 = head.bias[0]; a.hw2 = head.weight[1]; a.hb2 = head.bias[1];
-    a.hw3 = head.weight[2]; a.hb3 = head.bias[2]; a.hw4 = head.weight[3]; a.hb4 = head.bias[3];
-    a.wh1 = g.w_h.weight[0]; a.bh1 = g.w_h.bias[0]; a.wh2 = g.w_h.weight[1]; a.bh2 = g.w_h.bias[1];
+    set_weights(a, g, head);
     return true;
 }
 

@@ -403,8 +403,7 @@ extern "C" size_t rgl_graph_forward_workspace_bytes(const RglGraph* graph, const
     const size_t scene = rgl::scene_forward_workspace_bytes(graph, value_head, motion_head, n_scenes, scenes_per_crowd, H);
     // outside the shipped shapes: the tile kernels (other embedding MLPs, x_dim = 64); RGL_TILES_FORWARD=2 (tests) runs them first
     // for the shipped shapes too
-    const char* e = getenv("RGL_TILES_FORWARD");
-    if ((scene && !(e && e[0] == '2')) || rgl::validate_graph(*graph, H)) return scene;
+    if ((scene && tiles_forward_mode() != 2) || rgl::validate_graph(*graph, H)) return scene;
     const size_t tiles = rgl::tiles_forward_workspace_bytes(graph, value_head, motion_head, n_scenes, scenes_per_crowd, H, 0);
     return scene > tiles ? scene : tiles;
 }
@@ -419,13 +418,10 @@ extern "C" int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_
                                             humans_next);
         if (rc) return rc;
         if (n_scenes == 0) return RGL_OK;
-        {   // RGL_TILES_FORWARD=2 (tests): the tile kernels first, also for the shipped shapes
-            const char* e = getenv("RGL_TILES_FORWARD");
-            if (e && e[0] == '2') {
-                rc = rgl::launch_tiles_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, nullptr,
-                                               value_out, humans_next, workspace, workspace_bytes, (hipStream_t)stream);
-                if (rc != 1) return rc;
-            }
+        if (tiles_forward_mode() == 2) {      // RGL_TILES_FORWARD=2 (tests): the tile kernels first, also for the shipped shapes
+            rc = rgl::launch_tiles_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, nullptr,
+                                           value_out, humans_next, workspace, workspace_bytes, (hipStream_t)stream);
+            if (rc != 1) return rc;
         }
         rc = rgl::launch_scene_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, value_out,
                                        humans_next, workspace, workspace_bytes, (hipStream_t)stream);
@@ -434,8 +430,7 @@ extern "C" int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_
                                        humans_next, workspace, workspace_bytes, (hipStream_t)stream);
         if (rc != 1) return rc;
         // RGL_REQUIRE_MFMA_FORWARD=1 (tests): refuse instead of running the general VALU kernel
-        const char* e = getenv("RGL_REQUIRE_MFMA_FORWARD");
-        if (e && e[0] == '1') return RGL_ERR_BAD_MODE;
+        if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
     }
     return rgl::launch_generic_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H,
                                        H_out, A_out, value_out, humans_next, (hipStream_t)stream);

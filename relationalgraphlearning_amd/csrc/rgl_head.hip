@@ -123,11 +123,9 @@ __global__ __launch_bounds__(kAnyWaves * 64) void robot_head_any_kernel(const He
 
 }  // namespace
 
-namespace rgl {
-
 // rows [M][64] (stage-1 hand-off) -> value;  1 = no kernel for this head (see head_variant)
-int launch_head_rows(const RglGraph* g, const RglMlp* h, const float* rows, int M, float* value, hipStream_t stream,
-                     const float* image, const void* tail, size_t tail_bytes, int* tail_done, int A) {
+static int launch_stage2(const RglGraph* g, const RglMlp* h, const float* rows, int M, float* value, hipStream_t stream,
+                         const float* image, const TailArgs* tail, int* tail_done, int A) {
     if (tail_done) *tail_done = 0;
     const int hv = head_variant(*h);
     if (hv < 0) return 1;
@@ -151,10 +149,20 @@ int launch_head_rows(const RglGraph* g, const RglMlp* h, const float* rows, int 
     }
     HeadArgs ha;
     int chain = 0;
-    head_args_for(g, h, hv, rows, M, value, image, tail, tail_bytes, A, hv == 0 ? 512 : 256, &ha, &chain);
+    head_args_for(g, h, hv, rows, M, value, image, tail, A, hv == 0 ? 512 : 256, &ha, &chain);
     const int rc = hv == 0 ? launch_head<32, 100, 100>(ha, stream) : launch_head<150, 100, 100>(ha, stream);
     if (rc == RGL_OK && ha.tail.enabled && tail_done) *tail_done = chain ? 2 : 1;
     return rc;
+}
+
+namespace rgl {
+
+int launch_head_rows(const RglGraph* g, const RglMlp* h, const float* rows, int M, float* value, hipStream_t stream) {
+    return launch_stage2(g, h, rows, M, value, stream, nullptr, nullptr, nullptr, 0);
+}
+
+int launch_head_children(const RglGraph* g, const RglMlp* h, const ChildrenCall& c, const float* rows) {
+    return launch_stage2(g, h, rows, c.P * c.A, c.child_value, c.stream, c.image, c.tail, c.tail_done, c.A);
 }
 
 }  // namespace rgl

@@ -155,7 +155,7 @@ __device__ __forceinline__ void head_rows_and_tail(float* lds, const HeadArgs& a
 // HeadArgs of the shipped heads for the rows of P = M / A parents; `slots` = workgroups the launch keeps resident.  With the search's
 // tail arguments: parents per workgroup and whether the launch runs the whole back-up chain (returned in *chain).
 inline void head_args_for(const RglGraph* g, const RglMlp* h, int hv, const float* rows, int M, float* value, const float* image,
-                          const void* tail, size_t tail_bytes, int A, int slots, HeadArgs* out, int* chain_out) {
+                          const TailArgs* tail, int A, int slots, HeadArgs* out, int* chain_out) {
     HeadArgs& ha = *out;
     ha.image = hv == 0 ? image : nullptr;
     ha.w_last = g->Ws[g->num_layer - 1];
@@ -170,21 +170,13 @@ inline void head_args_for(const RglGraph* g, const RglMlp* h, int hv, const floa
     ha.n_tiles = (M + 15) / 16;
     ha.tail = TailArgs{};
     ha.A = A; ha.P = A > 0 ? M / A : 0; ha.parents_per_wg = 1; ha.own_rows = 0;
-    const TailArgs* ta = (tail && tail_bytes == sizeof(TailArgs) && ((const TailArgs*)tail)->enabled && A > 0 && M % A == 0)
-                             ? (const TailArgs*)tail : nullptr;
-    static const bool tail_off = [] { const char* e = getenv("RGL_FUSED_NO_TAIL"); return e && e[0] == '1'; }();
+    const TailArgs* ta = (tail && tail->enabled && A > 0 && M % A == 0) ? tail : nullptr;
     int chain = 0;
-    if (ta && !tail_off) {
-        // parents per workgroup: one workgroup slot per parent block, whole roots at the deepest level where that keeps >= half
-        // of the slots busy (as in the fused children kernel)
+    if (ta && !fused_tail_disabled()) {
+        // parents per workgroup: one workgroup slot per parent block, whole roots at the deepest level where that keeps half of the
+        // slots, or 128 of them, busy
         const int P = ha.P;
-        int unit = 1;
-        if (ta->chain) {
-            long u = 1;
-            for (int l = 0; l < ta->level && u <= P; ++l) u *= ta->W;
-            if (u <= P && P % u == 0 && (P / u >= slots / 2 || P / u >= 128)) { unit = (int)u; chain = 1; }
-            else if (u == 1) chain = 1;
-        }
+        const int unit = rgl::tail_ownership(*ta, P, slots / 2 < 128 ? slots / 2 : 128, &chain);
         int k = (P + slots - 1) / slots;
         if (k < 1) k = 1;
         k = ((k + unit - 1) / unit) * unit;

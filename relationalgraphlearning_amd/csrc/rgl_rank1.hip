@@ -601,28 +601,21 @@ inline int launch_rank1(const Rank1Plan& pl, bool skip, hipStream_t st) {
 
 #ifdef RGL_PHASE_TIMING
 extern "C" int rgl_debug_read_phase_cycles(unsigned long long* out16, int reset) {
-    RGL_HIP_TRY(hipDeviceSynchronize());
-    RGL_HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_cycles), 16 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[16] = {0};
-        RGL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)));
-    }
-    return 0;
+    return rgl::read_phase_cycles(HIP_SYMBOL(g_phase_cycles), out16, reset);
 }
 #endif
 
 namespace rgl {
 
 // 1 = outside this kernel's envelope
-int launch_rank1_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                          float* rows_out, hipStream_t stream, const float* image) {
-    Rank1Plan rp = plan_rank1(*g, P, A, H);
+int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_out) {
+    Rank1Plan rp = plan_rank1(*g, c.P, c.A, c.H);
     if (!rp.ok) return 1;
-    rp.a.image = rp.image_layout ? image : nullptr;
-    rp.a.child_robot = child_robot;
-    rp.a.humans = humans_next;
+    rp.a.image = rp.image_layout ? c.image : nullptr;
+    rp.a.child_robot = c.child_robot;
+    rp.a.humans = c.humans_next;
     rp.a.rows_out = rows_out;
-    return launch_rank1(rp, g->skip_connection != 0, stream);
+    return launch_rank1(rp, g->skip_connection != 0, c.stream);
 }
 
 }  // namespace rgl

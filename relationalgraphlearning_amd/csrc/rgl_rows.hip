@@ -971,12 +971,6 @@ extern "C" int rgl_plan_mlp_rows(const RglMlp* mlp, int n_rows, int max_waves, R
 
 #ifdef RGL_PHASE_TIMING
 extern "C" int rgl_debug_read_backward_phase_cycles(unsigned long long* out16, int reset) {
-    RGL_HIP_TRY(hipDeviceSynchronize());
-    RGL_HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_cycles), 16 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[16] = {0};
-        RGL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z)));
-    }
-    return 0;
+    return rgl::read_phase_cycles(HIP_SYMBOL(g_phase_cycles), out16, reset);
 }
 #endif

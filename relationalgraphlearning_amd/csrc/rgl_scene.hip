@@ -234,10 +234,6 @@ int launch_scene(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* chil
     return launch_scene_k<NT, 1, WAVES>(sa, lds_bytes, children, st);
 }
 
-}  // namespace
-
-namespace {
-
 static bool scene_kernel_covers(const RglGraph& g, int N) {
     const bool path_m = mlp_is(g.w_r, 9, HID, XD, true) && mlp_is(g.w_h, 5, HID, XD, true);
     const bool path_g = mlp_is(g.w_r, 6, HID, XD, true) && mlp_is(g.w_h, 7, HID, XD, true);        // gcn.ValueNetwork's inputs
@@ -245,44 +241,12 @@ static bool scene_kernel_covers(const RglGraph& g, int N) {
            (path_m || path_g) && N <= 128 && (N <= 64 || scene_similarity_mode(g) != SIM_CONCAT);
 }
 
-static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per,
-                           int P, int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows, bool embed_inside,
-                           const float* sp_image, int slots, int region_floats = 0);
-
-// embeddings (one launch) + one-wave-per-scene graph forward; mh != null: motion head -> humans_next; rows_out != null: value rows
-static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per, int P,
-                             int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows,
-                             const ChildrenArgs* ca, hipStream_t stream, const ChildrenArgs* embed_children = nullptr,
-                             const float* sp_image = nullptr) {
-    const int N = H + 1, n_crowds = P / crowds_per;
-    const int NT0 = N > 64 ? 8 : (N + 15) / 16;
-    // few scenes of the shipped shape: the scene kernel embeds its own node tiles (one launch for the level instead of two)
-    static const bool emb_off = [] { const char* e = getenv("RGL_SCENE_EMBED_INSIDE"); return e && e[0] == '0'; }();
-    const bool embed_inside = !emb_off && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
-                              (NT0 == 1 || NT0 == 2 || NT0 == 4) && P <= 512 &&     // measured: +1.5-3 % up to 512 scenes, -2 % at 1-2 k (sibling scenes repeat their crowd's rows)
-                              (NT0 == 1 || P < scene_split_below(NT0));       // the split form (see launch_scene)
-    if (!embed_inside) {
-        int rc = launch_row_mlp2_pair(g.w_r, robot, x0_rows, P, g.w_h, humans, xh_rows, n_crowds * H, stream, embed_children);
-        if (rc) return rc;
-    }
-    SceneArgs sa;
-    const size_t lds_bytes = fill_scene_args(sa, g, mh, robot, humans, crowds_per, P, H, humans_next, rows_out, x0_rows, xh_rows,
-                                             embed_inside, sp_image, 0) * sizeof(float);
-    switch (NT0) {
-        case 1: return launch_scene<1, 8>(sa, lds_bytes, ca, stream);
-        case 2: return launch_scene<2, 8>(sa, lds_bytes, ca, stream);
-        case 3: return launch_scene<3, 4>(sa, lds_bytes, ca, stream);
-        case 4: return launch_scene<4, 4>(sa, lds_bytes, ca, stream);
-        default: return launch_scene_wide(sa, lds_bytes, ca, stream);
-    }
-}
-
 // SceneArgs of the scene kernel (and of the level prologue); returns the LDS floats.  `slots` > 0: the level prologue -- that many
 // scene slots in the workgroup (one per wave) and the row buffer of its cooperative embeddings, as large as `region_floats` LDS floats
 // leave room for; 0: the launcher's choice
 static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per,
                            int P, int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows, bool embed_inside,
-                           const float* sp_image, int slots, int region_floats) {
+                           const float* sp_image, int slots, int region_floats = 0) {
     const int N = H + 1;
     const int NT = N > 64 ? 8 : (N + 15) / 16;
     sa.robot_rows = embed_inside ? robot : nullptr;
@@ -342,6 +306,34 @@ static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, c
     return off;
 }
 
+// embeddings (one launch) + one-wave-per-scene graph forward; mh != null: motion head -> humans_next; rows_out != null: value rows
+static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per, int P,
+                             int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows,
+                             const ChildrenArgs* ca, hipStream_t stream, const ChildrenArgs* embed_children = nullptr,
+                             const float* sp_image = nullptr) {
+    const int N = H + 1, n_crowds = P / crowds_per;
+    const int NT0 = N > 64 ? 8 : (N + 15) / 16;
+    // few scenes of the shipped shape: the scene kernel embeds its own node tiles (one launch for the level instead of two)
+    static const bool emb_off = [] { const char* e = getenv("RGL_SCENE_EMBED_INSIDE"); return e && e[0] == '0'; }();
+    const bool embed_inside = !emb_off && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
+                              (NT0 == 1 || NT0 == 2 || NT0 == 4) && P <= 512 &&     // measured: +1.5-3 % up to 512 scenes, -2 % at 1-2 k (sibling scenes repeat their crowd's rows)
+                              (NT0 == 1 || P < scene_split_below(NT0));       // the split form (see launch_scene)
+    if (!embed_inside) {
+        int rc = launch_row_mlp2_pair(g.w_r, robot, x0_rows, P, g.w_h, humans, xh_rows, n_crowds * H, stream, embed_children);
+        if (rc) return rc;
+    }
+    SceneArgs sa;
+    const size_t lds_bytes = fill_scene_args(sa, g, mh, robot, humans, crowds_per, P, H, humans_next, rows_out, x0_rows, xh_rows,
+                                             embed_inside, sp_image, 0) * sizeof(float);
+    switch (NT0) {
+        case 1: return launch_scene<1, 8>(sa, lds_bytes, ca, stream);
+        case 2: return launch_scene<2, 8>(sa, lds_bytes, ca, stream);
+        case 3: return launch_scene<3, 4>(sa, lds_bytes, ca, stream);
+        case 4: return launch_scene<4, 4>(sa, lds_bytes, ca, stream);
+        default: return launch_scene_wide(sa, lds_bytes, ca, stream);
+    }
+}
+
 }  // namespace
 
 namespace rgl {
@@ -382,16 +374,12 @@ int pack_scene_image_for(const RglGraph& g, const RglMlp* mh, float* image, hipS
 // The level prologue of the fused children kernel (rgl_fused.hip): the state predictor's scenes of the parents a workgroup owns in the
 // unsplit BX + EMB form of scene_body (one slot per wave, embeddings inside), and the level's reward / next-state pairs.  1 = outside
 // that form's envelope: the six-term bf16 scene kernel with two node tiles (softmax similarity, 9-wide robot state, a motion head).
-int level_prologue_args(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
-                        float* humans_next, const float* sp_image, const void* children, size_t children_bytes, void* out,
-                        size_t out_bytes) {
-    if (!out || out_bytes != sizeof(LevelPrologue) || !children || children_bytes != sizeof(ChildrenArgs)) return 1;
-    if (!sp_image || level_prologue_layout(pl, crowds_per, P, H, nullptr, nullptr)) return 1;
-    LevelPrologue* lp = (LevelPrologue*)out;
-    lp->scene_floats = fill_scene_args(lp->scene, pl->predictor_graph, &pl->motion_head, robot, humans, crowds_per, P, H, humans_next,
-                                       nullptr, nullptr, nullptr, true, sp_image, 8, fused_prologue_region_floats());
+int level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& ca, float* humans_next, const float* sp_image, LevelPrologue* lp) {
+    if (!sp_image || level_prologue_layout(pl, ca.humans_per, ca.P, ca.H, nullptr, nullptr)) return 1;
+    lp->scene_floats = fill_scene_args(lp->scene, pl->predictor_graph, &pl->motion_head, ca.robot, ca.humans, ca.humans_per, ca.P, ca.H,
+                                       humans_next, nullptr, nullptr, nullptr, true, sp_image, 8, fused_prologue_region_floats());
     if (!lp->scene.bx) return 1;
-    lp->children = *(const ChildrenArgs*)children;
+    lp->children = ca;
     return 0;
 }
 
@@ -414,11 +402,11 @@ int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, i
 }
 
 // humans_next[s] = motion_head(RGL(robot[s], humans[s / crowds_per]))[1:]  for P scenes (StatePredictor.forward).
-int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float* humans, int crowds_per, int P, int H,
-                          float* humans_next, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                          const void* children, size_t children_bytes, int* children_done, const float* sp_image) {
-    const ChildrenArgs* ca = (children && children_bytes == sizeof(ChildrenArgs)) ? (const ChildrenArgs*)children : nullptr;
-    if (children_done) *children_done = 0;
+int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, float* humans_next, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream, int* children_done, const float* sp_image) {
+    const float *robot = level.robot, *humans = level.humans;
+    const int crowds_per = level.humans_per, P = level.P, H = level.H;
+    *children_done = 0;
     const RglGraph& g = pl->predictor_graph;
     const RglMlp& mh = pl->motion_head;
     const int N = H + 1;
@@ -431,8 +419,7 @@ int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float
                                                 workspace_bytes, stream);
             if (rc != 1) return rc;
         }
-        const char* e = getenv("RGL_REQUIRE_MFMA_FORWARD");          // tests: refuse instead of running the general VALU kernel
-        if (e && e[0] == '1') return RGL_ERR_BAD_MODE;
+        if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
         return launch_generic_forward(&g, nullptr, &mh, robot, humans, P, crowds_per, H, nullptr, nullptr, nullptr,
                                       humans_next, stream);
     }
@@ -444,11 +431,11 @@ int launch_predict_humans(const MprlPlanner* pl, const float* robot, const float
     // 2048 roots 0.3022 -> 0.2988 ms, 1024 roots 0.1773 -> 0.1759, 512 roots unchanged); RGL_SCENE_CHILDREN_BELOW overrides (measurements)
     static const int below_env = [] { const char* e = getenv("RGL_SCENE_CHILDREN_BELOW"); return e ? atoi(e) : -1; }();
     const int children_in_scene_below = below_env >= 0 ? below_env : (pl->contraction_dtype == RGL_CONTRACT_BF16X6 ? 1100 : 3072);
-    const ChildrenArgs* in_scene = (ca && P < children_in_scene_below) ? ca : nullptr;
-    const ChildrenArgs* in_embed = (ca && !in_scene) ? ca : nullptr;
+    const ChildrenArgs* in_scene = P < children_in_scene_below ? &level : nullptr;
+    const ChildrenArgs* in_embed = in_scene ? nullptr : &level;
     const int rc = run_scene_kernels(g, &mh, robot, humans, crowds_per, P, H, humans_next, nullptr, x0_rows, xh_rows, in_scene, stream,
                                      in_embed, pl->contraction_dtype == RGL_CONTRACT_BF16X6 ? sp_image : nullptr);
-    if (rc == RGL_OK && ca && children_done) *children_done = 1;
+    if (rc == RGL_OK) *children_done = 1;
     return rc;
 }
 
@@ -500,19 +487,18 @@ size_t scene_children_workspace_bytes(int P, int A, int H) {
     return ((size_t)P * A * (XD + 64) + (size_t)P * H * XD) * sizeof(float);
 }
 
-int launch_scene_children(const MprlPlanner* pl, const float* child_robot, const float* humans_next, int P, int H,
-                          float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c) {
     const RglGraph& g = pl->value_graph;
-    const int A = pl->num_actions, N = H + 1;
-    if (!scene_kernel_covers(g, N) || head_variant(pl->value_head) < 0 || !workspace ||
-        workspace_bytes < scene_children_workspace_bytes(P, A, H))
+    const int P = c.P, A = c.A, H = c.H, N = H + 1;
+    if (!scene_kernel_covers(g, N) || head_variant(pl->value_head) < 0 || !c.workspace ||
+        c.workspace_bytes < scene_children_workspace_bytes(P, A, H))
         return 1;
-    float* x0_rows = (float*)workspace;                      // [P*A][32]
+    float* x0_rows = (float*)c.workspace;                    // [P*A][32]
     float* xh_rows = x0_rows + (size_t)P * A * XD;           // [P][H][32]
     float* rows = xh_rows + (size_t)P * H * XD;              // [P*A][64]
-    int rc = run_scene_kernels(g, nullptr, child_robot, humans_next, A, P * A, H, nullptr, rows, x0_rows, xh_rows, nullptr, stream);
+    int rc = run_scene_kernels(g, nullptr, c.child_robot, c.humans_next, A, P * A, H, nullptr, rows, x0_rows, xh_rows, nullptr, c.stream);
     if (rc) return rc;
-    return launch_head_rows(&g, &pl->value_head, rows, P * A, child_value, stream);
+    return launch_head_rows(&g, &pl->value_head, rows, P * A, c.child_value, c.stream);
 }
 
 }  // namespace rgl

@@ -6,49 +6,10 @@
 #include "rgl_children.h"
 #include "rgl_mlp_chain.h"
 
+using rgl::LevelPrologue;      // rgl_search_args.h
+using rgl::SceneArgs;
+
 namespace {
-
-struct SceneArgs {
-    // EMB kernels (few scenes: the embedding launch would cost more than its work): raw state rows + the two embedding MLPs
-    const float* robot_rows;           // [P][9]
-    const float* human_rows;           // [n_crowds][H][5]
-    const float *er_w1, *er_b1, *er_w2, *er_b2;      // w_r, k-major [9][64], [64], [64][32], [32]
-    const float *eh_w1, *eh_b1, *eh_w2, *eh_b2;      // w_h
-    int off_er, off_eh;                // LDS: fragment sets of the two MLPs (kRowMlpSetFloats each)
-    int bx;                            // launch the bf16 six-term (BX) form: the WEIGHT products (Wa, W_l, motion head) as layer_mfma_b6
-                                       // over a packed image of three-piece fragments (RGL_CONTRACT_BF16X6); S and A H stay f32
-    int ws_stride;                     // floats between the layer matrices in the LDS image
-    int image_floats;                  // BX: floats of the packed image
-    int off_rows;                      // WGE (the level prologue): LDS row buffer of a chunk of parents -- [crowd][H][32] human embeddings
-                                       // of the chunk's distinct crowds (at most chunk_crowds), then at off_rows + chunk_crowds H 32 its
-                                       // [parent][32] robot rows.  (This int and chunk_crowds sit where the struct had padding: the
-                                       // scene kernels' kernel arguments keep their size and offsets.)
-    const float* image;                // BX: the weight image in this kernel's LDS layout (pack_scene_image)
-    const float* xh_rows;              // [n_crowds][H][32]  human embeddings
-    const float* x0_rows;              // [P][32]            robot embeddings
-    int crowds_per;                    // scene s uses crowd s / crowds_per
-    const float* wa;                   // [32][32]
-    const float* Ws[RGL_MAX_GCN_LAYERS];
-    int L, skip;
-    int sim;                           // SIM_* row normalisation
-    int chunk_crowds;                  // WGE: most distinct crowds of a chunk (prologue_chunk_end)
-    const float *wm1, *bm1, *wm2, *bm2;   // motion head, k-major [32][64], [64], [64][5], [5]
-    float* humans_next;                // [P][H][5]   (state predictor)
-    float* rows_out;                   // null, or [P][64]: value mode -- rows [ (A H_{L-1})[robot] | H_{L-1}[robot] ] for robot_head_kernel
-    int layerwise;                     // adjacency recomputed from H_l in every layer (graph_model.py:119-122)
-    const float *wc1, *bc1, *wc2, *bc2;   // concatenation: pair MLP, k-major [64][64], [64], [64][1], [1]
-    int off_wc1, off_bc1, off_wc2;
-    int P, H, N;
-    int off_wa, off_ws, off_wm1, off_bm1, off_wm2, off_bm2, off_wave, wave_stride;
-};
-
-// The state predictor and the reward / next-state work of a tree level, as the fused children kernel's prologue runs them for the
-// parents each workgroup owns (RGL_LEVEL_PROLOGUE): filled by level_prologue_args (rgl_scene.hip), handed opaquely with its size.
-struct LevelPrologue {
-    SceneArgs scene;          // unsplit BX + EMB form: 8 slots, embeddings inside, LDS offsets from the prologue's scene base
-    ChildrenArgs children;
-    int scene_floats;         // LDS floats of the scene region (image, embedding sets, wave slots)
-};
 
 constexpr int M2LD = 20;   // LDS row stride of the [64][5 -> 16] motion output layer (4*M2LD % 32 == 16)
 

@@ -8,39 +8,13 @@
 #include "rgl_common.h"
 #include "rgl_mfma.h"
 
+using rgl::TailArgs;      // rgl_search_args.h
+using rgl::TailLevel;
+
 namespace {
 
 constexpr int kMaxSparseWidth = 16;     // sparse (one action per group) searches: widest clipping the select step supports
 constexpr int kRootLanes = 16;          // lanes that score the kept actions of one root side by side (tail_root)
-
-struct TailLevel {
-    const float* reward;      // [P][A]
-    const float* child_value; // [P][A]   V(child)
-    int* keep;                // [P][W]
-    float* backup;            // [P][W]
-    int* best_slot;           // [P]
-    int P;
-};
-
-struct TailArgs {
-    int enabled;              // 0: the kernel has no tail work (stand-alone value_children calls)
-    int level, D, A, W, clip, sparse;
-    float gamma_f;
-    const int* groups;        // [A] or null
-    const float* child_robot; // this level [P][A][9]
-    float* value1;            // this level [P][A]
-    const float* reward_sel;  // null, or [P][A]: the rewards THIS level's selection uses instead of lv[level].reward (joint-state
-                              // roots: upstream's root action_clip reads the tensor state, the root values the JointState)
-    float* next_robot;        // next level's robot rows [P*W][9]; null at the deepest level
-    TailLevel lv[8];
-    int chain;                // deepest level only: the launch also runs the back-up steps of the levels above and the root step
-                              // (every workgroup owns the parents of whole roots)
-    int B;
-    int* best_action;         // [B]
-    float* best_value;        // [B]
-    float* root_values;       // [B][W] or null
-    int* root_kept;           // [B][W] or null
-};
 
 __device__ __forceinline__ int tail_fallback(const int* kl, int k) { return k > 0 ? kl[k - 1] : 0; }
 

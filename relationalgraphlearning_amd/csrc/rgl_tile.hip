@@ -642,19 +642,18 @@ int launch_children(const ChildPlan& pl, hipStream_t st) {
 namespace rgl {
 
 // 1 = outside this kernel's envelope
-int launch_tile_children(const RglGraph* g, int P, int A, int H, const float* child_robot, const float* humans_next,
-                         float* rows_out, hipStream_t stream) {
-    ChildPlan cp = plan_children(*g, P, A, H);
+int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_out) {
+    ChildPlan cp = plan_children(*g, c.P, c.A, c.H);
     if (!cp.ok) return 1;
-    cp.a.child_robot = child_robot;
-    cp.a.humans = humans_next;
+    cp.a.child_robot = c.child_robot;
+    cp.a.humans = c.humans_next;
     cp.a.rows_out = rows_out;
     switch (cp.ks_bucket) {
-        case 2: return launch_children<2>(cp, stream);
-        case 5: return launch_children<5>(cp, stream);
-        case 8: return launch_children<8>(cp, stream);
-        case 13: return launch_children<13>(cp, stream);
-        default: return launch_children<16>(cp, stream);
+        case 2: return launch_children<2>(cp, c.stream);
+        case 5: return launch_children<5>(cp, c.stream);
+        case 8: return launch_children<8>(cp, c.stream);
+        case 13: return launch_children<13>(cp, c.stream);
+        default: return launch_children<16>(cp, c.stream);
     }
 }
 

@@ -188,7 +188,7 @@ int launch_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* 
                          hipStream_t st) {
     const bool has_v = vh && vh->n_layers > 0 && value_out, has_m = mh && mh->n_layers > 0 && humans_next;
     if (!graph || !workspace || !tiles_cover(*graph, H) || S < 1 || spc < 1 || S % spc) return 1;
-    if (env_int("RGL_TILES_FORWARD", 1) == 0) return 1;          // measurements: the general kernel instead
+    if (tiles_forward_mode() == 0) return 1;          // measurements: the general kernel instead
     if (workspace_bytes < tiles_forward_workspace_bytes(graph, has_v ? vh : nullptr, has_m ? mh : nullptr, S, spc, H, H_out != nullptr))
         return 1;
     const RglGraph& g = *graph;
@@ -259,7 +259,7 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
                          float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice) {
     // RGL_BACKWARD_MFMA = 0: never, 1: whenever the structure allows; default: by batch size, and whenever the per-scene kernel cannot
     // hold a scene in LDS (only_choice)
-    const int mode = env_int("RGL_BACKWARD_MFMA", -1);
+    const int mode = backward_mfma_mode();
     if (mode == 0) return 1;
     if (mode < 1 && !only_choice && S < env_int("RGL_BACKWARD_MFMA_MIN", 256)) {
         // Below the threshold the pipeline's device time is still the shorter one (84 vs 94 us at 100 scenes of 6 nodes, 95 vs 125 us
@@ -411,7 +411,7 @@ int launch_backward_mfma(const RglGraph* graph, const RglMlp* vh, const RglMlp* 
                          float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice) {
     const int rc = backward_tiles(graph, vh, mh, robot, humans, S, H, detach_graph, d_value, d_humans_next, d_H, grad_out, workspace,
                                   workspace_bytes, st, only_choice);
-    return (rc == 1 && env_int("RGL_BACKWARD_MFMA", -1) == 2) ? RGL_ERR_BAD_MODE : rc;
+    return (rc == 1 && backward_mfma_mode() == 2) ? RGL_ERR_BAD_MODE : rc;
 }
 
 }  // namespace rgl

@@ -260,14 +260,22 @@ inline int plan_levels(const MprlPlanner& pl, int B, int H, LevelLayout* lv, lon
     return RGL_OK;
 }
 
+// The action table and the kinematics of a planner.  Path M reports a missing table as RGL_ERR_NULL, after the kinematics; path G
+// (`path_g`) as a shape error, before them.
+inline int validate_actions(int num_actions, const double* actions, int kinematics, bool path_g) {
+    if (num_actions < 1 || num_actions > RGL_MAX_ACTIONS || (path_g && !actions)) return RGL_ERR_BAD_SHAPE;
+    if (kinematics != RGL_HOLONOMIC && kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
+    return actions ? RGL_OK : RGL_ERR_NULL;
+}
+
 inline int validate_planner(const MprlPlanner& pl, int H) {
-    if (pl.num_actions < 1 || pl.num_actions > RGL_MAX_ACTIONS) return RGL_ERR_BAD_SHAPE;
+    // (an action count out of range is a shape error like the two below: which of them answers first does not show)
     if (pl.planning_depth < 1 || pl.planning_depth > 8) return RGL_ERR_BAD_SHAPE;
     if (pl.do_action_clip && (pl.planning_width < 1 || pl.planning_width > pl.num_actions)) return RGL_ERR_BAD_SHAPE;
-    if (pl.kinematics != RGL_HOLONOMIC && pl.kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
-    if (!pl.actions) return RGL_ERR_NULL;
+    int rc = validate_actions(pl.num_actions, pl.actions, pl.kinematics, false);
+    if (rc) return rc;
     if (pl.do_action_clip && pl.sparse_search && !pl.action_groups) return RGL_ERR_NULL;
-    int rc = rgl::validate_graph(pl.value_graph, H);
+    rc = rgl::validate_graph(pl.value_graph, H);
     if (rc) return rc;
     rc = rgl::validate_mlp(pl.value_head, pl.value_graph.x_dim, 1);
     if (rc) return rc;
@@ -282,36 +290,42 @@ inline int validate_planner(const MprlPlanner& pl, int H) {
     return RGL_OK;
 }
 
-// One level: steps 1-3 of the header comment of mprl_expand_f32.
-int expand_level(const MprlPlanner& pl, const float* robot, const float* humans, int humans_per, int P, int H, int joint,
-                 float* humans_next, float* child_robot, float* reward, float* child_value, void* scratch,
-                 size_t scratch_bytes, hipStream_t st, int image_ready = 0, const TailArgs* tail = nullptr,
-                 int* tail_done = nullptr, const float* sp_image = nullptr, hipEvent_t before_children = nullptr,
-                 float* reward_clip = nullptr) {
-    const int A = pl.num_actions;
+// The reward / next-state work of P parents (mprl_children_kernel and the launches that carry it): whole-level arrays
+inline ChildrenArgs children_args_for(const MprlPlanner& pl, const float* robot, const float* humans, int humans_per, int P, int H,
+                                      int joint, float* child_robot, float* reward, float* reward_clip) {
     ChildrenArgs ca;
     ca.reward_clip = reward_clip;
     ca.robot = robot; ca.humans = humans; ca.humans_per = humans_per; ca.actions = pl.actions;
-    ca.P = P; ca.H = H; ca.A = A; ca.kinematics = pl.kinematics; ca.dt = pl.time_step; ca.joint = joint;
+    ca.P = P; ca.H = H; ca.A = pl.num_actions; ca.kinematics = pl.kinematics; ca.dt = pl.time_step; ca.joint = joint;
     ca.child_robot = child_robot; ca.reward = reward;
     ca.v_max = pl.action_speed_bound > 0.0 ? (float)pl.action_speed_bound * 1.0001f : 0.f;
     ca.p_base = ca.c_base = 0;
     const bool roots64 = joint && humans_per == 1 && pl.root_robot_f64 && pl.root_humans_f64;
     ca.robot64 = roots64 ? pl.root_robot_f64 : nullptr;
     ca.humans64 = roots64 ? pl.root_humans_f64 : nullptr;
+    return ca;
+}
+
+// One level: steps 1-3 of the header comment of mprl_expand_f32.  `ca`: the level's parents and their reward / next-state work;
+// `vc`: the value-of-children call behind it (vc.humans_next = humans_next); `before_children`: null, or an event of a traced search
+int expand_level(const MprlPlanner& pl, const ChildrenArgs& ca, float* humans_next, const rgl::ChildrenCall& vc, const float* sp_image,
+                 hipEvent_t before_children) {
+    const float* humans = ca.humans;
+    const int humans_per = ca.humans_per, P = ca.P, H = ca.H;
+    hipStream_t st = vc.stream;
     int children_done = 0;              // set when the state predictor's scene kernel ran them on its extra workgroups
     // The level as ONE launch where the fused children kernel's prologue form covers it (bf16x6, 17..20-node crowds, softmax
     // similarity): each workgroup runs the state predictor and the reward / next-state pairs of the parents it owns, then their
     // children.  Traced searches keep the three launches (predictor_ms / children_ms).  RGL_LEVEL_PROLOGUE=0: the three launches.
-    static const bool prologue_on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
     LevelPrologue lp;
-    const bool fold = prologue_on && !before_children &&
-                      rgl::level_prologue_args(&pl, robot, humans, humans_per, P, H, humans_next, sp_image, &ca, sizeof(ca), &lp,
-                                               sizeof(lp)) == 0 &&
-                      rgl::fused_prologue_fits(&pl, P, H, scratch_bytes, lp.scene_floats);
-    if (fold)
-        return rgl::launch_value_children(&pl, child_robot, humans_next, P, H, child_value, scratch, scratch_bytes, st, image_ready,
-                                          tail, tail ? sizeof(TailArgs) : 0, tail_done, &lp, sizeof(lp));
+    const bool fold = level_prologue_enabled() && !before_children &&
+                      rgl::level_prologue_args(&pl, ca, humans_next, sp_image, &lp) == 0 &&
+                      rgl::fused_prologue_fits(&pl, P, H, vc.workspace_bytes, lp.scene_floats);
+    if (fold) {
+        rgl::ChildrenCall folded = vc;
+        folded.prologue = &lp;
+        return rgl::launch_value_children(&pl, folded);
+    }
     // (Round 6: the reward work inside the children launch -- every workgroup for the parents it owns, in its prologue under the
     // weight image's DMA, inputs staged in LDS -- was built and measured: the embedding launch drops from 13.6 / 15.6 to 7.9 / 7.3 us,
     // the children launches grow by 7.3 / 5.9: 277.6 against 279.0 us per 2048-root step, not worth a second home for that code;
@@ -330,17 +344,26 @@ int expand_level(const MprlPlanner& pl, const float* robot, const float* humans,
         }
         RGL_LAUNCH_CHECK();
     } else {
-        int rc = rgl::launch_predict_humans(&pl, robot, humans, humans_per, P, H, humans_next, scratch, scratch_bytes, st,
-                                            &ca, sizeof(ca), &children_done, sp_image);
+        int rc = rgl::launch_predict_humans(&pl, ca, humans_next, vc.workspace, vc.workspace_bytes, st, &children_done, sp_image);
         if (rc) return rc;
     }
     if (!children_done) {
-        hipLaunchKernelGGL(mprl_children_kernel, grid_for((long long)P * A), dim3(kBlock), 0, st, ca);
+        hipLaunchKernelGGL(mprl_children_kernel, grid_for((long long)P * ca.A), dim3(kBlock), 0, st, ca);
         RGL_LAUNCH_CHECK();
     }
     if (before_children) RGL_HIP_TRY(hipEventRecord(before_children, st));     // traced searches: state predictor | children
-    return rgl::launch_value_children(&pl, child_robot, humans_next, P, H, child_value, scratch, scratch_bytes, st, image_ready,
-                                      tail, tail ? sizeof(TailArgs) : 0, tail_done);
+    return rgl::launch_value_children(&pl, vc);
+}
+
+// the value-of-children call of P parents of this planner: no tail, no image in the workspace
+inline rgl::ChildrenCall children_call_for(const MprlPlanner& pl, const float* child_robot, const float* humans_next, int P, int H,
+                                           float* child_value, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    rgl::ChildrenCall c{};
+    c.child_robot = child_robot; c.humans_next = humans_next; c.child_value = child_value;
+    c.P = P; c.A = pl.num_actions; c.H = H;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.image = pl.children_image;
+    return c;
 }
 
 }  // namespace
@@ -355,8 +378,9 @@ extern "C" int mprl_expand_f32(const MprlPlanner* planner, const float* robot, c
     if (rc) return rc;
     if (P == 0) return RGL_OK;
     hipStream_t st = (hipStream_t)stream;
-    rc = expand_level(*planner, robot, humans, 1, P, H, parents_are_joint_states, humans_next, child_robot, reward,
-                      child_value, workspace, workspace_bytes, st, 0, nullptr, nullptr, planner->predictor_image);
+    rc = expand_level(*planner, children_args_for(*planner, robot, humans, 1, P, H, parents_are_joint_states, child_robot, reward, nullptr),
+                      humans_next, children_call_for(*planner, child_robot, humans_next, P, H, child_value, workspace, workspace_bytes, st),
+                      planner->predictor_image, nullptr);
     if (rc) return rc;
     if (value1) {
         const long long n = (long long)P * planner->num_actions;
@@ -380,8 +404,8 @@ extern "C" int mprl_value_children_f32(const MprlPlanner* planner, const float* 
     int rc = validate_planner(*planner, H);
     if (rc) return rc;
     if (P == 0) return RGL_OK;
-    return rgl::launch_value_children(planner, child_robot, humans_next, P, H, child_value, workspace, workspace_bytes,
-                                      (hipStream_t)stream);
+    return rgl::launch_value_children(planner, children_call_for(*planner, child_robot, humans_next, P, H, child_value, workspace,
+                                                                 workspace_bytes, (hipStream_t)stream));
 }
 
 extern "C" size_t mprl_predictor_image_bytes(const MprlPlanner* planner) { return rgl::scene_image_bytes(planner); }
@@ -454,8 +478,8 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
 
     // weight images of the value-of-children kernels: prepared once, every level copies them into LDS (0 = prepared)
     // (or handed in by the caller, packed once for fixed weights: MprlPlanner::children_image)
-    const int image_mode = pl.contraction_dtype == RGL_CONTRACT_BF16X6 ? 2 : 0;
-    const int image_ready = (pl.contraction_dtype == RGL_CONTRACT_F32 || image_mode != 0) &&
+    const rgl::FusedImageMode image_mode = pl.contraction_dtype == RGL_CONTRACT_BF16X6 ? rgl::kModeBx : rgl::kModeF32;
+    const int image_ready = (pl.contraction_dtype == RGL_CONTRACT_F32 || image_mode != rgl::kModeF32) &&
                             (pl.children_image != nullptr ||
                              rgl::pack_children_images(&pl.value_graph, &pl.value_head, (int)lv[D - 1].P, A, H, ws + scratch_off,
                                                        (size_t)scratch_bytes, st, image_mode) == 0);
@@ -496,10 +520,13 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
         tail.reward_sel = reward_clip;
         int tail_done = 0;           // 1: the children kernel selected for its parents; 2: ... and finished the search (deepest level)
         if (events) RGL_HIP_TRY(hipEventRecord((hipEvent_t)events[3 * l], st));
-        rc = expand_level(pl, pr, ph, humans_per, P, H, l == 0 ? roots_are_joint_states : 0,
-                          (float*)(ws + L.humans_next), (float*)(ws + L.child_robot), (float*)(ws + L.reward),
-                          (float*)(ws + L.child_value), ws + scratch_off, (size_t)scratch_bytes, st, image_ready, &tail, &tail_done,
-                          sp_image, events ? (hipEvent_t)events[3 * l + 1] : nullptr, reward_clip);
+        float* humans_next = (float*)(ws + L.humans_next);
+        rgl::ChildrenCall vc = children_call_for(pl, tail.child_robot, humans_next, P, H, (float*)(ws + L.child_value), ws + scratch_off,
+                                                 (size_t)scratch_bytes, st);
+        vc.image_ready = image_ready; vc.tail = &tail; vc.tail_done = &tail_done;
+        rc = expand_level(pl, children_args_for(pl, pr, ph, humans_per, P, H, l == 0 ? roots_are_joint_states : 0,
+                                                (float*)(ws + L.child_robot), (float*)(ws + L.reward), reward_clip),
+                          humans_next, vc, sp_image, events ? (hipEvent_t)events[3 * l + 1] : nullptr);
         if (rc) return rc;
         if (!tail_done) {
             // the deepest level's selection also writes the leaf values and (below the root) does its own back-up step
@@ -565,20 +592,10 @@ extern "C" int mprl_estimate_reward_f32(const MprlPlanner* planner, const float*
     if (!planner || !robot || !humans || !child_robot || !reward) return RGL_ERR_NULL;
     if (P < 0 || H < 1 || H + 1 > RGL_MAX_NODES) return RGL_ERR_BAD_SHAPE;
     const MprlPlanner& pl = *planner;
-    if (pl.num_actions < 1 || pl.num_actions > RGL_MAX_ACTIONS) return RGL_ERR_BAD_SHAPE;
-    if (pl.kinematics != RGL_HOLONOMIC && pl.kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
-    if (!pl.actions) return RGL_ERR_NULL;
+    const int rc = validate_actions(pl.num_actions, pl.actions, pl.kinematics, false);
+    if (rc) return rc;
     if (P == 0) return RGL_OK;
-    ChildrenArgs ca;
-    ca.reward_clip = nullptr;
-    ca.robot = robot; ca.humans = humans; ca.humans_per = 1; ca.actions = pl.actions;
-    ca.P = P; ca.H = H; ca.A = pl.num_actions; ca.kinematics = pl.kinematics; ca.dt = pl.time_step; ca.joint = parents_are_joint_states;
-    ca.child_robot = child_robot; ca.reward = reward;
-    ca.v_max = pl.action_speed_bound > 0.0 ? (float)pl.action_speed_bound * 1.0001f : 0.f;
-    ca.p_base = ca.c_base = 0;
-    const bool roots64 = parents_are_joint_states && pl.root_robot_f64 && pl.root_humans_f64;
-    ca.robot64 = roots64 ? pl.root_robot_f64 : nullptr;
-    ca.humans64 = roots64 ? pl.root_humans_f64 : nullptr;
+    const ChildrenArgs ca = children_args_for(pl, robot, humans, 1, P, H, parents_are_joint_states, child_robot, reward, nullptr);
     hipLaunchKernelGGL(mprl_children_kernel, grid_for((long long)P * pl.num_actions), dim3(kBlock), 0, (hipStream_t)stream, ca);
     RGL_LAUNCH_CHECK();
     return RGL_OK;
@@ -631,23 +648,26 @@ extern "C" int gcn_rotate_f32(const float* joint14, float* rotated13, int n_rows
     return RGL_OK;
 }
 
+static int launch_gcn_prepare(const GcnPlanner& pl, const float* robot, const float* humans, int B, int H, float* self6, float* hum7,
+                              float* reward, hipStream_t st) {
+    const long long S = (long long)B * pl.num_actions;
+    const int prep_threads = (H >= kBlock ? 1 : kBlock / H) * H;        // whole (root, action) groups per workgroup
+    const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;
+    hipLaunchKernelGGL(gcn_prepare_kernel, grid_for(S * H, prep_threads), dim3(prep_threads), prep_threads * sizeof(double), st, robot,
+                       humans, r64 ? pl.root_robot_f64 : nullptr, r64 ? pl.root_humans_f64 : nullptr, pl.actions, B, H, pl.num_actions,
+                       pl.kinematics, pl.time_step, self6, hum7, reward);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}
+
 // propagate + rotate + compute_reward for the B x A candidate scenes of a one-step search on their own (ABI 5): the first launch of
 // gcn_predict_f32 (cadrl.py:113-138,241-276, multi_human_rl.py:46-51,73-96), exported for GCN.compute_reward / tests
 extern "C" int gcn_prepare_f32(const GcnPlanner* planner, const float* robot, const float* humans, int B, int H,
                                float* self6, float* hum7, float* reward, rgl_stream_t stream) {
     if (!planner || !robot || !humans || !self6 || !hum7 || !reward) return RGL_ERR_NULL;
     if (B < 1 || H < 1 || H + 1 > RGL_MAX_NODES) return RGL_ERR_BAD_SHAPE;
-    const GcnPlanner& pl = *planner;
-    if (pl.num_actions < 1 || pl.num_actions > RGL_MAX_ACTIONS || !pl.actions) return RGL_ERR_BAD_SHAPE;
-    if (pl.kinematics != RGL_HOLONOMIC && pl.kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
-    const long long S = (long long)B * pl.num_actions;
-    const int prep_threads = (H >= kBlock ? 1 : kBlock / H) * H;        // whole (root, action) groups per workgroup
-    const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;
-    hipLaunchKernelGGL(gcn_prepare_kernel, grid_for(S * H, prep_threads), dim3(prep_threads), prep_threads * sizeof(double),
-                       (hipStream_t)stream, robot, humans, r64 ? pl.root_robot_f64 : nullptr, r64 ? pl.root_humans_f64 : nullptr,
-                       pl.actions, B, H, pl.num_actions, pl.kinematics, pl.time_step, self6, hum7, reward);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    const int rc = validate_actions(planner->num_actions, planner->actions, planner->kinematics, true);
+    return rc ? rc : launch_gcn_prepare(*planner, robot, humans, B, H, self6, hum7, reward, (hipStream_t)stream);
 }
 
 constexpr long long kGcnImageBytes = 64 * 1024;      // >= scene_image_bytes_for(): Wa + 4 layer matrices + motion-head slots as 6-byte weights
@@ -667,9 +687,9 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
     if (!planner || !robot || !humans || !workspace || !action_values || !best_action) return RGL_ERR_NULL;
     if (B < 1) return RGL_ERR_BAD_SHAPE;
     const GcnPlanner& pl = *planner;
-    if (pl.num_actions < 1 || pl.num_actions > RGL_MAX_ACTIONS || !pl.actions) return RGL_ERR_BAD_SHAPE;
-    if (pl.kinematics != RGL_HOLONOMIC && pl.kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
-    int rc = rgl::validate_graph(pl.graph, H);
+    int rc = validate_actions(pl.num_actions, pl.actions, pl.kinematics, true);
+    if (rc) return rc;
+    rc = rgl::validate_graph(pl.graph, H);
     if (rc) return rc;
     if (pl.graph.w_r.dims[0] != 6 || pl.graph.w_h.dims[0] != 7) return RGL_ERR_BAD_SHAPE;
     rc = rgl::validate_mlp(pl.value_head, pl.graph.x_dim, 1);
@@ -696,12 +716,8 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
             if (rgl::pack_scene_image_for(pl.graph, nullptr, img, st) == RGL_OK) rows_image = img;
         }
     }
-    const int prep_threads = (H >= kBlock ? 1 : kBlock / H) * H;        // whole (root, action) groups per workgroup
-    hipLaunchKernelGGL(gcn_prepare_kernel, grid_for(S * H, prep_threads), dim3(prep_threads), prep_threads * sizeof(double), st, robot, humans,
-                       pl.root_robot_f64 && pl.root_humans_f64 ? pl.root_robot_f64 : nullptr,
-                       pl.root_robot_f64 && pl.root_humans_f64 ? pl.root_humans_f64 : nullptr, pl.actions, B, H, A,
-                       pl.kinematics, pl.time_step, self6, hum7, reward);
-    RGL_LAUNCH_CHECK();
+    rc = launch_gcn_prepare(pl, robot, humans, B, H, self6, hum7, reward, st);
+    if (rc) return rc;
     // the B x A rotated scenes: one wave per scene on the MFMA kernel where it covers the model (the shipped ValueNetwork: 6 / 7
     // inputs, 64-32 embeddings, head 150-100-100-1), else the general kernel
     rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, fwd_ws, fwd_bytes,
@@ -710,8 +726,7 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
         rc = rgl::launch_tiles_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, value, nullptr, fwd_ws,
                                        fwd_bytes, st);
     if (rc == 1) {
-        const char* e = getenv("RGL_REQUIRE_MFMA_FORWARD");          // tests: refuse instead of running the general VALU kernel
-        if (e && e[0] == '1') return RGL_ERR_BAD_MODE;
+        if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
         rc = rgl::launch_generic_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, nullptr, value,
                                          nullptr, st);
     }

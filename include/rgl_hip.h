@@ -376,6 +376,36 @@ typedef struct RglPrologueEmbeddingPlan {
 } RglPrologueEmbeddingPlan;
 int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, int H, int crowds_per, int unit, RglPrologueEmbeddingPlan* plan);
 
+/* rgl_plan_deep_children (ABI 8, additive) -- whether a stand-alone mprl_value_children_f32 call for P parents (crowds of H humans,
+ * planner->num_actions children each, a workspace of mprl_value_children_workspace_bytes) reaches the shared-crowd deep kernel
+ * (children_deep_kernel<NT, F16, SKIP, SOFT, T4> of rgl_deep.hip: three-layer graphs, and two-layer graphs beyond 32 nodes), and in
+ * which form.  The answer comes from the functions the launcher itself calls, asked in the launcher's order: the fused and the
+ * rank-1 kernel first, then the deep kernel's own plan.  HOST ONLY: no device call, no launch; reads the dimensions and modes of
+ * `planner` (no pointer of it is read) and the process's RGL_DEEP_T4, RGL_DEEP_FUSE_HEAD, RGL_CHILDREN_TILE_KERNEL,
+ * RGL_FORCE_GENERIC and RGL_FUSED_* settings (once each).  image_at_hand: the call has a packed value-estimator image
+ * (MprlPlanner.children_image, or the search's own) -- what stage 2 inside the launch needs.
+ *   covered            0: another kernel takes the call, or none of this kind does (the other fields are 0 then) -- two layers
+ *                      and at most 32 nodes (rank-1 / fused), more than 64 nodes or 96 children, a similarity outside the five
+ *                      row normalisations below, a layerwise graph, embeddings or x_dim outside the shipped shapes, tables
+ *                      beyond a CU's LDS (the tile kernel answers), f16 without three layers or a softmax similarity (the call
+ *                      answers RGL_ERR_BAD_MODE), RGL_CHILDREN_TILE_KERNEL=1
+ *   node_tiles         NT = ceil(N / 16), N = H + 1;   child_tiles CT = ceil(A / 16): the crowd waves join the child tiles of
+ *                      phases A and B when CT > 8 - NT;   table_stride TLD: row stride of the per-child tables;   layers L: 2 | 3
+ *   norm               0 softmax (embedded_gaussian, gaussian), 1 squared, 2 equal_attention, 3 diagonal
+ *   f16, skip, t4      the instantiation: f16-input MFMA for layer 1's dense products; skip connections; the last node tile (at
+ *                      most four valid nodes) on the 4 x 4 x 1 MFMA
+ *   fuse_head          1: stage 2 runs inside the launch and workgroup b owns the parents [b k, (b + 1) k), k = parents_per_wg
+ *                      (a search's level may raise k to whole roots); 0: workgroup b walks parents b, b + grid, .. and
+ *                      robot_head_kernel follows (parents_per_wg = 1)
+ *   grid               workgroups;   workgroups_per_cu 1 | 2;   lds_bytes dynamic LDS of a workgroup
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (P or H < 1). */
+typedef struct RglDeepChildrenPlan {
+    int covered, node_tiles, child_tiles, table_stride, layers, norm, f16, skip, t4, fuse_head, parents_per_wg, grid;
+    int workgroups_per_cu, reserved;
+    size_t lds_bytes;
+} RglDeepChildrenPlan;
+int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan);
+
 /* Bytes of the weight image above; 0 when the configuration has no image-based children kernel (the searches then ignore
  * `children_image`).  Depends on the architecture only (not on the weights, P, A or H).  Round 4: also offered for three-layer
  * graphs and crowds beyond 32 agents with the shipped embedding / head shapes (f32 layout): there the

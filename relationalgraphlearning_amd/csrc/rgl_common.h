@@ -77,6 +77,9 @@ int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_
 int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_out, int f16, const RglMlp* head,
                          int* head_done);                                                                           // rgl_deep.hip
 int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_out);                                // rgl_tile.hip
+// host only, no launch: whether the two kernels asked before the deep one take a call of these sizes (their own plans' answers)
+bool rank1_children_covers(const RglGraph* g, int P, int A, int H);                                                 // rgl_rank1.hip
+bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, int mode);                   // rgl_fused.hip
 // stage 2, rows [M][64] -> value; for the rows of a call's P * A children (launch_head_children) the head kernel's workgroups own
 // whole parents and run the call's tail for them (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
 int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value, hipStream_t stream);   // rgl_head.hip

@@ -838,18 +838,44 @@ inline DeepPlan plan_deep(const RglGraph& g, int P, int A, int H) {
     return pl;
 }
 
+// ---- the launch decisions, each made in ONE place: read by the launchers below and by rgl_plan_deep_children --------------------
+// an instantiation exists for the request: f16 contractions are built for the softmax similarities only
+inline bool deep_form_exists(const DeepPlan& pl, bool f16) { return !f16 || pl.a.sim == SIM_SOFTMAX; }
+// the T4 instantiation: plan_deep found the shape eligible (three layers, softmax, NT >= 2, RGL_DEEP_T4 not 0) and the form is f32
+inline bool deep_takes_t4(const DeepPlan& pl, bool f16) { return pl.t4 && !f16; }
+// workgroup slots a launch keeps resident
+inline int deep_slots(size_t lds_bytes) { return 256 * deep_workgroups_per_cu(lds_bytes); }
+// stage 2 inside the launch: the shipped value head, the call's packed image at hand, RGL_DEEP_FUSE_HEAD not 0
+inline bool deep_fuses_head(const RglMlp* head, bool outputs_at_hand, bool image_at_hand) {
+    static const bool fuse_off = [] { const char* e = getenv("RGL_DEEP_FUSE_HEAD"); return e && e[0] == '0'; }();
+    return head && outputs_at_hand && image_at_hand && !fuse_off && head_variant(*head) == 0;
+}
+// ... its LDS (the head's fragments take the tables' place) and, without the search's tail, the contiguous parents of a workgroup
+inline size_t deep_fused_lds_bytes(size_t lds_bytes) {
+    const size_t head_lds = (size_t)HeadLds<32, 100, 100>::total * sizeof(float);
+    return lds_bytes > head_lds ? lds_bytes : head_lds;
+}
+inline int deep_standalone_parents_per_wg(int P, size_t fused_lds_bytes) {
+    const int slots = deep_slots(fused_lds_bytes);
+    return (P + slots - 1) / slots;
+}
+// the grid: persistent workgroups striding the parents, or (head fused) one per block of parents_per_wg contiguous parents
+inline int deep_grid(const DeepPlan& pl) {
+    if (pl.a.fuse_head) return (pl.a.P + pl.a.parents_per_wg - 1) / pl.a.parents_per_wg;
+    const int slots = deep_slots(pl.lds_bytes);
+    return pl.a.P < slots ? pl.a.P : slots;
+}
+
 template <int NT, bool F16, bool SKIP, bool SOFT, bool T4 = false>
 int launch_deep_t(const DeepPlan& pl, const HeadArgs& ha, hipStream_t st) {
     if constexpr (!T4 && !F16 && SOFT && NT >= 2) {
-        if (pl.t4) return launch_deep_t<NT, F16, SKIP, SOFT, true>(pl, ha, st);      // plan_deep: eligible and its tables fit (RGL_DEEP_T4=0: never)
+        if (deep_takes_t4(pl, F16)) return launch_deep_t<NT, F16, SKIP, SOFT, true>(pl, ha, st);      // plan_deep: eligible and its tables fit (RGL_DEEP_T4=0: never)
     }
     auto kern = children_deep_kernel<NT, F16, SKIP, SOFT, T4>;
     if (pl.lds_bytes > 64 * 1024)
         RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)pl.lds_bytes));
-    const int per_cu = deep_workgroups_per_cu(pl.lds_bytes);
-    int grid = pl.a.P < 256 * per_cu ? pl.a.P : 256 * per_cu;             // persistent workgroups
-    if (pl.a.fuse_head) grid = (pl.a.P + pl.a.parents_per_wg - 1) / pl.a.parents_per_wg;      // contiguous parents per workgroup
+    const int grid = deep_grid(pl);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kDeepThreads), pl.lds_bytes, st, pl.a, ha);
     RGL_LAUNCH_CHECK();
     return RGL_OK;
@@ -858,8 +884,8 @@ int launch_deep_t(const DeepPlan& pl, const HeadArgs& ha, hipStream_t st) {
 template <int NT>
 int launch_deep_nt(const DeepPlan& pl, const HeadArgs& ha, bool f16, bool skip, hipStream_t st) {
     const bool soft = pl.a.sim == SIM_SOFTMAX;
+    if (!deep_form_exists(pl, f16)) return 1;
     if (f16) {
-        if (!soft) return 1;                      // f16 contractions are built for the softmax similarities only
         return skip ? launch_deep_t<NT, true, true, true>(pl, ha, st) : launch_deep_t<NT, true, false, true>(pl, ha, st);
     }
     if (soft) return skip ? launch_deep_t<NT, false, true, true>(pl, ha, st) : launch_deep_t<NT, false, false, true>(pl, ha, st);
@@ -892,15 +918,12 @@ int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
     pl.a.fuse_head = 0;
     pl.a.parents_per_wg = 1;
     HeadArgs ha{};
-    static const bool fuse_off = [] { const char* e = getenv("RGL_DEEP_FUSE_HEAD"); return e && e[0] == '0'; }();
-    const size_t head_lds = (size_t)HeadLds<32, 100, 100>::total * sizeof(float);
-    if (head && head_done && c.child_value && c.image && !fuse_off && head_variant(*head) == 0) {
-        const size_t lds = pl.lds_bytes > head_lds ? pl.lds_bytes : head_lds;
+    if (deep_fuses_head(head, head_done && c.child_value, c.image != nullptr)) {
+        const size_t lds = deep_fused_lds_bytes(pl.lds_bytes);
         int chain = 0;
-        head_args_for(g, head, 0, rows_out, P * A, c.child_value, c.image, c.tail, A, 256 * deep_workgroups_per_cu(lds), &ha, &chain);
+        head_args_for(g, head, 0, rows_out, P * A, c.child_value, c.image, c.tail, A, deep_slots(lds), &ha, &chain);
         if (!ha.tail.enabled) {                   // stand-alone call: no tail, the same ownership of rows
-            const int slots = 256 * deep_workgroups_per_cu(lds);
-            ha.parents_per_wg = (P + slots - 1) / slots;
+            ha.parents_per_wg = deep_standalone_parents_per_wg(P, lds);
             ha.own_rows = 1;
         }
         pl.lds_bytes = lds;
@@ -919,3 +942,46 @@ int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
 }
 
 }  // namespace rgl
+
+// What launch_value_children does for a stand-alone call of P parents with a workspace of value_children_workspace_bytes, up to the
+// point where the deep kernel would be launched: the same order of preference (rgl_fast.hip), the same functions.
+extern "C" int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan) {
+    if (!planner || !plan) return RGL_ERR_NULL;
+    if (P < 1 || H < 1) return RGL_ERR_BAD_SHAPE;
+    *plan = RglDeepChildrenPlan{};
+    const RglGraph& g = planner->value_graph;
+    const int A = planner->num_actions;
+    const bool want_f16 = planner->contraction_dtype == RGL_CONTRACT_F16;
+    const bool want_b6 = planner->contraction_dtype == RGL_CONTRACT_BF16X6;
+    if (planner->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return RGL_OK;
+    if (head_variant(planner->value_head) < 0) return RGL_OK;              // no stage-2 kernel: the call is not staged
+    if (!want_f16) {                                                       // the kernels asked before this one
+        if (rgl::fused_children_covers(&g, &planner->value_head, P, A, H, want_b6 ? rgl::kModeBx : rgl::kModeF32)) return RGL_OK;
+        if (rgl::rank1_children_covers(&g, P, A, H)) return RGL_OK;
+    }
+    if (want_f16 && g.num_layer != 3) return RGL_OK;                       // RGL_ERR_BAD_MODE in the call
+    DeepPlan pl = plan_deep(g, P, A, H);
+    if (!pl.ok || !deep_form_exists(pl, want_f16)) return RGL_OK;
+    pl.a.fuse_head = 0;
+    pl.a.parents_per_wg = 1;
+    if (deep_fuses_head(&planner->value_head, true, image_at_hand && !want_b6)) {      // (a three-piece bf16 image is not this head's)
+        pl.lds_bytes = deep_fused_lds_bytes(pl.lds_bytes);
+        pl.a.fuse_head = 1;
+        pl.a.parents_per_wg = deep_standalone_parents_per_wg(P, pl.lds_bytes);
+    }
+    plan->covered = 1;
+    plan->node_tiles = pl.NT;
+    plan->child_tiles = pl.a.CT;
+    plan->table_stride = pl.a.TLD;
+    plan->layers = pl.a.L;
+    plan->norm = pl.a.sim;
+    plan->f16 = want_f16;
+    plan->skip = g.skip_connection != 0;
+    plan->t4 = deep_takes_t4(pl, want_f16);
+    plan->fuse_head = pl.a.fuse_head;
+    plan->parents_per_wg = pl.a.parents_per_wg;
+    plan->grid = deep_grid(pl);
+    plan->workgroups_per_cu = deep_workgroups_per_cu(pl.lds_bytes);
+    plan->lds_bytes = pl.lds_bytes;
+    return RGL_OK;
+}

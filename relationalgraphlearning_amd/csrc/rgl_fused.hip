@@ -1426,6 +1426,11 @@ bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_b
     return prologue_form(plan_fused(pl->value_graph, pl->value_head, P, pl->num_actions, H, 1, kModeBx), scene_floats);
 }
 
+// host only: would launch_fused_children take the call?  (rgl_plan_deep_children)
+bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, int mode) {
+    return plan_fused(*g, *head, P, A, H, 1, mode).ok || (mode && plan_fused(*g, *head, P, A, H, 1, kModeF32).ok);      // (its f32 form)
+}
+
 }  // namespace rgl
 
 extern "C" int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, int H, int crowds_per, int unit,

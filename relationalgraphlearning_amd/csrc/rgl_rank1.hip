@@ -618,4 +618,7 @@ int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_
     return launch_rank1(rp, g->skip_connection != 0, c.stream);
 }
 
+// host only: would launch_rank1_children take the call?  (rgl_plan_deep_children)
+bool rank1_children_covers(const RglGraph* g, int P, int A, int H) { return plan_rank1(*g, P, A, H).ok; }
+
 }  // namespace rgl

@@ -84,15 +84,15 @@ bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, 
 // whole parents and run the call's tail for them (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
 int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value, hipStream_t stream);   // rgl_head.hip
 int launch_head_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, const float* rows);         // rgl_head.hip
-// the fused tile kernel (rgl_fused.hip).  Its weight image is prepared in global memory by pack_images_kernel: by the caller once per
+// the fused tile kernel (rgl_fused_kernel.hip; its planner and this driver: rgl_fused.hip).  Its weight image is prepared in global memory by pack_images_kernel: by the caller once per
 // parameter state (c.image = MprlPlanner::children_image), else once per tree search (c.image_ready = 1 on the per-level calls)
 // or by the call itself, at the END of the workspace it is given.
 // kModeBx: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
-int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode);
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode);       // rgl_fused.hip
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, FusedImageMode mode);   // P = the largest launch; 1 = the fused kernel does not apply
-size_t fused_children_workspace_bytes(int P, int A, int H);
-const float* fused_workspace_image(const void* workspace, size_t workspace_bytes);   // where pack_children_images put the image
+                         hipStream_t stream, FusedImageMode mode);   // P = the largest launch; 1 = the fused kernel does not apply   // rgl_fused_image.hip
+size_t fused_children_workspace_bytes(int P, int A, int H);                                                         // rgl_fused.hip
+const float* fused_workspace_image(const void* workspace, size_t workspace_bytes);   // where pack_children_images put the image   // rgl_fused_image.hip
 int launch_value_children(const MprlPlanner* pl, ChildrenCall c);                                                  // rgl_fast.hip
 size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);                                        // rgl_fast.hip
 // `level`: the parents and crowds, and their independent next-state / reward work; when the MFMA scene kernel runs, it executes that

@@ -25,6 +25,14 @@ __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 // Compiler-only fence: stops hipcc from hoisting every operand-fragment load of a long unrolled MFMA
 // chain to the top (which costs hundreds of VGPRs); each k-group loads its fragments right before use.
 __device__ __forceinline__ void load_fence() { asm volatile("" ::: "memory"); }
+// s_waitcnt vmcnt(0) alone: every vector-memory load of the wave has landed -- the LDS-direct b128 loads
+// (__builtin_amdgcn_global_load_lds, 16 bytes per lane) among them, which return no register the compiler could wait on.
+// gfx9 encoding of the immediate: vmcnt = bits 15:14 | 3:0, expcnt = bits 6:4, lgkmcnt = bits 11:8; 0x0F70 leaves expcnt (7) and
+// lgkmcnt (15) at their "no wait" maxima.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "device code of this library is gfx950 only: the 16-byte LDS-direct loads are gfx950 instructions, the s_waitcnt immediate is gfx9's"
+#endif
+__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 // Butterfly reductions over the four 16-lane k-groups of a wave (lanes l, l^16, l^32, l^48), on the VALU
 // (gfx950 v_permlane16_swap / v_permlane32_swap) instead of the LDS crossbar (ds_bpermute).
@@ -42,7 +50,7 @@ __device__ __forceinline__ float kgroups_sum(float x) {
 }
 // v_mfma_f32_4x4x1_16B_f32: sixteen independent 4 x 4 x 1 blocks, block = lane / 4, A row = B column = lane % 4, D register = row
 // (tools/micro/mfma_4x4.hip: layout checked on the hardware, 12 clocks per instruction against 32 for the 16 x 16 x 4 form).
-// Used where a 16-row MFMA tile would carry at most four valid rows (rgl_mlp_chain.h Partial4, rgl_fused.hip T1P, rgl_deep.hip T4).
+// Used where a 16-row MFMA tile would carry at most four valid rows (rgl_mlp_chain.h Partial4, rgl_fused_kernel.hip T1P, rgl_deep.hip T4).
 __device__ __forceinline__ f32x4 mfma4x4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 // lane (n, q) <- sum over the four k-groups of register q (see above)
 __device__ __forceinline__ float kgroups_reduce_scatter(const f32x4& p) {

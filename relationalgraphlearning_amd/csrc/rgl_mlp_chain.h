@@ -155,7 +155,7 @@ __device__ __forceinline__ void fill_matrix(float* dst, const float* __restrict_
 }
 
 // The weight image of the shipped value estimator (w_r, w_h, Wa, W1, value-head vectors and A fragments) in the LDS layout of
-// children_fused_kernel (rgl_fused.hip); pack_images_kernel writes it to global memory once per parameter state.  The two-stage pair
+// children_fused_kernel (rgl_fused_kernel.hip); pack_images_kernel writes it to global memory once per parameter state.  The two-stage pair
 // takes its parts from the same image when one is at hand: children_rank1_kernel the first `b1` floats, robot_head_kernel the rest.
 template <int IN, int OUT>
 struct HeadFragFloats {
@@ -410,6 +410,16 @@ __device__ __forceinline__ void split3_unit(f32x2 x, unsigned& H, unsigned& M, u
     M = __builtin_bit_cast(unsigned, m);
     L = __builtin_bit_cast(unsigned, l);
 }
+// ... and of ONE weight, for the packers of the weight images (frag_bf3_ld, rgl_fused_image.hip): piece pc of w --
+// 0: hi = bf16(w), 1: mid = bf16(w - hi), 2: lo = w - hi - mid (exact).  The same roundings as split3_unit, one element at a time
+// (scalar on purpose: the packers' kernels keep the code they had when each spelled the three lines out).
+__device__ __forceinline__ __bf16 split3_piece(float w, int pc) {
+    const __bf16 hi = (__bf16)w;
+    const float r1 = w - (float)hi;
+    const __bf16 mid = (__bf16)r1;
+    const __bf16 lo = (__bf16)(r1 - (float)mid);
+    return pc == 0 ? hi : (pc == 1 ? mid : lo);
+}
 
 // The D2 x D3 head layer (BxLayout) as a software pipeline (round 6).  Register budget: the kernel around it holds ~100 VGPRs of crowd
 // quantities across the tile loop; the partial output tile goes FIRST (it reads every input tile), then one chunk at a time, two
@@ -418,6 +428,11 @@ __device__ __forceinline__ void split3_unit(f32x2 x, unsigned& H, unsigned& M, u
 // while the partner wave of the SIMD cannot fill the matrix pipe's shadow (the older wave's next MFMA blocks the issue port).  So the
 // split of chunk c + 1 (44 VALU) and the fragment loads of the next pair of output tiles are issued BETWEEN the twelve MFMAs of a
 // pair of output tiles of chunk c (sched_group_barrier pins the order); only chunk 0's split stays in front.
+// RGL_BX_PIPE_WBUF (a build switch, -D): fragment buffers of the pipeline.  2: the next stage's fragments are loaded under this
+// stage's MFMAs (+24 VGPRs: 11 spill in the children kernel; -1.8 % instead of -1.2 %, profiles/r06_f_*)
+#ifndef RGL_BX_PIPE_WBUF
+#define RGL_BX_PIPE_WBUF 1
+#endif
 template <int IN, int OUT, bool BIAS>
 __device__ __forceinline__ void layer_mfma_bx(const float* frags, const f32x4 (&in)[Tiles<IN>::v], f32x4 (&out)[Tiles<OUT>::v],
                                                    int lane, const float* bias = nullptr) {
@@ -452,11 +467,7 @@ __device__ __forceinline__ void layer_mfma_bx(const float* frags, const f32x4 (&
 #pragma unroll
     for (int p = 0; p < 4; ++p) split3_unit(unit_of(0, p), H[p], M[p], L[p]);
     unsigned Hn_[4] = {0u, 0u, 0u, 0u}, Mn_[4] = {0u, 0u, 0u, 0u}, Ln_[4] = {0u, 0u, 0u, 0u};      // the next chunk's pieces, filled stage by stage
-#ifndef RGL_BX_PIPE_WBUF
-#define RGL_BX_PIPE_WBUF 1
-#endif
-    constexpr int WB = RGL_BX_PIPE_WBUF;                           // 2: the next stage's fragments are loaded under this stage's MFMAs (+24 VGPRs:
-                                                                   // 11 spill in the children kernel; -1.8 % instead of -1.2 %, profiles/r06_f_*)
+    constexpr int WB = RGL_BX_PIPE_WBUF;
     bf16x8 w[WB][2][3];                                            // [buffer][tile of the pair][piece]
     if constexpr (WB == 2) {
 #pragma unroll
@@ -682,11 +693,7 @@ __device__ __forceinline__ float frag_bf3_ld(const float* __restrict__ W, int ld
         const int e = 2 * p + k, t = 2 * c + (e >> 2);
         const int in = 16 * t + 4 * q + (e & 3);
         const float w = (t < IT && in < IN && out < n_out) ? W[in * ld + out] : 0.f;
-        const __bf16 hi = (__bf16)w;
-        const float r1 = w - (float)hi;
-        const __bf16 mid = (__bf16)r1;
-        const __bf16 lo = (__bf16)(r1 - (float)mid);
-        v[k] = pc == 0 ? hi : (pc == 1 ? mid : lo);
+        v[k] = split3_piece(w, pc);
     }
     return __builtin_bit_cast(float, v);
 }

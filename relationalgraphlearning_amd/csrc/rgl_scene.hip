@@ -371,7 +371,7 @@ int pack_scene_image_for(const RglGraph& g, const RglMlp* mh, float* image, hipS
     return RGL_OK;
 }
 
-// The level prologue of the fused children kernel (rgl_fused.hip): the state predictor's scenes of the parents a workgroup owns in the
+// The level prologue of the fused children kernel (rgl_fused_kernel.hip): the state predictor's scenes of the parents a workgroup owns in the
 // unsplit BX + EMB form of scene_body (one slot per wave, embeddings inside), and the level's reward / next-state pairs.  1 = outside
 // that form's envelope: the six-term bf16 scene kernel with two node tiles (softmax similarity, 9-wide robot state, a motion head).
 int level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& ca, float* humans_next, const float* sp_image, LevelPrologue* lp) {

@@ -1,6 +1,6 @@
 // rgl_scene_body.h -- the state predictor's scene graph forward (one scene per wave, or NT waves per scene) as a device function over
 // a range of scenes and an LDS base: the body of scene_graph_kernel (rgl_scene.hip) and of the level prologue of
-// children_fused_kernel (rgl_fused.hip), which run the same code on the same inputs and so write the same bits.
+// children_fused_kernel (rgl_fused_kernel.hip), which run the same code on the same inputs and so write the same bits.
 // Follows (reference paths): crowd_nav/policy/state_predictor.py:20-39, graph_model.py:99-130.
 #pragma once
 #include "rgl_children.h"
@@ -17,7 +17,7 @@ constexpr int M2LD = 20;   // LDS row stride of the [64][5 -> 16] motion output 
 // (ONE w_r tile of robot rows) that use at most `max_crowds` distinct crowds -- kPrologueChunkCrowds, or fewer where a predictor of
 // three or four layers leaves less LDS behind its image (fill_scene_args).  16 sibling-sharing parents (crowds_per >= 2) span at
 // most 9 crowds; at the root level (crowds_per = 1) the crowd bound cuts a chunk to 12 parents -- 16 crowds of 19 humans would be
-// 41 KB of rows, and 32 592 B lie free behind the scene region of a two-layer predictor (rgl_fused.hip proves the fit).
+// 41 KB of rows, and 32 592 B lie free behind the scene region of a two-layer predictor (rgl_fused_kernel.hip proves the fit).
 constexpr int kPrologueChunk = 16, kPrologueChunkCrowds = 12;
 // parents [c0, prologue_chunk_end) form the chunk that starts at c0: its crowds c0 / crowds_per .. (end - 1) / crowds_per
 __host__ __device__ inline int prologue_chunk_end(int c0, int end, int crowds_per, int max_crowds) {
@@ -181,7 +181,7 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.image + fl),
                                                  (__attribute__((address_space(3))) void*)(lds + c * kChunk), 16, 0, 0);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                                    // vmcnt(0): my chunks have landed (the barrier below: everyone's)
+        wait_vmcnt0();                                                         // my chunks have landed (the barrier below: everyone's)
     } else
     {   // weight image in two phases -- every global load of the thread first, then the LDS stores -- so that the whole
         // 30 KB image costs ONE L2 round trip (filling matrix by matrix cost one per matrix: ~9 us of a ~35 us launch)

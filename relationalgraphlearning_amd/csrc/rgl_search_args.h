@@ -40,6 +40,9 @@ struct TailArgs {
     int* root_kept;           // [B][W] or null
 };
 
+// LDS ints private to a wave that runs the select step (tail_select, rgl_tail.h): kept indices | V(child) | reward of a parent's actions
+constexpr int kTailLdsInts = 3 * RGL_MAX_ACTIONS;
+
 // Who owns the tail's parents: workgroups take them in blocks that are multiples of the returned unit.  At the deepest level (t.chain)
 // that is the W^level parents of one root where the launch still has `min_roots` such blocks; it then walks the whole back-up chain
 // and decides the roots (*chain = 1).  A level whose roots are single parents chains with unit 1.

@@ -1,6 +1,6 @@
 // The search's bookkeeping steps per tree node -- one-step values + top-w clipping (action_clip), the V_planning back-up and the
 // root's first-maximum -- as device functions, shared by the stand-alone kernels of rgl_tree.hip (mprl_select_kernel,
-// mprl_backup_kernel, mprl_root_kernel) and by the TAIL of children_fused_kernel (rgl_fused.hip), where the workgroup that scored
+// mprl_backup_kernel, mprl_root_kernel) and by the TAIL of children_fused_kernel (rgl_fused_kernel.hip), where the workgroup that scored
 // all 81 children of a parent goes on to select / back up / decide for the parents (and, at the deepest level, the whole roots)
 // it owns: no launch of their own, no second pass over HBM.
 // Follows crowd_nav/policy/model_predictive_rl.py:228-231 (strict '>' argmax), :242-269 (action_clip), :271-302 (V_planning).
@@ -10,6 +10,7 @@
 
 using rgl::TailArgs;      // rgl_search_args.h
 using rgl::TailLevel;
+using rgl::kTailLdsInts;
 
 namespace {
 
@@ -25,8 +26,6 @@ __device__ __forceinline__ int tail_fallback(const int* kl, int k) { return k > 
 // Written for LATENCY (in the fused kernel's tail nothing else hides it): every global load that does not depend on the selection
 // -- rewards, child values, the parent's own value one level up -- is issued up front, and what the back-up needs of the kept
 // actions comes from the LDS copy instead of a second trip to memory.
-constexpr int kTailLdsInts = 3 * RGL_MAX_ACTIONS;
-
 __device__ __forceinline__ void tail_select(const TailArgs& t, int p, int* kl) {
     const int lane = threadIdx.x & 63;
     const int A = t.A, W = t.W;

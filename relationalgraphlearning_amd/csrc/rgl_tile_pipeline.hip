@@ -21,7 +21,7 @@
 // each kernel keeps one job; everything else lives in LDS / registers.  Below RGL_BACKWARD_MFMA_MIN scenes of an eager step
 // rgl_backward.hip runs.
 //
-// (2) launch_tiles_forward chains 1., 2. and head rows forward-only for models the shipped-shape kernels (rgl_scene.hip, rgl_fused.hip,
+// (2) launch_tiles_forward chains 1., 2. and head rows forward-only for models the shipped-shape kernels (rgl_scene.hip, rgl_fused_kernel.hip,
 // ...) do not cover -- other embedding MLPs, x_dim = 64 -- instead of the general VALU kernel; sibling scenes of a rollout share
 // their crowd's embedded rows.
 //
@@ -169,7 +169,7 @@ extern "C" int rgl_plan_graph_tiles(const RglGraph* graph, int n_scenes, int H, 
 namespace rgl {
 
 // ------------------------------------------------------------------------------------------------
-// forward on the same tile kernels: models the shipped-shape MFMA kernels (rgl_scene.hip, rgl_fused.hip, ..) do not cover -- other
+// forward on the same tile kernels: models the shipped-shape MFMA kernels (rgl_scene.hip, rgl_fused_kernel.hip, ..) do not cover -- other
 // embedding MLPs (wr_dims / wh_dims), x_dim = 64 -- instead of the general VALU kernel.  0 bytes / 1 = not covered.
 //   1. mlp rows (forward): robot rows [S][X], human rows [S / spc][H][X] (sibling scenes share their crowd's rows)
 //   2. graph_kernel<.., false>: H_L -- all rows (motion head, H_out) or the robot row only (value head)

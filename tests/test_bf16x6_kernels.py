@@ -315,7 +315,8 @@ def fused_cases(C):
 
 def fused_bx_live(H, sim):
     """The fused kernel's bf16x6 forms that fit a CU's LDS: <8,1> and <20,1> for every similarity, <20,2> (N = 17..20) for the
-    softmax one only; the others (N = 17..20 with a plain-weight similarity, N = 21..32) run the f32 form on an image of their own."""
+    softmax one only; the others (N = 17..20 with a plain-weight similarity, N = 21..32) run the f32 form on an image of their own.
+    (rgl_fused.h states the same window in static_asserts on fused_form_fits, and no kernel is compiled outside it.)"""
     N = H + 1
     return N <= 16 or (N <= 20 and sim == "embedded_gaussian")
 
@@ -344,7 +345,7 @@ def children_outputs(c, dev):
 
 
 def test_fused_children_kernel_every_dealing_plan_both_modes(dev, tmp_path):
-    """B: the fused children kernel (rgl_fused.hip) under each forced dealing plan -- tiles per item G, the inline partial tile --
+    """B: the fused children kernel (rgl_fused_kernel.hip) under each forced dealing plan -- tiles per item G, the inline partial tile --
     and the cost model's own, in child processes with RGL_CHILDREN_FUSED=1 (so that f32 takes the small launches too): f32 and
     bf16x6 against float64 ValueEstimator arithmetic.  N <= 20: (a)-(c); N = 21..32: the bf16x6 request runs the f32 kernel on an
     image of its own (the larger image does not fit a CU), bit for bit."""

@@ -1,5 +1,5 @@
 """CPU emulation of the six-term bf16 product whose BOTH operands are split in registers (children_fused_kernel, BX mode:
-the crowd's S = G Xh^T and U = E Xh, the tile's robot row / column of S -- b6_block in rgl_fused.hip).
+the crowd's S = G Xh^T and U = E Xh, the tile's robot row / column of S -- b6_block in rgl_fused_kernel.hip).
 
 Each operand element x is split by round-to-nearest-even into bf16 pieces h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)
 (split3_pair); the block sums the six terms l.h, m.m, h.l, m.h, h.m, h.h (weight piece first), each one K = 32 MFMA whose

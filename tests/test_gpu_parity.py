@@ -814,7 +814,7 @@ print("OK")
 
 
 def test_fused_tile_kernel_forced(dev):
-    """The fused tile-stream kernel (rgl_fused.hip) is picked for large launches only; RGL_CHILDREN_FUSED=1 forces it for the small,
+    """The fused tile-stream kernel (rgl_fused_kernel.hip; its planner: rgl_fused.hip) is picked for large launches only; RGL_CHILDREN_FUSED=1 forces it for the small,
     odd-sized launches here (partial tiles, every register bucket, skip on/off, the plain-weight similarities, action tables whose
     size is / is not a multiple of 16) -- against the oracle, and whole searches against the two-stage pair.  Child process: the
     switch is read once."""
@@ -856,7 +856,7 @@ for H, skip, P, sim, flavour in ((19, True, 5, "embedded_gaussian", "trained"), 
     worst = max(worst, err)
     assert err < 1e-4, (H, skip, P, sim, err)
 # sharp attention: w_a scaled so that the similarities span hundreds -- the row weights' exponent differences (msh_i - S_i0) run
-# past both ends of the fp32 exp range; the packed row pass caps r = alpha / beta at e^60 (rgl_fused.hip), the oracle softmax is plain
+# past both ends of the fp32 exp range; the packed row pass caps r = alpha / beta at e^60 (rgl_fused_kernel.hip), the oracle softmax is plain
 import copy
 for scale, H, P in ((25.0, 19, 40), (-40.0, 9, 33), (300.0, 5, 17)):
     ck = copy.deepcopy(gio.checkpoint("trained", 2))

@@ -400,12 +400,12 @@ def _source_constant(path, pattern):
 def roots_per_workgroup(B, dev):
     """(fused kernel, robot_head_kernel) roots per workgroup of a D = 1 search of B roots, and the roots one pass of their tail_root
     loops holds, with the block sizes and slot counts read from the sources that set them: plan_items (rgl_fused.hip,
-    `k = (P + n_cu - 1) / n_cu`) hands ceil(P / CUs) parents to a fused workgroup of kFusedWaves waves; head_args_for
+    `k = (P + n_cu - 1) / n_cu`) hands ceil(P / CUs) parents to a fused workgroup of kFusedWaves waves (rgl_fused.h); head_args_for
     (rgl_head_body.h, `k = (P + slots - 1) / slots`) ceil(P / slots) to a head workgroup of kHeadThreads threads, slots being what
     launch_head_rows passes for the shipped head (rgl_head.hip, `hv == 0 ? 512 : 256`); tail_root scores a root on kRootLanes
     lanes (rgl_tail.h).  The kernel record (profiles/search_bookkeeping_forms.txt) shows the launches these sizes produce."""
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    fused_threads = 64 * _source_constant("rgl_fused.hip", r"constexpr int kFusedWaves = (\d+);")
+    fused_threads = 64 * _source_constant("rgl_fused.h", r"constexpr int kFusedWaves = (\d+);")
     head_threads = _source_constant("rgl_head_body.h", r"constexpr int kHeadThreads = (\d+);")
     head_slots = _source_constant("rgl_head.hip", r"hv == 0 \? (\d+) : \d+, &ha, &chain")
     lanes = _source_constant("rgl_tail.h", r"constexpr int kRootLanes = (\d+);")

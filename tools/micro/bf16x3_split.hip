@@ -1,6 +1,6 @@
 // Micro-benchmark: can an f32-EQUIVALENT contraction run on the gfx950 matrix pipe faster than the f32 MFMA?
 //
-// The workload is the value head of the children kernel as it sits in rgl_fused.hip: a wave owns a 16-child tile, the activations
+// The workload is the value head of the children kernel as it sits in rgl_fused_kernel.hip: a wave owns a 16-child tile, the activations
 // are the B operand (column = my lane's child, the D registers of the previous layer ARE the next B operand), the weights are A
 // fragments read from an LDS image every wave shares; chain 32 -> 32 -> 100 -> 100 with bias + ReLU (the 100 -> 1 row is noise).
 //

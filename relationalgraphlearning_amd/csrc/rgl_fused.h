@@ -45,6 +45,8 @@ struct FusedArgs {
     int phase_delay;              // measurements (RGL_FUSED_PHASE_DELAY): waves 4..7 start this many 512-cycle sleeps late
     int prio;                     // RGL_FUSED_PRIO: bit 1 (default) = s_setprio 2 inside the head: -0.6 % / -1.3 % at 2048 / 4096 parents; bit 0
                                   // (measurements) = static s_setprio 1 for waves 4..7: nothing (profiles/r06_c_phase_prio_ab.txt)
+    int head_early;               // RGL_FUSED_HEAD_EARLY (default 1): the waves that run out of items first score the tile-packed rows of the
+                                  // partial tiles while the others still work (0: a pass behind a workgroup barrier, one wave per tile)
     TailArgs tail;                // tail.enabled: select (+ back-up chain + root step) for the owned parents at the end
 };
 

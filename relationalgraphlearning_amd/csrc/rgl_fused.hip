@@ -240,6 +240,8 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenC
     static const int phase_delay = env_int("RGL_FUSED_PHASE_DELAY", 0), prio = env_int("RGL_FUSED_PRIO", 2);
     fp.a.phase_delay = phase_delay;
     fp.a.prio = prio;
+    static const int head_early = env_int("RGL_FUSED_HEAD_EARLY", 1);
+    fp.a.head_early = head_early;
     if (ta) {
         fp.a.tail = *ta;
         fp.a.tail.chain = chain;

@@ -425,6 +425,11 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
     constexpr int kChunksA = (LO::f_last + kChunk - 1) / kChunk, kChunksAll = (LO::scratch + kChunk - 1) / kChunk;
     static_assert(LO::scratch == FusedImage<BX>::scratch, "fused_lds_floats is written for the shipped head's image");
     int* image_arrivals = reinterpret_cast<int*>(lds + fused_lds_floats(HR, NT, SOFT, BX) - kArrivalFloats);
+    // ... and in the same granule, for the tile-packed head pass (RGL_FUSED_HEAD_EARLY, below): the rows the partial tiles have
+    // handed off so far, and the packed tiles taken so far
+    int* rows_arrivals = image_arrivals + 1;
+    int* packed_taken = image_arrivals + 2;
+    static_assert(kArrivalFloats >= 3, "three counters");
     auto image_chunk = [&](int c) {
         const int fl = c * kChunk + lane * 4;
         if (fl < LO::scratch)                                              // the last chunk is partial
@@ -468,7 +473,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
     // (the first item's state rows are requested BEFORE the image: the wait in front of the barrier covers them, and no later
     // wait for them can hold the wave until the head fragments have landed as well -- vmcnt counts in order)
     if (wave < n_items) item_loads(item_at(0));
-    if (tid == 0) *image_arrivals = 0;
+    if (tid == 0) *image_arrivals = *rows_arrivals = *packed_taken = 0;
     bool image_complete = false;                                           // wave-uniform
     if (a.image_sync) {                                                    // RGL_FUSED_IMAGE_SYNC=1 (measurements): the round-3 copy
         copy_image<LO::scratch, nthreads>(lds, a.image, tid);
@@ -713,7 +718,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         }
         __builtin_amdgcn_wave_barrier();
         load_fence();
-        PHASE_MARK(3);
+        PHASE_MARK_ALT(!full, 3);      // (the partial tile's crowd stage -- this phase and the row pass -- has counter 15)
 
         // ---------------- row pass over my 16 children -------------------------------------------------------------------
         f32x4 tp4[2] = {zero4(), zero4()};           // PK: t_c without the robot-row / skip terms, D layout (child n, features)
@@ -795,7 +800,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         }
         __builtin_amdgcn_wave_barrier();
         load_fence();
-        PHASE_MARK(4);
+        PHASE_MARK_ALT(!full, 4);
 
         // ---------------- robot row: H1_0 = relu(T_0 W1)(+x0), t_c += p00 * H1_0 ---------------------------------------
         f32x4 tin[2], hp[2];
@@ -848,6 +853,11 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
                     *reinterpret_cast<f32x4*>(out + 32 + 16 * ot + 4 * q) = hp[ot];
                 }
             }
+            if (a.head_early) {                                    // my rows have landed: one count per row, released to the workgroup
+                wait_vmcnt0();
+                asm volatile("" ::: "memory");
+                if (lane == 0) __hip_atomic_fetch_add(rows_arrivals, a.rem, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
             continue;
         }
 
@@ -865,9 +875,28 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         // Rows of this workgroup's partial tiles (its own parents, all written by waves of THIS workgroup): scored here,
         // tile-packed over parents -- 16 parents' `stop` children fill one head tile exactly, so the head never multiplies
         // padding columns and the path needs no second launch.
-        __syncthreads();
+        // Who scores them (RGL_FUSED_HEAD_EARLY): the waves that run out of items FIRST take the packed tiles, one at a time, while
+        // the others still work -- a partial tile is the first tile of its item, so the rows are there long before (rows_arrivals
+        // says when: no barrier).  Measured, the waves of a workgroup wait 21 k / 26 k cycles on average for its slowest (launches
+        // of 2048 / 4096 parents), and the pass -- 11 k cycles on ONE wave behind a barrier, the form RGL_FUSED_HEAD_EARLY=0 keeps:
+        // straight-line code that runs once per launch and is fetched as it goes, on rows that cross the barrier before their
+        // loads can start -- fits into that wait (profiles/stop_child_ab.txt).  The values do not depend on the wave that
+        // computes them.
         const int n_rows = k_b * a.rem;
-        for (int tt = wave; 16 * tt < n_rows; tt += kFusedWaves) {
+        const bool early = a.head_early != 0;
+        auto take_tile = [&]() {
+            int tt = 0;
+            if (lane == 0) tt = __hip_atomic_fetch_add(packed_taken, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return __builtin_amdgcn_readfirstlane(tt);
+        };
+        PHASE_MARK(0);
+        if (!early) __syncthreads();
+        PHASE_MARK(0);
+        for (int tt = early ? take_tile() : wave; 16 * tt < n_rows; tt = early ? take_tile() : tt + kFusedWaves) {
+            if (early) {
+                while (__hip_atomic_load(rows_arrivals, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < n_rows) __builtin_amdgcn_s_sleep(1);
+                asm volatile("" ::: "memory");
+            }
             const int i = 16 * tt + n;
             const bool valid = i < n_rows;
             const int lp = valid ? i / a.rem : 0, k = valid ? i - lp * a.rem : 0;
@@ -887,7 +916,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void children_fused_kernel(const 
         // The search's bookkeeping for the parents this workgroup owns (rgl_tail.h): every value of theirs was written by a wave
         // of this workgroup, so a workgroup barrier is all the synchronisation there is.  One wave per parent selects; at the
         // deepest level the workgroup owns the parents of whole roots and walks the back-up chain up to the root decision.
+        PHASE_MARK(7);                   // the tile-packed pass: what its waves spend on it (the others: nothing)
         __syncthreads();
+        PHASE_MARK(0);                   // ... and with the loop top, what a wave waits at the barriers behind its items
         static_assert(fused_scratch_floats(HR, NT, SOFT) >= kTailLdsInts, "the wave's scratch holds the select step's tables");
         int* kl = reinterpret_cast<int*>(WS);                    // the wave's scratch is free now
         for (int lp = wave; lp < k_b; lp += kFusedWaves) tail_select(a.tail, p_first + lp, kl);

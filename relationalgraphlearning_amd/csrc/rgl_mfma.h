@@ -93,6 +93,7 @@ __device__ __forceinline__ float relu1(float x) { return __int_as_float(max(__fl
 __device__ unsigned long long g_phase_cycles[16];
 #define PHASE_START()                                                      \
     unsigned long long phase_acc__[8] = {0, 0, 0, 0, 0, 0, 0, 0};          \
+    unsigned long long phase_alt__ = 0;                                    \
     const unsigned long long phase_rt0__ = __builtin_amdgcn_s_memrealtime(); \
     const unsigned long long phase_ct0__ = __builtin_amdgcn_s_memtime();   \
     unsigned long long phase_t0__ = __builtin_amdgcn_s_memtime()
@@ -102,10 +103,20 @@ __device__ unsigned long long g_phase_cycles[16];
         phase_acc__[idx] += now__ - phase_t0__;                            \
         phase_t0__ = now__;                                                \
     } while (0)
+// the same, into counter 15 where `alt` holds (the fused kernel: the partial tile's crowd stage apart from the full tiles')
+#define PHASE_MARK_ALT(alt, idx)                                           \
+    do {                                                                   \
+        const unsigned long long now__ = __builtin_amdgcn_s_memtime();     \
+        if (alt) phase_alt__ += now__ - phase_t0__;                        \
+        else phase_acc__[idx] += now__ - phase_t0__;                       \
+        phase_t0__ = now__;                                                \
+    } while (0)
 #define PHASE_FLUSH()                                                      \
     do {                                                                   \
-        if ((threadIdx.x & 63) == 0)                                       \
+        if ((threadIdx.x & 63) == 0) {                                     \
             for (int i__ = 0; i__ < 8; ++i__) atomicAdd(&g_phase_cycles[i__], phase_acc__[i__]); \
+            if (phase_alt__) atomicAdd(&g_phase_cycles[15], phase_alt__);  \
+        }                                                                  \
         if (threadIdx.x == 0 && blockIdx.x == 0) { /* shader clock: s_memtime ticks per 100 MHz s_memrealtime tick */ \
             atomicAdd(&g_phase_cycles[8], __builtin_amdgcn_s_memtime() - phase_ct0__);           \
             atomicAdd(&g_phase_cycles[9], __builtin_amdgcn_s_memrealtime() - phase_rt0__);       \
@@ -113,6 +124,7 @@ __device__ unsigned long long g_phase_cycles[16];
     } while (0)
 #else
 #define PHASE_MARK(idx) do { } while (0)
+#define PHASE_MARK_ALT(alt, idx) do { } while (0)
 #define PHASE_START() do { } while (0)
 #define PHASE_FLUSH() do { } while (0)
 #endif

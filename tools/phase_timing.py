@@ -4,6 +4,8 @@ make -C relationalgraphlearning_amd/csrc timing; per-wave s_memtime deltas, i.e.
 
     RGL_HIP_LIBRARY=relationalgraphlearning_amd/lib/librgl_hip_timing.so python tools/phase_timing.py
     ... python tools/phase_timing.py prologue [roots]     the level prologue of the fused children kernel (bf16x6 searches), per level
+    ... python tools/phase_timing.py stop [roots]         what the `stop` child costs in that kernel, per level: its partial tile's crowd
+                                                          stage and the tile-packed head pass (RGL_FUSED_HEAD_EARLY=0: on one wave)
 """
 import ctypes as C
 import os
@@ -64,10 +66,64 @@ def prologue_main(roots):
         print("  %-46s %9.0f" % ("total", sum(cyc) / waves))
 
 
+def search_counters(roots, reps=5):
+    """The fused kernel's 16 counters per search of a depth-1 and a depth-2 width-2 bf16x6 search of `roots` roots (prologue_main's
+    levels: the first from depth 1, the second as the difference), and their event time in ms."""
+    dev = torch.device("cuda:0")
+    raw = C.CDLL(nat.LIB_PATH)
+    read = raw.rgl_debug_read_fused_phase_cycles
+    buf = (C.c_ulonglong * 16)()
+    A.contraction = "bf16x6"
+    per_depth, ms = {}, {}
+    for depth in (1, 2):
+        A.depth = depth
+        pol = bench.make_policy(A, dev)
+        ts = pol.tree_search()
+        robot, humans = bench.synth_scenes(5, roots, A.humans)
+        r, h = robot.to(dev), humans.to(dev)
+        ts.search(r, h, roots_are_joint_states=False, want_root_values=False)
+        read(buf, 1)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            ts.search(r, h, roots_are_joint_states=False, want_root_values=False)
+        e1.record()
+        torch.cuda.synchronize()
+        read(buf, 1)
+        per_depth[depth] = [buf[i] / reps for i in range(16)]
+        ms[depth] = e0.elapsed_time(e1) / reps
+    return per_depth, ms
+
+
+def stop_main(roots):
+    """The `stop` child's two costs in the fused children kernel over a depth-1 (one launch: `roots` parents) and a depth-2 width-2
+    bf16x6 search (two launches: `roots` and 2 x `roots` parents): the crowd stage of a parent's partial tile (robot row / column of
+    S, softmax, p Xh, table, row pass: counter 15, per partial tile = per parent) next to a full tile's and its head, and the
+    tile-packed head pass -- counter 7: what the waves that score packed tiles spend on it, per workgroup and launch; counter 0: what
+    a wave spends at the loop top and waiting at the barriers behind its items (RGL_FUSED_HEAD_EARLY=0: the pass's barrier, where
+    seven waves wait for the eighth's chain, and the tail's), per wave and launch.  Counter 8 is workgroup 0's clock over its
+    launches.  A mark is an s_memtime round trip of ~400 cycles."""
+    per_depth, ms = search_counters(roots)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print("RGL_FUSED_HEAD_EARLY=%s   search: depth 1 %.4f ms, depth 2 %.4f ms (timing build)" % (
+        os.environ.get("RGL_FUSED_HEAD_EARLY", "(default)"), ms[1], ms[2]))
+    for depth, launches, parents in ((1, 1, roots), (2, 2, 3 * roots)):
+        cyc = per_depth[depth]
+        wgs = launches * min(cus, roots)
+        print("depth-%d search, %d launch(es), %d parents in all: core-clock cycles" % (depth, launches, parents))
+        print("  partial tile's crowd stage, per parent            %8.0f   (a full tile's: %.0f; its head: %.0f)" % (
+            cyc[15] / parents, (cyc[3] + cyc[4]) / (5 * parents), cyc[6] / (5 * parents)))
+        print("  tile-packed pass, per workgroup and launch        %8.0f" % (cyc[7] / wgs))
+        print("  loop top + waits at the barriers, per wave, launch %7.0f" % (cyc[0] / (8 * wgs)))
+        print("  workgroup 0's clock, per launch                   %8.0f" % (cyc[8] / launches))
+
+
 def main():
     """usage: phase_timing.py [parents] [humans layers contraction]   (N > 32 or 3 layers -> the deep kernel's phases)"""
     if len(sys.argv) > 1 and sys.argv[1] == "prologue":
         return prologue_main(int(sys.argv[2]) if len(sys.argv) > 2 else 2048)
+    if len(sys.argv) > 1 and sys.argv[1] == "stop":
+        return stop_main(int(sys.argv[2]) if len(sys.argv) > 2 else 2048)
     P = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     if len(sys.argv) > 4:
         A.humans, A.layers, A.contraction = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]

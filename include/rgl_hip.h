@@ -406,6 +406,51 @@ typedef struct RglDeepChildrenPlan {
 } RglDeepChildrenPlan;
 int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan);
 
+/* rgl_plan_scene_forward (ABI 8, additive) -- the form in which the one-wave-per-scene MFMA forward (scene_graph_kernel<NT, SK, WAVES,
+ * CH, SPLIT, EMB, BX> of rgl_scene.hip) takes n_scenes scenes of H humans, scenes_per_crowd sibling scenes per crowd: the state
+ * predictor of a tree level (motion_head 1), path G's value rows, the module forwards of rgl_graph_forward_f32 and the children the
+ * shared-crowd kernels do not cover (motion_head 0: value rows, a row kernel applies the head).  The answer comes from the functions
+ * the launcher itself calls -- run_scene_kernels and the launch_scene* templates run with a plan in place of the launches.  HOST
+ * ONLY: no device call, no launch; reads the dimensions and modes of `graph` (no pointer of it is read) and the process's
+ * RGL_SCENE_SPLIT_BELOW, RGL_SCENE_EMBED_INSIDE, RGL_SCENE_CHILDREN_BELOW, RGL_SCENE_WIDE_SLOTS and RGL_FORCE_GENERIC settings (once
+ * each).  Which kernel family a CALL asks first (RGL_TILES_FORWARD, the shared-crowd children kernels) is not this plan's matter.
+ * image_at_hand: the call is in the bf16x6 mode with its packed three-piece image.  reward_offered: a tree level offers its reward /
+ * next-state work to the launch (mprl_expand_f32 and the searches; never the other callers).
+ *   covered          0: not this kernel (the other fields are 0 then) -- embeddings other than 9|6 / 5|7 -> 64 -> 32, x_dim other
+ *                    than 32, more than 4 layers, more than 128 nodes, concatenation beyond 64 nodes, an unknown similarity,
+ *                    RGL_FORCE_GENERIC=1
+ *   node_tiles       NT: ceil(N / 16) for N = H + 1 <= 64, 8 beyond
+ *   family           SK: 0 softmax (embedded_gaussian, gaussian), 1 plain weights (squared, equal_attention, diagonal), 2 cosine
+ *                    (cosine, cosine_softmax), 3 concatenation
+ *   waves            waves of a workgroup: 8, or 4 for the unsplit NT 3 | 4 forms
+ *   split            1: the NT column tiles of a scene go to NT waves -- NT 2 | 4 (SK 0..2) below 3072 | 4096 scenes, NT 8 always
+ *   embed_inside     1: the kernel embeds its own rows -- softmax family, 9-wide robot rows, NT 1 | 2 | 4, at most 512 scenes, no
+ *                    reward work in the embedding launch; 0: rows from the launch that precedes (embed_launch 1)
+ *   bx               1: the six-term bf16 weight products (image_at_hand, softmax family, NT 2)
+ *   slots            scenes in flight per workgroup: waves, or waves / NT when split; workgroup b takes scenes slots b + k (k <
+ *                    slots), then walks on by grid slots: a split workgroup whose last scenes run out recomputes the launch's
+ *                    last scene in the idle slots and writes nothing from them
+ *   grid, grid_cap   scene workgroups min(ceil(n_scenes / slots), grid_cap); grid_cap = 256 x (2 when two workgroups' LDS fit a
+ *                    CU, else 1) x (2 for 4-wave workgroups)
+ *   last_steps       k steps of A H over the last node tile that reach a valid node: ceil((N - 16 (NT - 1)) / 4), at least 0 (NT 8
+ *                    up to 112 nodes); 4 for the concatenation family, whose last tile keeps the plain node order
+ *   children_riding  1: the offered reward work rides on extra workgroups of THIS launch (fewer than 3072 scenes; 1100 in the
+ *                    bf16x6 mode); offered and 0: it rides in the embedding launch
+ *   embed_launch     1: a row_mlp2_pair_kernel launch precedes
+ *   lds_bytes        dynamic LDS of a scene workgroup: the weight image (Wa, L x W_l, the motion head: 32 x 36 (1 + L) + 32 x 80 +
+ *                    64 + 64 x 20 + 16 floats; bx: its bf16 fragments), for concatenation the pair MLP (64 x 80 + 64 + 64), with
+ *                    the embeddings inside two sets of 3168 floats, and the node rows 16 NT x 36 floats per region slot -- 8 / NT
+ *                    with the embeddings inside and NT 2 | 4, else 8 (NT 1 | 2), 4 (NT 3 | 4), 1 (NT 8)
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (n_scenes, scenes_per_crowd or H < 1, n_scenes no multiple of scenes_per_crowd, more than
+ * RGL_MAX_NODES nodes). */
+typedef struct RglSceneForwardPlan {
+    int covered, node_tiles, family, waves, split, embed_inside, bx, slots, grid, grid_cap, last_steps, children_riding;
+    int embed_launch, reserved;
+    size_t lds_bytes;
+} RglSceneForwardPlan;
+int rgl_plan_scene_forward(const RglGraph* graph, int motion_head, int n_scenes, int scenes_per_crowd, int H, int image_at_hand,
+                           int reward_offered, RglSceneForwardPlan* plan);
+
 /* Bytes of the weight image above; 0 when the configuration has no image-based children kernel (the searches then ignore
  * `children_image`).  Depends on the architecture only (not on the weights, P, A or H).  Round 4: also offered for three-layer
  * graphs and crowds beyond 32 agents with the shipped embedding / head shapes (f32 layout): there the

@@ -88,6 +88,12 @@ class RglDeepChildrenPlan(C.Structure):
                  "parents_per_wg", "grid", "workgroups_per_cu", "reserved")] + [("lds_bytes", C.c_size_t)]
 
 
+class RglSceneForwardPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in
+                ("covered", "node_tiles", "family", "waves", "split", "embed_inside", "bx", "slots", "grid", "grid_cap", "last_steps",
+                 "children_riding", "embed_launch", "reserved")] + [("lds_bytes", C.c_size_t)]
+
+
 class CrowdSimConfig(C.Structure):
     _fields_ = [("time_step", C.c_double), ("time_limit", C.c_double), ("success_reward", C.c_double),
                 ("collision_penalty", C.c_double), ("discomfort_dist", C.c_double),
@@ -162,6 +168,8 @@ SIGNATURES = {
     "rgl_plan_graph_tiles": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglGraphTilesPlan)]),
     "rgl_plan_prologue_embedding": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglPrologueEmbeddingPlan)]),
     "rgl_plan_deep_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.POINTER(RglDeepChildrenPlan)]),
+    "rgl_plan_scene_forward": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(RglSceneForwardPlan)]),
     "rgl_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rgl_transpose_many_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rgl_gather_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -215,7 +223,7 @@ SIGNATURES = {
 
 # Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
-ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
+ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64"}
 
 _lib = None

@@ -431,6 +431,13 @@ extern "C" int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_
         if (rc != 1) return rc;
         // RGL_REQUIRE_MFMA_FORWARD=1 (tests): refuse instead of running the general VALU kernel
         if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
+    } else if (!workspace && !H_out && !A_out && require_mfma_forward()) {
+        // no workspace: rgl_graph_forward_workspace_bytes is 0 when no MFMA kernel covers the model, and the refusal must not
+        // depend on the caller having one (it answered with the general kernel: concatenation beyond 64 nodes, five layers)
+        int rc = rgl::validate_forward_call(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, value_out,
+                                            humans_next);
+        if (rc) return rc;
+        if (n_scenes > 0) return RGL_ERR_BAD_MODE;
     }
     return rgl::launch_generic_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H,
                                        H_out, A_out, value_out, humans_next, (hipStream_t)stream);

@@ -174,6 +174,10 @@ inline int launch_row_mlp2_pair(const RglMlp& wr, const float* robot_rows, float
     return RGL_OK;
 }
 
+// ---- the launch decisions, each made in ONE place: read by the launchers below and by rgl_plan_scene_forward -----------------------
+// node tiles of an N-node scene: 1..4 tiles of 16, the eight-tile form beyond 64 nodes
+inline int scene_node_tiles(int N) { return N > 64 ? 8 : (N + 15) / 16; }
+
 // Split scenes (NT waves per scene) below this many scenes: env RGL_SCENE_SPLIT_BELOW overrides (0 = never, tests / measurements)
 inline int scene_split_below(int nt) {
     static const int env = [] { const char* e = getenv("RGL_SCENE_SPLIT_BELOW"); return e ? atoi(e) : -1; }();
@@ -181,15 +185,59 @@ inline int scene_split_below(int nt) {
     return nt == 2 ? 3072 : 4096;
 }
 
+// few scenes of the shipped shape: the scene kernel embeds its own node tiles (one launch for the level instead of two)
+inline bool scene_embeds_inside(const RglGraph& g, int NT0, int P, bool embed_children) {
+    static const bool emb_off = [] { const char* e = getenv("RGL_SCENE_EMBED_INSIDE"); return e && e[0] == '0'; }();
+    return !emb_off && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
+           (NT0 == 1 || NT0 == 2 || NT0 == 4) && P <= 512 &&     // measured: +1.5-3 % up to 512 scenes, -2 % at 1-2 k (sibling scenes repeat their crowd's rows)
+           (NT0 == 1 || P < scene_split_below(NT0));       // the split form (see launch_scene)
+}
+
+// scene slots the LDS region of a launch holds (fill_scene_args): one per wave, or -- the split form, which launch_scene always
+// takes with the embeddings inside -- one per NT waves of its 8 (with the unsplit count a 50-agent scene workgroup held 95 KB instead
+// of 76: one per CU, and the launch's reward workgroups, which reserve the same LDS, waited for a scene workgroup to retire)
+inline int scene_region_slots(int NT, bool embed_inside) {
+    static const bool wide_slots = [] { const char* e = getenv("RGL_SCENE_WIDE_SLOTS"); return e && e[0] == '1'; }();      // measurements
+    return (embed_inside && (NT == 2 || NT == 4) && !wide_slots) ? 8 / NT : (NT <= 2 ? 8 : (NT <= 4 ? 4 : 1));
+}
+
+// scenes in flight per workgroup of an instantiation, and the most scene workgroups of a launch (one or two per CU by LDS; 4-wave
+// workgroups: twice as many)
+constexpr int scene_slots(bool split, int waves, int nt) { return split ? waves / nt : waves; }
+inline int scene_grid_cap(size_t lds_bytes, int waves) {
+    return 256 * (lds_bytes * 2 <= (size_t)rgl::kLdsBytesPerCu ? 2 : 1) * (waves == 4 ? 2 : 1);
+}
+
+// the level's reward / next-state work rides in the scene kernel's launch below this many scenes (launch_predict_humans)
+// cross-over: ~3 k scenes for the f32 scene kernel (round 2), ~1.1 k once its weight products run on the matrix pipe (round 5:
+// 2048 roots 0.3022 -> 0.2988 ms, 1024 roots 0.1773 -> 0.1759, 512 roots unchanged); RGL_SCENE_CHILDREN_BELOW overrides (measurements)
+inline int scene_children_below(bool bf16x6) {
+    static const int below_env = [] { const char* e = getenv("RGL_SCENE_CHILDREN_BELOW"); return e ? atoi(e) : -1; }();
+    return below_env >= 0 ? below_env : (bf16x6 ? 1100 : 3072);
+}
+
+// What a launch would be, recorded INSTEAD of launched (rgl_plan_scene_forward): with a ScenePlan the launchers below take every
+// branch they take otherwise and stop short of the launch itself.
+struct ScenePlan {
+    int node_tiles, family, waves, split, embed_inside, bx, slots, grid, grid_cap, children_riding, embed_launch;
+    size_t lds_bytes;
+};
+
 template <int NT, int SK, int WAVES, bool SPLIT = false, bool EMB = false, bool BX = false>
-int launch_scene_k(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st) {
+int launch_scene_k(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st, ScenePlan* plan = nullptr) {
     if constexpr (!SPLIT && SK != 3 && (NT == 2 || NT == 4)) {
-        if (sa.P < scene_split_below(NT)) return launch_scene_k<NT, SK, 8, true, EMB, BX>(sa, lds_bytes, children, st);
+        if (sa.P < scene_split_below(NT)) return launch_scene_k<NT, SK, 8, true, EMB, BX>(sa, lds_bytes, children, st, plan);
     }
-    constexpr int kSlots = SPLIT ? WAVES / NT : WAVES;
+    constexpr int kSlots = scene_slots(SPLIT, WAVES, NT);
     int grid = (sa.P + kSlots - 1) / kSlots;
-    const int cap = 256 * (lds_bytes * 2 <= (size_t)rgl::kLdsBytesPerCu ? 2 : 1) * (WAVES == 4 ? 2 : 1);
+    const int cap = scene_grid_cap(lds_bytes, WAVES);
     if (grid > cap) grid = cap;
+    if (plan) {
+        plan->node_tiles = NT; plan->family = SK; plan->waves = WAVES; plan->split = SPLIT; plan->embed_inside = EMB; plan->bx = BX;
+        plan->slots = kSlots; plan->grid = grid; plan->grid_cap = cap; plan->children_riding = children != nullptr;
+        plan->lds_bytes = lds_bytes;
+        return RGL_OK;
+    }
     ChildrenArgs ca{};
     int grid_children = 0;
     if (children) {
@@ -208,30 +256,30 @@ int launch_scene_k(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* ch
 
 // 64 < N <= 128: eight column tiles, always split over the eight waves of a workgroup (one scene per workgroup pass; the
 // unsplit form would hold an 8 x 8 block of adjacency tiles per wave: 256 VGPRs).  The pair-MLP similarity has no split form.
-inline int launch_scene_wide(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st) {
-    if (sa.sim == SIM_SOFTMAX) return launch_scene_k<8, 0, 8, true>(sa, lds_bytes, children, st);
-    if (sa.sim == SIM_COSINE || sa.sim == SIM_COSINE_SOFTMAX) return launch_scene_k<8, 2, 8, true>(sa, lds_bytes, children, st);
+inline int launch_scene_wide(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st, ScenePlan* plan = nullptr) {
+    if (sa.sim == SIM_SOFTMAX) return launch_scene_k<8, 0, 8, true>(sa, lds_bytes, children, st, plan);
+    if (sa.sim == SIM_COSINE || sa.sim == SIM_COSINE_SOFTMAX) return launch_scene_k<8, 2, 8, true>(sa, lds_bytes, children, st, plan);
     if (sa.sim == SIM_CONCAT) return 1;
-    return launch_scene_k<8, 1, 8, true>(sa, lds_bytes, children, st);
+    return launch_scene_k<8, 1, 8, true>(sa, lds_bytes, children, st, plan);
 }
 
 template <int NT, int WAVES>
-int launch_scene(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st) {
+int launch_scene(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st, ScenePlan* plan = nullptr) {
     if constexpr (NT == 2) {
         if (sa.bx)                                       // six-term bf16 weight products (softmax similarity, two node tiles)
-            return sa.robot_rows ? launch_scene_k<2, 0, 8, true, true, true>(sa, lds_bytes, children, st)
-                                 : launch_scene_k<2, 0, WAVES, false, false, true>(sa, lds_bytes, children, st);
+            return sa.robot_rows ? launch_scene_k<2, 0, 8, true, true, true>(sa, lds_bytes, children, st, plan)
+                                 : launch_scene_k<2, 0, WAVES, false, false, true>(sa, lds_bytes, children, st, plan);
     }
     if constexpr (NT == 1) {
-        if (sa.robot_rows) return launch_scene_k<1, 0, 8, false, true>(sa, lds_bytes, children, st);           // embeddings inside
+        if (sa.robot_rows) return launch_scene_k<1, 0, 8, false, true>(sa, lds_bytes, children, st, plan);           // embeddings inside
     }
     if constexpr (NT == 2 || NT == 4) {
-        if (sa.robot_rows) return launch_scene_k<NT, 0, 8, true, true>(sa, lds_bytes, children, st);          // ... and split scenes
+        if (sa.robot_rows) return launch_scene_k<NT, 0, 8, true, true>(sa, lds_bytes, children, st, plan);          // ... and split scenes
     }
-    if (sa.sim == SIM_SOFTMAX) return launch_scene_k<NT, 0, WAVES>(sa, lds_bytes, children, st);
-    if (sa.sim == SIM_COSINE || sa.sim == SIM_COSINE_SOFTMAX) return launch_scene_k<NT, 2, WAVES>(sa, lds_bytes, children, st);
-    if (sa.sim == SIM_CONCAT) return launch_scene_k<NT, 3, WAVES>(sa, lds_bytes, children, st);
-    return launch_scene_k<NT, 1, WAVES>(sa, lds_bytes, children, st);
+    if (sa.sim == SIM_SOFTMAX) return launch_scene_k<NT, 0, WAVES>(sa, lds_bytes, children, st, plan);
+    if (sa.sim == SIM_COSINE || sa.sim == SIM_COSINE_SOFTMAX) return launch_scene_k<NT, 2, WAVES>(sa, lds_bytes, children, st, plan);
+    if (sa.sim == SIM_CONCAT) return launch_scene_k<NT, 3, WAVES>(sa, lds_bytes, children, st, plan);
+    return launch_scene_k<NT, 1, WAVES>(sa, lds_bytes, children, st, plan);
 }
 
 static bool scene_kernel_covers(const RglGraph& g, int N) {
@@ -248,7 +296,7 @@ static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, c
                            int P, int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows, bool embed_inside,
                            const float* sp_image, int slots, int region_floats = 0) {
     const int N = H + 1;
-    const int NT = N > 64 ? 8 : (N + 15) / 16;
+    const int NT = scene_node_tiles(N);
     sa.robot_rows = embed_inside ? robot : nullptr;
     sa.human_rows = embed_inside ? humans : nullptr;
     sa.er_w1 = g.w_r.weight[0]; sa.er_b1 = g.w_r.bias[0]; sa.er_w2 = g.w_r.weight[1]; sa.er_b2 = g.w_r.bias[1];
@@ -290,12 +338,9 @@ static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, c
         sa.off_eh = take(kRowMlpSetFloats);
     }
     sa.wave_stride = 16 * NT * XLD;
-    // scene slots of a workgroup: one per wave, or -- the split form, which launch_scene always takes with the embeddings inside --
-    // one per NT waves of its 8 (with the unsplit count a 50-agent scene workgroup held 95 KB instead of 76: one per CU, and the
-    // launch's reward workgroups, which reserve the same LDS, waited for a scene workgroup to retire)
-    static const bool wide_slots = [] { const char* e = getenv("RGL_SCENE_WIDE_SLOTS"); return e && e[0] == '1'; }();      // measurements
+    // scene slots of a workgroup: the level prologue's, or the launcher's choice
     const bool prologue = slots > 0;
-    if (slots <= 0) slots = (embed_inside && (NT == 2 || NT == 4) && !wide_slots) ? 8 / NT : (NT <= 2 ? 8 : (NT <= 4 ? 4 : 1));
+    if (slots <= 0) slots = scene_region_slots(NT, embed_inside);
     sa.off_wave = take(slots * sa.wave_stride);
     sa.off_rows = sa.chunk_crowds = 0;
     if (prologue) {      // the row buffer, behind everything else (prologue_scene_floats counts it so): as many crowds as the region holds
@@ -307,30 +352,30 @@ static int fill_scene_args(SceneArgs& sa, const RglGraph& g, const RglMlp* mh, c
 }
 
 // embeddings (one launch) + one-wave-per-scene graph forward; mh != null: motion head -> humans_next; rows_out != null: value rows
+// `plan` (rgl_plan_scene_forward): nothing is launched, the form of the launches is recorded
 static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* robot, const float* humans, int crowds_per, int P,
                              int H, float* humans_next, float* rows_out, float* x0_rows, float* xh_rows,
                              const ChildrenArgs* ca, hipStream_t stream, const ChildrenArgs* embed_children = nullptr,
-                             const float* sp_image = nullptr) {
+                             const float* sp_image = nullptr, ScenePlan* plan = nullptr) {
     const int N = H + 1, n_crowds = P / crowds_per;
-    const int NT0 = N > 64 ? 8 : (N + 15) / 16;
-    // few scenes of the shipped shape: the scene kernel embeds its own node tiles (one launch for the level instead of two)
-    static const bool emb_off = [] { const char* e = getenv("RGL_SCENE_EMBED_INSIDE"); return e && e[0] == '0'; }();
-    const bool embed_inside = !emb_off && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
-                              (NT0 == 1 || NT0 == 2 || NT0 == 4) && P <= 512 &&     // measured: +1.5-3 % up to 512 scenes, -2 % at 1-2 k (sibling scenes repeat their crowd's rows)
-                              (NT0 == 1 || P < scene_split_below(NT0));       // the split form (see launch_scene)
+    const int NT0 = scene_node_tiles(N);
+    const bool embed_inside = scene_embeds_inside(g, NT0, P, embed_children != nullptr);
     if (!embed_inside) {
-        int rc = launch_row_mlp2_pair(g.w_r, robot, x0_rows, P, g.w_h, humans, xh_rows, n_crowds * H, stream, embed_children);
-        if (rc) return rc;
+        if (plan) plan->embed_launch = 1;
+        else {
+            int rc = launch_row_mlp2_pair(g.w_r, robot, x0_rows, P, g.w_h, humans, xh_rows, n_crowds * H, stream, embed_children);
+            if (rc) return rc;
+        }
     }
     SceneArgs sa;
     const size_t lds_bytes = fill_scene_args(sa, g, mh, robot, humans, crowds_per, P, H, humans_next, rows_out, x0_rows, xh_rows,
                                              embed_inside, sp_image, 0) * sizeof(float);
     switch (NT0) {
-        case 1: return launch_scene<1, 8>(sa, lds_bytes, ca, stream);
-        case 2: return launch_scene<2, 8>(sa, lds_bytes, ca, stream);
-        case 3: return launch_scene<3, 4>(sa, lds_bytes, ca, stream);
-        case 4: return launch_scene<4, 4>(sa, lds_bytes, ca, stream);
-        default: return launch_scene_wide(sa, lds_bytes, ca, stream);
+        case 1: return launch_scene<1, 8>(sa, lds_bytes, ca, stream, plan);
+        case 2: return launch_scene<2, 8>(sa, lds_bytes, ca, stream, plan);
+        case 3: return launch_scene<3, 4>(sa, lds_bytes, ca, stream, plan);
+        case 4: return launch_scene<4, 4>(sa, lds_bytes, ca, stream, plan);
+        default: return launch_scene_wide(sa, lds_bytes, ca, stream, plan);
     }
 }
 
@@ -427,10 +472,7 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
     float* xh_rows = x0_rows + (size_t)P * XD;               // [n_crowds][H][32]
     // the level's reward / next-state work rides in the scene kernel's launch while the scene workgroups leave LDS free (few scenes),
     // in the embedding launch otherwise: never a launch of its own on this path
-    // cross-over: ~3 k scenes for the f32 scene kernel (round 2), ~1.1 k once its weight products run on the matrix pipe (round 5:
-    // 2048 roots 0.3022 -> 0.2988 ms, 1024 roots 0.1773 -> 0.1759, 512 roots unchanged); RGL_SCENE_CHILDREN_BELOW overrides (measurements)
-    static const int below_env = [] { const char* e = getenv("RGL_SCENE_CHILDREN_BELOW"); return e ? atoi(e) : -1; }();
-    const int children_in_scene_below = below_env >= 0 ? below_env : (pl->contraction_dtype == RGL_CONTRACT_BF16X6 ? 1100 : 3072);
+    const int children_in_scene_below = scene_children_below(pl->contraction_dtype == RGL_CONTRACT_BF16X6);
     const ChildrenArgs* in_scene = P < children_in_scene_below ? &level : nullptr;
     const ChildrenArgs* in_embed = in_scene ? nullptr : &level;
     const int rc = run_scene_kernels(g, &mh, robot, humans, crowds_per, P, H, humans_next, nullptr, x0_rows, xh_rows, in_scene, stream,
@@ -502,3 +544,34 @@ int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c) {
 }
 
 }  // namespace rgl
+
+// What rgl_graph_forward_f32 (values / next humans with a workspace), launch_predict_humans, launch_scene_children and path G's value
+// rows do once they reach run_scene_kernels: the same functions, with a ScenePlan in place of the launches.
+extern "C" int rgl_plan_scene_forward(const RglGraph* graph, int motion_head, int n_scenes, int scenes_per_crowd, int H,
+                                      int image_at_hand, int reward_offered, RglSceneForwardPlan* plan) {
+    if (!graph || !plan) return RGL_ERR_NULL;
+    if (n_scenes < 1 || scenes_per_crowd < 1 || H < 1 || H + 1 > RGL_MAX_NODES || n_scenes % scenes_per_crowd != 0) return RGL_ERR_BAD_SHAPE;
+    *plan = RglSceneForwardPlan{};
+    const RglGraph& g = *graph;
+    const int N = H + 1;
+    if (!scene_kernel_covers(g, N)) return RGL_OK;
+    // stand-ins: the launchers ask only WHETHER there are rows to embed, an image, a motion head, reward work (nothing is read)
+    static const float rows_stand_in = 0.f;
+    static const RglMlp head_stand_in{};
+    static const ChildrenArgs reward_stand_in{};
+    const bool b6 = image_at_hand != 0;
+    const ChildrenArgs* in_scene = reward_offered && n_scenes < scene_children_below(b6) ? &reward_stand_in : nullptr;
+    const ChildrenArgs* in_embed = reward_offered && !in_scene ? &reward_stand_in : nullptr;
+    ScenePlan sp{};
+    const int rc = run_scene_kernels(g, motion_head ? &head_stand_in : nullptr, &rows_stand_in, &rows_stand_in, scenes_per_crowd, n_scenes, H,
+                                     nullptr, nullptr, nullptr, nullptr, in_scene, nullptr, in_embed, b6 ? &rows_stand_in : nullptr, &sp);
+    if (rc) return RGL_OK;                  // (concatenation beyond 64 nodes never gets here: scene_kernel_covers)
+    plan->covered = 1;
+    plan->node_tiles = sp.node_tiles; plan->family = sp.family; plan->waves = sp.waves; plan->split = sp.split;
+    plan->embed_inside = sp.embed_inside; plan->bx = sp.bx; plan->slots = sp.slots; plan->grid = sp.grid; plan->grid_cap = sp.grid_cap;
+    const int steps = scene_last_steps(N, sp.node_tiles, sp.family);
+    plan->last_steps = steps > 0 ? steps : 0;
+    plan->children_riding = sp.children_riding; plan->embed_launch = sp.embed_launch;
+    plan->lds_bytes = sp.lds_bytes;
+    return RGL_OK;
+}

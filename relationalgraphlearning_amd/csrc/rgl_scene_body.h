@@ -46,6 +46,10 @@ constexpr SceneImageLayout scene_image_layout(int L, bool bx = false) {
     return o;
 }
 
+// k steps of A H over the LAST node tile that reach a valid node (PERM in scene_body): ceil(valid / 4) of its four; all four for the
+// concatenation family (SK 3: no node permutation); <= 0 where the eight-tile form's last tile is padding only (N <= 112)
+__host__ __device__ constexpr int scene_last_steps(int N, int NT, int SK) { return SK != 3 ? (N - 16 * (NT - 1) + 3) >> 2 : 4; }
+
 constexpr int kRowMlpSetFloats = 4 * 1 * 4 * 64 + 2 * 4 * 4 * 64 + HID + XD;
 // LDS floats of the level prologue's scene region for an L-layer predictor and crowds of H humans (17..20 nodes): the BX image, the
 // two embedding sets, 8 wave slots of two node tiles, the row buffer -- what fill_scene_args lays out (level_prologue_args checks it)
@@ -360,7 +364,7 @@ __device__ __forceinline__ void scene_body(const SceneArgs& a, float* lds, int f
         // ceil(valid / 4) k steps and the steps over padding nodes are skipped (N = 20: 5 of 8 steps per layer, N = 5: 2 of 4).
         constexpr bool PERM = SK != 3;
         auto jnode = [&](int jt, int r) { return 16 * jt + ((PERM && jt == NT - 1) ? 4 * r + q : 4 * q + r); };
-        const int last_steps = PERM ? (N - 16 * (NT - 1) + 3) >> 2 : 4;
+        const int last_steps = scene_last_steps(N, NT, SK);
         f32x4 pr[NT][NT];
         auto adjacency = [&]() {
             if constexpr (SK == 3) {

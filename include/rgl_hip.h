@@ -751,6 +751,58 @@ typedef struct CrowdExploreJob {
 } CrowdExploreJob;
 int crowd_explore_select_f64(const CrowdExploreJob* job);
 
+/* ---------------------------------------------------------------------------------------------
+ * Nonstop humans (ABI 8, additive): CrowdSim.step with sim.nonstop_human on (crowd_sim/envs/crowd_sim.py:96, 346-349).
+ * crowd_step_nonstop_f64 is crowd_step_f64 with update = 1 -- the same robot move, closest-approach loop, reward ladder, human
+ * actions and clock, from the same device functions -- and, in the same launch, upstream's regeneration of every human that
+ * arrives, drawn from the environment's own numpy stream (`state`, the layout of crowd_explore_seed_u32, which the exploration
+ * kernel shares: one stream, two consumers).  One wave per environment.  For a LIVE environment (done[b] == 0 on entry):
+ *   1. the stream is advanced past policy_draws doubles (2 outputs each, twists included): what the robot's policy drew on the
+ *      host for this decision (`predict` takes one random() in every phase; 0 when crowd_explore_select_f64 made the draw on
+ *      `state` itself, or for a policy that draws nothing);
+ *   2. the robot steps; then the humans in index order: human i moves by its action (decided on the state before anyone moved) and
+ *      ARRIVES when sqrt(dx * dx + dy * dy) < radius_i for its new position against its goal (float64, numpy's roundings);
+ *   3. an arrived human is regenerated at once (generate_human(human), crowd_sim.py:117-169): with scene.randomize_attributes
+ *      v_pref = 0.5 + u, radius = 0.3 + 0.2 u' (two doubles) replace its own; then the scenario's rejection loop (circle: three
+ *      doubles per attempt, goal = the mirrored position; square: one sign double, then position attempts, then goal attempts, two
+ *      doubles each) with its own v_pref as the circle's noise scale.  The clearance list is [robot] + humans as upstream holds
+ *      them at that moment: the robot at its NEW position; humans before i as their steps (and regenerations) left them; human i
+ *      ITSELF at the position it just reached, with its old goal and its new radius; humans after i where they stood BEFORE the
+ *      step.  Accepted: position, goal, zero velocity (and radius, v_pref) are written; the stream stands after the accepted
+ *      attempt.  This happens on the episode's last step too.
+ *   scene.max_attempts bounds the attempts of ONE regeneration (position and goal attempts of a square add up).  At the cap the
+ *   human stays where its step left it (position, velocity, goal; redrawn attributes are kept), status[b] is set to 1 and the
+ *   stream stands after the attempts consumed; later humans of the environment are still processed.  status is only ever SET: the
+ *   caller zeroes it and may read it after many steps.
+ *   A finished environment draws and moves nothing (reward 0, CROWD_INFO_DONE, dmin inf, attempts 0).
+ *   attempts (nullable) [B][H]: attempts consumed by human h's regeneration in this step, 0 = it did not arrive.
+ *   Of `scene` the fields circle_radius, square_width, discomfort_dist, scenario, randomize_attributes and max_attempts are read.
+ * Asynchronous, allocates nothing, one launch.  Errors: RGL_ERR_NULL for a missing required pointer (human_goals, human_vpref and
+ * state included); RGL_ERR_BAD_SHAPE for B < 1, H < 1, H + 1 > RGL_MAX_NODES, policy_draws < 0 or max_attempts < 1;
+ * RGL_ERR_BAD_MODE for unknown kinematics, human policy or scenario.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct CrowdNonstopJob {
+    CrowdSimConfig sim;
+    CrowdSceneConfig scene;
+    double* robot;                  /* device [B][9], in place                                          */
+    double* humans;                 /* device [B][H][5], in place                                       */
+    double* human_goals;            /* device [B][H][2], in place                                       */
+    double* human_vpref;            /* device [B][H], in place                                          */
+    const double* robot_action;     /* device [B][2]                                                    */
+    const double* human_actions;    /* device [B][H][2]; required for CROWD_HUMAN_GIVEN                 */
+    double* time;                   /* device [B]                                                       */
+    int* done;                      /* device [B]                                                       */
+    unsigned* state;                /* device [B][CROWD_EXPLORE_STATE_WORDS], advanced in place         */
+    int* status;                    /* device [B]: set to 1 where a regeneration reached the cap        */
+    int* attempts;                  /* device [B][H]; nullable                                          */
+    float* reward;                  /* device [B]                                                       */
+    int* info;                      /* device [B]                                                       */
+    double* dmin;                   /* device [B]                                                       */
+    int B, H, policy_draws, reserved;
+    rgl_stream_t stream;
+} CrowdNonstopJob;
+int crowd_step_nonstop_f64(const CrowdNonstopJob* job);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

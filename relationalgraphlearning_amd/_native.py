@@ -152,6 +152,15 @@ class CrowdExploreJob(C.Structure):
                 ("B", C.c_int), ("n_actions", C.c_int), ("stream", C.c_void_p)]
 
 
+class CrowdNonstopJob(C.Structure):
+    _fields_ = [("sim", CrowdSimConfig), ("scene", CrowdSceneConfig), ("robot", C.c_void_p), ("humans", C.c_void_p),
+                ("human_goals", C.c_void_p), ("human_vpref", C.c_void_p), ("robot_action", C.c_void_p),
+                ("human_actions", C.c_void_p), ("time", C.c_void_p), ("done", C.c_void_p), ("state", C.c_void_p),
+                ("status", C.c_void_p), ("attempts", C.c_void_p), ("reward", C.c_void_p), ("info", C.c_void_p),
+                ("dmin", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("policy_draws", C.c_int), ("reserved", C.c_int),
+                ("stream", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/rgl_hip.h declares
 SIGNATURES = {
     "rgl_graph_forward_workspace_bytes": (C.c_size_t, [C.POINTER(RglGraph), C.POINTER(RglMlp), C.POINTER(RglMlp), C.c_int,
@@ -217,6 +226,7 @@ SIGNATURES = {
     "rgl_replay_push_f32": (C.c_int, [C.POINTER(RglReplayPushJob)]),
     "crowd_explore_seed_u32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "crowd_explore_select_f64": (C.c_int, [C.POINTER(CrowdExploreJob)]),
+    "crowd_step_nonstop_f64": (C.c_int, [C.POINTER(CrowdNonstopJob)]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
@@ -224,7 +234,7 @@ SIGNATURES = {
 # Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
-            "crowd_explore_seed_u32", "crowd_explore_select_f64"}
+            "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64"}
 
 _lib = None
 

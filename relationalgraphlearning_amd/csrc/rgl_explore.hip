@@ -3,8 +3,9 @@
 // Upstream seeds numpy once per case (CrowdSim.reset, crowd_sim/envs/crowd_sim.py:185-191), lets generate_human consume doubles
 // and then continues the SAME stream in every predict of the episode: `probability = np.random.random()` and, when
 // `probability < epsilon`, `np.random.choice(len(action_space))` (crowd_nav/policy/model_predictive_rl.py:208-210,
-// multi_human_rl.py:34-36).  With ORCA or linear humans nothing else draws, so an exploring episode of case k is a function of
-// k, epsilon and the weights.  These kernels carry that stream per environment: `state[b]` is the 624 MT19937 words plus the
+// multi_human_rl.py:34-36).  With ORCA or linear humans and sim.nonstop_human off nothing else draws.  With nonstop humans the
+// step regenerates arriving humans from the same stream (rgl_nonstop.hip) and `state` is then the simulator's own, shared by both
+// consumers.  Either way an exploring episode of case k is a function of k, epsilon and the weights.  These kernels carry that stream per environment: `state[b]` is the 624 MT19937 words plus the
 // position of the next word (624: twist first), as the scene generator's Stream::pos.
 //
 // One decision of a live environment: u = random_sample() (two words); explored = u < epsilon (strict, float64); if explored and

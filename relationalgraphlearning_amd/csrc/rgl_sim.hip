@@ -6,17 +6,9 @@
 // Follows (reference paths): crowd_sim/envs/crowd_sim.py:252-368 (step), crowd_sim/envs/utils/agent.py:113-139
 // (compute_position, step), crowd_sim/envs/policy/linear.py:16-22 (Linear.predict), crowd_sim/envs/utils/utils.py:4-26.
 #include "rgl_common.h"
+#include "rgl_sim_step.h"        // the robot's step, the reward ladder, a human's action
 
 namespace {
-
-__device__ __forceinline__ double seg_dist_origin(double px, double py, double ex, double ey) {
-    const double sx = ex - px, sy = ey - py;
-    if (sx == 0.0 && sy == 0.0) return sqrt(px * px + py * py);
-    double u = ((0.0 - px) * sx + (0.0 - py) * sy) / (sx * sx + sy * sy);
-    u = u > 1.0 ? 1.0 : (u < 0.0 ? 0.0 : u);
-    const double cx = px + u * sx, cy = py + u * sy;
-    return sqrt(cx * cx + cy * cy);
-}
 
 // one thread per environment
 __global__ void crowd_step_kernel(const CrowdSimConfig cfg, double* __restrict__ robot, double* __restrict__ humans,
@@ -36,61 +28,26 @@ __global__ void crowd_step_kernel(const CrowdSimConfig cfg, double* __restrict__
     double* hs = humans + (size_t)b * H * 5;
     const double dt = cfg.time_step;
     const double a0 = robot_action[2 * b], a1 = robot_action[2 * b + 1];
-    double avx, avy, npx, npy, ntheta = r[8];
-    if (cfg.kinematics == RGL_HOLONOMIC) {
-        avx = a0; avy = a1;
-        npx = r[0] + a0 * dt; npy = r[1] + a1 * dt;
-    } else {
-        const double th = r[8] + a1;
-        avx = a0 * cos(a1 + r[8]); avy = a0 * sin(a1 + r[8]);
-        npx = r[0] + cos(th) * a0 * dt; npy = r[1] + sin(th) * a0 * dt;
-        ntheta = fmod(th, 2.0 * M_PI);
-        if (ntheta < 0.0) ntheta += 2.0 * M_PI;          // python's % returns a non-negative remainder
-    }
-    bool collision = false;
-    double dmin = INFINITY;
-    for (int h = 0; h < H; ++h) {
-        const double px = hs[h * 5] - r[0], py = hs[h * 5 + 1] - r[1];
-        const double vx = hs[h * 5 + 2] - avx, vy = hs[h * 5 + 3] - avy;
-        const double d = seg_dist_origin(px, py, px + vx * dt, py + vy * dt) - hs[h * 5 + 4] - r[4];
-        if (d < 0.0) { collision = true; break; }          // the reference stops at the first collision
-        if (d < dmin) dmin = d;
-    }
-    const double gx = npx - r[5], gy = npy - r[6];
-    const bool reaching = sqrt(gx * gx + gy * gy) < r[4];
-    double rew = 0.0;
-    int code = CROWD_INFO_NOTHING, fin = 0;
-    if (time[b] >= cfg.time_limit - 1.0) { rew = 0.0; fin = 1; code = CROWD_INFO_TIMEOUT; }
-    else if (collision) { rew = cfg.collision_penalty; fin = 1; code = CROWD_INFO_COLLISION; }
-    else if (reaching) { rew = cfg.success_reward; fin = 1; code = CROWD_INFO_REACH_GOAL; }
-    else if (dmin < cfg.discomfort_dist) { rew = (dmin - cfg.discomfort_dist) * cfg.discomfort_penalty_factor * dt; code = CROWD_INFO_DISCOMFORT; }
-    reward[b] = (float)rew;
-    info[b] = code;
-    dmin_out[b] = collision ? -1.0 : dmin;
+    const RobotStep o = crowd_robot_step(cfg, r, hs, H, a0, a1, time[b]);
+    reward[b] = (float)o.reward;
+    info[b] = o.info;
+    dmin_out[b] = o.dmin;
     if (!update) return;
     // humans act on the state BEFORE anyone moves (crowd_sim.py:257-268), then everybody steps
+    const double* env_goals = human_goals ? human_goals + (size_t)b * H * 2 : nullptr;
+    const double* env_vpref = human_vpref ? human_vpref + (size_t)b * H : nullptr;
+    const double* env_given = human_actions ? human_actions + (size_t)b * H * 2 : nullptr;
     for (int h = 0; h < H; ++h) {
         double hvx, hvy;
-        if (cfg.human_policy == CROWD_HUMAN_LINEAR) {
-            const double th = atan2(human_goals[((size_t)b * H + h) * 2 + 1] - hs[h * 5 + 1],
-                                    human_goals[((size_t)b * H + h) * 2] - hs[h * 5]);
-            const double vp = human_vpref[(size_t)b * H + h];
-            hvx = cos(th) * vp; hvy = sin(th) * vp;
-        } else if (cfg.human_policy == CROWD_HUMAN_CONSTANT_VELOCITY) {
-            hvx = hs[h * 5 + 2]; hvy = hs[h * 5 + 3];
-        } else {
-            hvx = human_actions[((size_t)b * H + h) * 2]; hvy = human_actions[((size_t)b * H + h) * 2 + 1];
-        }
+        crowd_human_velocity(cfg, hs, env_goals, env_vpref, env_given, h, hvx, hvy);
         hs[h * 5] += hvx * dt;
         hs[h * 5 + 1] += hvy * dt;
         hs[h * 5 + 2] = hvx;
         hs[h * 5 + 3] = hvy;
     }
-    r[0] = npx; r[1] = npy;
-    if (cfg.kinematics == RGL_HOLONOMIC) { r[2] = a0; r[3] = a1; }
-    else { r[8] = ntheta; r[2] = a0 * cos(ntheta); r[3] = a0 * sin(ntheta); }
+    crowd_robot_commit(cfg, r, o, a0, a1);
     time[b] += dt;
-    done[b] = fin;
+    done[b] = o.fin;
 }
 
 __global__ void crowd_observe_kernel(const double* __restrict__ robot, const double* __restrict__ humans, int B, int H,

@@ -6,7 +6,8 @@ Mirrors the parts of crowd_sim/envs/crowd_sim.py the rollout needs: seeded scene
 environments at once (crowd_nav/utils/explorer.py:21-111).  Humans follow the reference's `linear` policy
 (crowd_sim/envs/policy/linear.py), constant velocity, externally supplied actions, or ORCA (`human_policy="orca"`: the
 reference's default crowd, CentralizedORCA or per-human ORCA on device -- orca.py, csrc/rgl_orca.hip -- whose velocities
-the step then applies as supplied actions).
+the step then applies as supplied actions).  `SimConfig.nonstop_human` (crowd_sim.py:96, 346-349) regenerates arriving humans
+in the step itself, from the case's own numpy stream (crowd_step_nonstop_f64, csrc/rgl_nonstop.hip; `BatchedCrowdSim.stream`).
 """
 import ctypes as C
 
@@ -49,6 +50,9 @@ class SimConfig(object):
         # the device generator's attempt cap per human and what reset() does with a case that reaches it
         self.scene_generator, self.scene_max_attempts = "host", SCENE_MAX_ATTEMPTS
         self.scene_on_unplaced = "raise"                 # device generator, a case at the cap: "raise" | "host" (generate_scene)
+        # upstream's sim.nonstop_human (crowd_sim.py:96, 346-349): a human that reaches its goal is regenerated in the same step,
+        # from the case's own numpy stream (BatchedCrowdSim.stream); scene_max_attempts bounds one regeneration as well
+        self.nonstop_human = False
         for k, v in over.items():
             if not hasattr(self, k):
                 raise AttributeError(k)
@@ -64,7 +68,8 @@ class SimConfig(object):
                          square_width=c.sim.square_width, circle_radius=c.sim.circle_radius, human_num=c.sim.human_num,
                          human_radius=c.humans.radius, human_v_pref=c.humans.v_pref, robot_radius=c.robot.radius,
                          robot_v_pref=c.robot.v_pref, robot_visible=c.robot.visible,
-                         centralized_planning=c.sim.centralized_planning)
+                         centralized_planning=c.sim.centralized_planning,
+                         nonstop_human=bool(getattr(c.sim, "nonstop_human", False)))
 
 
 def generate_scene(cfg, phase, case):
@@ -233,6 +238,10 @@ class BatchedCrowdSim(object):
         self.B = 0
         self._scene_cache = {}
         self.scene_seeds = self.scene_draws = None
+        # nonstop humans (cfg.nonstop_human): the environments' numpy streams, (B, 625) int32 (624 MT19937 words and the position
+        # of the next one: crowd_explore_seed_u32's layout, shared with VectorExplorer's device exploration), the cap flags that
+        # steps accumulate on the device, and per human the attempts its regeneration took in the last step (0: it did not arrive)
+        self.stream = self.nonstop_status = self.last_attempts = None
 
     # -- state ---------------------------------------------------------------------------------------------------
     def reset(self, phase, cases, generator=None):
@@ -246,6 +255,7 @@ class BatchedCrowdSim(object):
             robot, humans, goals, vpref, _, draws = generate_scenes_device(self.cfg, phase, cases, self.device, self.cfg.scene_on_unplaced)
             obs = self._load_tensors(robot, humans, goals, vpref)
             self.scene_seeds, self.scene_draws = _seed_tensor(phase, cases, self.device), draws
+            self._seed_stream()
             return obs
         if generator != "host":
             raise ValueError("unknown scene generator %r" % (generator,))
@@ -260,7 +270,33 @@ class BatchedCrowdSim(object):
                         np.stack([s[2] for s in scenes]), np.stack([s[3] for s in scenes]))
         self.scene_seeds = _seed_tensor(phase, cases, self.device)
         self.scene_draws = torch.tensor([s[4] for s in scenes], dtype=torch.int32).to(self.device)
+        self._seed_stream()
         return obs
+
+    def _seed_stream(self):
+        """Nonstop humans: every environment's stream where its scene left it (crowd_explore_seed_u32 of scene_seeds / scene_draws)."""
+        if not self.cfg.nonstop_human:
+            return
+        state = torch.empty(self.B, nat.EXPLORE_STATE_WORDS, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = nat.lib().crowd_explore_seed_u32(self.scene_seeds.data_ptr(), self.scene_draws.data_ptr(), self.B, state.data_ptr(),
+                                                  _stream())
+        nat.check(rc, "crowd_explore_seed_u32")
+        self.stream = state
+
+    def set_stream(self, state):
+        """Nonstop humans on a loaded state: the environments' streams, (B, 625) int32 or uint32 values -- 624 MT19937 words and
+        the position of the next one (0..624, 624 = twist first).  The simulator keeps a device copy and advances it in place."""
+        if not self.cfg.nonstop_human:
+            raise ValueError("set_stream is for a simulator with SimConfig.nonstop_human on")
+        if torch.is_tensor(state):
+            state = state.to(self.device)
+            state = state.view(torch.int32) if state.dtype == getattr(torch, "uint32", None) else state.to(torch.int32)
+        else:
+            state = torch.from_numpy(np.ascontiguousarray(np.asarray(state).astype(np.uint32)).view(np.int32)).to(self.device)
+        if tuple(state.shape) != (self.B, nat.EXPLORE_STATE_WORDS):
+            raise ValueError("the stream state must have shape (%d, %d), not %s" % (self.B, nat.EXPLORE_STATE_WORDS, tuple(state.shape)))
+        self.stream = state.contiguous().clone()
 
     def load(self, robot, humans, human_goals=None, human_vpref=None):
         dev = self.device
@@ -292,6 +328,10 @@ class BatchedCrowdSim(object):
         self._r32 = self._owned(None if obs is None else obs[0], (self.B, 9), torch.float32, "obs[0]")
         self._h32 = self._owned(None if obs is None else obs[1], (self.B, self.H, 5), torch.float32, "obs[1]")
         self._orca = torch.zeros(self.B, self.H, 2, dtype=torch.float64, device=dev) if self.human_policy == "orca" else None
+        self.stream = self.nonstop_status = self.last_attempts = None      # loaded states carry no stream: set_stream()
+        if self.cfg.nonstop_human:
+            self.nonstop_status = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.last_attempts = torch.zeros(self.B, self.H, dtype=torch.int32, device=dev)
         return self.observe()
 
     def observe(self):
@@ -324,11 +364,18 @@ class BatchedCrowdSim(object):
                                      self.cfg.centralized_planning, out)
 
     # -- dynamics ------------------------------------------------------------------------------------------------
-    def step(self, robot_actions, human_actions=None, update=True, out=None):
+    def step(self, robot_actions, human_actions=None, update=True, out=None, policy_draws=0):
         """robot_actions (B,2) float64 (vx,vy)|(v,r).  Returns (obs, reward (B,) fp32, done (B,) bool, info (B,) int32);
         `self.last_dmin` holds the closest approach (Discomfort.min_dist).  Finished environments stay frozen.
         out: optional caller-owned (reward (B,) float32, info (B,) int32, dmin (B,) float64) the step writes instead of
-        allocating."""
+        allocating.
+        With cfg.nonstop_human an updating step is crowd_step_nonstop_f64: humans that arrive are regenerated from `self.stream`
+        as upstream regenerates them (include/rgl_hip.h), after the stream of every live environment has been advanced past
+        `policy_draws` doubles -- what the robot's policy drew from numpy for this decision on the host (upstream's `predict`: 1;
+        0 when the draw was made on `self.stream` itself, or by a policy that draws nothing).  `self.last_attempts` (B, H) then
+        holds the attempts each regeneration took, and `self.nonstop_status` (B,) accumulates 1 where one reached
+        cfg.scene_max_attempts (that human stays where its step left it); nothing synchronises for it.  update=False regenerates
+        nothing and draws nothing."""
         dev = self.device
         act = torch.as_tensor(robot_actions, dtype=torch.float64).to(dev).contiguous()
         ha = None if human_actions is None else torch.as_tensor(human_actions, dtype=torch.float64).to(dev).contiguous()
@@ -339,6 +386,10 @@ class BatchedCrowdSim(object):
         info = self._owned(None if out is None else out[1], (self.B,), torch.int32, "out[1]")
         dmin = self._owned(None if out is None else out[2], (self.B,), torch.float64, "out[2]")
         cfg = self._config()
+        if self.cfg.nonstop_human and update:
+            self._step_nonstop(cfg, act, ha, reward, info, dmin, policy_draws)
+            self.last_dmin = dmin
+            return self.observe(), reward, self.done.bool(), info
         with torch.cuda.device(dev):
             rc = nat.lib().crowd_step_f64(C.byref(cfg), self.robot.data_ptr(), self.humans.data_ptr(),
                                           None if self.human_goals is None else self.human_goals.data_ptr(),
@@ -350,6 +401,28 @@ class BatchedCrowdSim(object):
         self.last_dmin = dmin
         done = (info >= 2) & (info <= 4) if not update else self.done.bool()
         return self.observe(), reward, done, info
+
+    def _step_nonstop(self, cfg, act, ha, reward, info, dmin, policy_draws):
+        if self.stream is None:
+            raise ValueError("nonstop humans regenerate from the case's numpy stream: reset() from seeded cases, or give the "
+                             "loaded state one with set_stream()")
+        if self.human_goals is None or self.human_vpref is None:
+            raise ValueError("nonstop humans need the humans' goals and v_pref")
+        if int(policy_draws) < 0:
+            raise ValueError("policy_draws must not be negative")
+        job = nat.CrowdNonstopJob()
+        job.sim, job.scene = cfg, _scene_config(self.cfg)
+        job.robot, job.humans = self.robot.data_ptr(), self.humans.data_ptr()
+        job.human_goals, job.human_vpref = self.human_goals.data_ptr(), self.human_vpref.data_ptr()
+        job.robot_action, job.human_actions = act.data_ptr(), None if ha is None else ha.data_ptr()
+        job.time, job.done, job.state = self.time.data_ptr(), self.done.data_ptr(), self.stream.data_ptr()
+        job.status, job.attempts = self.nonstop_status.data_ptr(), self.last_attempts.data_ptr()
+        job.reward, job.info, job.dmin = reward.data_ptr(), info.data_ptr(), dmin.data_ptr()
+        job.B, job.H, job.policy_draws = self.B, self.H, int(policy_draws)
+        with torch.cuda.device(self.device):
+            job.stream = _stream()
+            rc = nat.lib().crowd_step_nonstop_f64(C.byref(job))
+        nat.check(rc, "crowd_step_nonstop_f64")
 
     def onestep_lookahead(self, robot_actions, human_actions=None):
         return self.step(robot_actions, human_actions, update=False)
@@ -415,7 +488,8 @@ def run_episodes(sim, policy, phase, cases, gamma=0.9, max_steps=None, on_step=N
             break
         act_idx, _ = policy.predict_batch(robot32, humans32, roots_are_joint_states=True)
         actions = table[act_idx.long()]
-        (robot32, humans32), reward, done, info = sim.step(actions)
+        # upstream's predict draws one np.random.random() per decision in every phase: nonstop regenerations read what follows
+        (robot32, humans32), reward, done, info = sim.step(actions, policy_draws=1) if sim.cfg.nonstop_human else sim.step(actions)
         if on_step is not None:
             on_step(t, actions, info)
         cum += disc * reward.double()

@@ -28,6 +28,14 @@ multi_human_rl.py:34-36).  Every environment then carries its case's MT19937 sta
 environment, picks the action and writes the action row the simulator steps with (crowd_explore_select_f64, csrc/rgl_explore.hip):
 an exploring episode of training case k is a function of k, epsilon and the weights, as upstream's is with ORCA or linear humans.
 "host" exploration is NOT upstream's stream and not reproducible from the cases.
+
+Nonstop humans (`SimConfig.nonstop_human`): the simulator regenerates arriving humans from the case's stream (`sim.stream`), which
+upstream's `predict` also draws from -- one `np.random.random()` per decision in EVERY phase, plus the words of `choice` when it
+explores -- so the two consumers share one stream.  With exploration="device" the select kernel draws from `sim.stream` itself and
+runs in every phase (epsilon 0 outside `train`: the draw is made, nothing explores); with exploration="host" a step tells the
+simulator to skip the one double an index policy's `predict` would have drawn (`policy_draws=1`; 0 for a velocity policy, whose
+`predict` draws nothing), so `val` and `test` runs are upstream's in either mode, and `train` with host exploration stays "not
+upstream's stream".  A regeneration that reached `scene_max_attempts` raises UnplacedSceneError at the end of its chunk.
 """
 import ctypes as C
 import logging
@@ -40,6 +48,7 @@ from . import _native as nat
 from .actions import as_array
 from .nets import _require_device_tensor, _stream
 from .rollout import rotate
+from .sim import UnplacedSceneError
 
 COLLISION, SUCCESS, TIMEOUT = 2, 3, 4          # BatchedCrowdSim info codes
 CASE_SIZE = {"train": np.iinfo(np.uint32).max - 2000, "val": 100, "test": 500}     # crowd_sim.py:60-62 defaults
@@ -379,19 +388,23 @@ class VectorExplorer(object):
             idx = torch.where(explore, rand_idx, idx)
         return idx
 
-    def _seed_exploration(self, table):
+    def _seed_exploration(self, table, phase="train"):
         """The chunk's stream states, continued from where scene generation left each case's stream, and the select kernel's
-        outputs (one buffer per chunk; `explored` is recorded per step)."""
+        outputs (one buffer per chunk; `explored` is recorded per step).  A nonstop simulator's own streams are used as they
+        are -- its regenerations read what follows each decision -- and outside `train` the draw is made with epsilon 0."""
         sim = self.sim
         if sim.scene_seeds is None or sim.scene_draws is None:
             raise ValueError("exploration='device' needs a simulator reset from seeded cases: loaded states carry no stream")
         B, dev = sim.B, sim.device
-        state = torch.empty(B, nat.EXPLORE_STATE_WORDS, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = nat.lib().crowd_explore_seed_u32(sim.scene_seeds.data_ptr(), sim.scene_draws.data_ptr(), B, state.data_ptr(), _stream())
-        nat.check(rc, "crowd_explore_seed_u32")
+        if getattr(sim.cfg, "nonstop_human", False):
+            state = sim.stream
+        else:
+            state = torch.empty(B, nat.EXPLORE_STATE_WORDS, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                rc = nat.lib().crowd_explore_seed_u32(sim.scene_seeds.data_ptr(), sim.scene_draws.data_ptr(), B, state.data_ptr(), _stream())
+            nat.check(rc, "crowd_explore_seed_u32")
         eps = getattr(self.policy, "epsilon", None)
-        return {"state": state, "table": table, "epsilon": 0.0 if eps is None else float(eps), "explored": [],
+        return {"state": state, "table": table, "epsilon": 0.0 if eps is None or phase != "train" else float(eps), "explored": [],
                 "action": torch.empty(B, 2, dtype=torch.float64, device=dev)}
 
     def _select_on_device(self, greedy, n_actions):
@@ -417,6 +430,7 @@ class VectorExplorer(object):
         robot32, humans32 = sim.reset(phase, cases)
         B = sim.B
         self._explore = None
+        nonstop = bool(getattr(sim.cfg, "nonstop_human", False))
         velocity = bool(getattr(policy, "acts_in_velocity", False))
         if velocity:
             policy.check_kinematics(sim.kinematics)
@@ -425,8 +439,11 @@ class VectorExplorer(object):
             if policy.action_space is None:
                 policy.build_action_space(sim.cfg.robot_v_pref)
             table = torch.tensor(as_array(policy.action_space), dtype=torch.float64, device=sim.device)
-            if self.exploration == "device" and phase == "train":      # val / test: no draw is observable, no kernel runs
-                self._explore = self._seed_exploration(table)
+            # val / test: no draw is observable and no kernel runs -- unless nonstop humans read the stream after each decision
+            if self.exploration == "device" and (phase == "train" or nonstop):
+                self._explore = self._seed_exploration(table, phase)
+        # nonstop humans: what the step skips on the stream for the decision's draw, where the select kernel has not made it there
+        step_kw = {"policy_draws": 0 if (velocity or self._explore is not None) else 1} if nonstop else {}
         max_steps = int(round(sim.cfg.time_limit / sim.cfg.time_step)) + 2
         outcome = torch.zeros(B, dtype=torch.int32, device=sim.device)
         rewards, infos, dmins, states, actions = [], [], [], [], []
@@ -456,7 +473,8 @@ class VectorExplorer(object):
             else:
                 act = table[idx]
             (robot32, humans32), reward, _, info = sim.step(act,
-                                                            out=None if record is None else tuple(r[t] for r in record[2:]))
+                                                            out=None if record is None else tuple(r[t] for r in record[2:]),
+                                                            **step_kw)
             if velocity:
                 idx = idx.clone()                        # the policy may hand out one buffer per call
             actions.append(idx)
@@ -466,6 +484,13 @@ class VectorExplorer(object):
             ended = (info >= COLLISION) & (info <= TIMEOUT)
             outcome = torch.where(ended, info, outcome)
         info_t = torch.stack(infos).cpu().numpy()                    # (T,B); 5 = finished earlier
+        if nonstop:
+            capped = torch.nonzero(sim.nonstop_status).flatten().tolist()
+            if capped:
+                raise UnplacedSceneError("%d of %d %s episodes had a nonstop human that found no place within scene_max_attempts = %d "
+                                         "attempts: cases %s.  Raise SimConfig.scene_max_attempts."
+                                         % (len(capped), B, phase, int(sim.cfg.scene_max_attempts), [cases[b] for b in capped]),
+                                         [(phase, cases[b]) for b in capped])
         live = info_t != 5
         lengths = live.sum(0)
         reward_t = np.where(live, torch.stack(rewards).cpu().numpy().astype(np.float64), 0.0)

@@ -803,6 +803,72 @@ typedef struct CrowdNonstopJob {
 } CrowdNonstopJob;
 int crowd_step_nonstop_f64(const CrowdNonstopJob* job);
 
+/* ---------------------------------------------------------------------------------------------
+ * SARL / OM-SARL evaluation (ABI 8, additive): the one-step search of MultiHumanRL.predict (crowd_nav/policy/multi_human_rl.py:
+ * 12-71) with the attention value network of crowd_nav/policy/sarl.py:28-73 and, with_om, the occupancy maps of
+ * build_occupancy_maps (multi_human_rl.py:117-171).  Evaluation only: there is no backward pass.
+ *
+ * Supported shapes -- every other request returns RGL_ERR_BAD_SHAPE / RGL_ERR_BAD_MODE before anything is launched:
+ *   mlp1 D-150-100 (last_relu), mlp2 100-100-50, attention (200 | 100)-100-100-1 (200: with_global_state), mlp3 56-150-100-100-1;
+ *   D = 13 + cell_num^2 om_channel_size in {13, 29, 45, 61} (om_channel_size 0 = no maps; 1..3 with cell_num 4);
+ *   2 <= H with maps (upstream's np.concatenate raises for a single human), 1 <= H without, H <= RGL_SARL_MAX_HUMANS;
+ *   contraction_dtype RGL_CONTRACT_F32 only; n_scenes = B num_actions <= 2^26.
+ * ------------------------------------------------------------------------------------------- */
+#define RGL_SARL_MAX_HUMANS 20      /* the value kernel parks a wave's per-human mlp1 outputs in LDS: 7 424 bytes per human */
+
+typedef struct SarlPlanner {
+    RglMlp mlp1, mlp2, attention, mlp3;     /* sarl.ValueNetwork.{mlp1, mlp2, attention, mlp3}                          */
+    int with_global_state;                  /* the mean of mlp1's outputs over the humans joins every attention input   */
+    int om_channel_size;                    /* 0: no occupancy maps; 1 | 2 | 3                                          */
+    int cell_num;
+    int kinematics;
+    double cell_size;
+    int num_actions;
+    int contraction_dtype;                  /* RGL_CONTRACT_F32                                                         */
+    double time_step;
+    double gamma;                           /* raw gamma; the discount is gamma^(time_step * v_pref)                    */
+    const double* actions;                  /* device [A][2]                                                            */
+    const double* root_robot_f64;           /* optional, as in GcnPlanner: the float64 states the fp32 arrays were      */
+    const double* root_humans_f64;          /* rounded from (propagate, reward and the maps start from them)            */
+} SarlPlanner;
+
+/* Occupancy maps of B crowds: maps device [B][H][cell_num^2 om_channel_size] float32, row (b, i) = the map of human i among the
+ * other humans j != i of crowd b (by index), built from the NEXT states p + v time_step (time_step = 0: the states themselves,
+ * what MultiHumanRL.transform hands over).  Reads humans_f64 (device [B][H][5] float64) when set, else humans (float32, widened).
+ * All arithmetic is float64 with every operation rounded on its own, as numpy's: frame rotated by arctan2(vy, vx) of human i,
+ * indices floor(p / cell_size + cell_num / 2), out-of-range humans dropped; one channel: 0 / 1; two and three channels: per-slot
+ * means (sum in other-human order / count) with the slot base 2 * cell in BOTH cases, so with three channels neighbouring cells
+ * share a slot and the slots above 2 (cell_num^2 - 1) + 2 stay zero.  One launch.
+ * Errors: RGL_ERR_NULL; RGL_ERR_BAD_MODE (om_channel_size outside 1..3); RGL_ERR_BAD_SHAPE (B < 1, H < 2, H + 1 > RGL_MAX_NODES,
+ * cell_num outside 1..8, cell_size <= 0). */
+int sarl_occupancy_maps_f32(const double* humans_f64, const float* humans, int B, int H, double time_step, int cell_num,
+                            double cell_size, int om_channel_size, float* maps, rgl_stream_t stream);
+
+/* The value network for n_scenes scenes of H humans in one launch (plus one that lays the weights out as MFMA fragments in
+ * `workspace`, device, >= sarl_value_workspace_bytes(); 0 = the planner is outside the supported shapes).  Input, either
+ *   rows   device [n_scenes][H][D]: the rows sarl.ValueNetwork.forward takes (the other three pointers are not read), or
+ *   self6  device [n_scenes][6], hum7 device [n_scenes][H][7] as gcn_prepare_f32 writes them, and (D > 13) maps device
+ *          [n_scenes / scenes_per_root][H][D - 13]: scene s reads the maps of root s / scenes_per_root.
+ * value device [n_scenes], attention device [n_scenes][H] (the softmax weights of sarl.py:57-63).  No activation passes through
+ * global memory; the last, partial tile of sixteen scenes is masked.  Reads the four MLPs, with_global_state, om_channel_size,
+ * cell_num and contraction_dtype of `planner`. */
+size_t sarl_value_workspace_bytes(const SarlPlanner* planner);
+int sarl_value_f32(const SarlPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
+                   int n_scenes, int scenes_per_root, int H, void* workspace, size_t workspace_bytes, float* value,
+                   float* attention, rgl_stream_t stream);
+
+/* The search for B roots: gcn_prepare_f32, the maps (once per root and human: without query_env they do not depend on the action,
+ * multi_human_rl.py:52-55), the value network over the B x A scenes, value = reward + gamma^(time_step v_pref) V in float64 (:58)
+ * and the strict `>` walk of :60-64.
+ *   robot device [B][9], humans device [B][H][5]; workspace device, >= sarl_predict_workspace_bytes(planner, B, H) (0: unsupported)
+ *   action_values device [B][A], best_action device [B] int32 (-1 where no value beats -inf), best_value device [B] (nullable; 0
+ *   where best_action = -1), best_attention device [B][H] (nullable): the attention weights of the selected action (zeros where
+ *   best_action = -1) -- what get_attention_weights() returns after predict. */
+size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B, int H);
+int sarl_predict_f32(const SarlPlanner* planner, const float* robot, const float* humans, int B, int H, void* workspace,
+                     size_t workspace_bytes, float* action_values, int* best_action, float* best_value, float* best_attention,
+                     rgl_stream_t stream);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

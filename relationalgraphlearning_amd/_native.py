@@ -72,6 +72,16 @@ class GcnPlanner(C.Structure):
                 ("root_robot_f64", C.c_void_p), ("root_humans_f64", C.c_void_p), ("contraction_dtype", C.c_int), ("reserved", C.c_int)]
 
 
+SARL_MAX_HUMANS = 20
+
+
+class SarlPlanner(C.Structure):
+    _fields_ = [("mlp1", RglMlp), ("mlp2", RglMlp), ("attention", RglMlp), ("mlp3", RglMlp), ("with_global_state", C.c_int),
+                ("om_channel_size", C.c_int), ("cell_num", C.c_int), ("kinematics", C.c_int), ("cell_size", C.c_double),
+                ("num_actions", C.c_int), ("contraction_dtype", C.c_int), ("time_step", C.c_double), ("gamma", C.c_double),
+                ("actions", C.c_void_p), ("root_robot_f64", C.c_void_p), ("root_humans_f64", C.c_void_p)]
+
+
 class MprlPlanner(C.Structure):
     _fields_ = [("value_graph", RglGraph), ("value_head", RglMlp), ("predictor_graph", RglGraph),
                 ("motion_head", RglMlp), ("linear_state_predictor", C.c_int), ("kinematics", C.c_int),
@@ -227,6 +237,14 @@ SIGNATURES = {
     "crowd_explore_seed_u32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "crowd_explore_select_f64": (C.c_int, [C.POINTER(CrowdExploreJob)]),
     "crowd_step_nonstop_f64": (C.c_int, [C.POINTER(CrowdNonstopJob)]),
+    "sarl_occupancy_maps_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
+    "sarl_value_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner)]),
+    "sarl_value_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sarl_predict_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner), C.c_int, C.c_int]),
+    "sarl_predict_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
@@ -234,7 +252,8 @@ SIGNATURES = {
 # Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
-            "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64"}
+            "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
+            "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32"}
 
 _lib = None
 

@@ -1,0 +1,579 @@
+// rgl_sarl.hip -- SARL / OM-SARL evaluation: the occupancy maps of MultiHumanRL.build_occupancy_maps
+// (crowd_nav/policy/multi_human_rl.py:117-171), the attention value network of crowd_nav/policy/sarl.py:28-73 and the one-step
+// search of multi_human_rl.py:36-64 around them.  The search's first step (propagate, rotate, reward) is path G's gcn_prepare_f32.
+//
+// The value network is one f32 MFMA launch over all scenes.  A wave owns sixteen scenes; MFMA tile h holds human h of those sixteen
+// scenes as the B operand (column n = scene n), the weights are the A operand.  A 16 x 16 x 4 product leaves output feature
+// 16 mt + 4 g + i of scene n in register i of lane (g, n) (g = lane / 16, n = lane % 16).  The next layer takes the four k of its
+// k-step (t, i) from exactly those registers -- k-step (t, i) multiplies the input features {16 t + 4 g + i : g = 0..3} -- so an
+// activation never leaves the lane that computed it, and the mean over humans, the softmax over humans and the weighted sum are
+// element-wise over the wave's own tiles.  The A fragments of that k order are laid out once per call by sarl_pack_kernel
+// ([t][mt][lane][i]: one 16-byte load per lane serves four MFMAs) and read from L2: the four MLPs hold 415 KB, more than a CU's LDS.
+// The LDS parks the per-human mlp1 outputs of a tile's scenes (they are read twice: by the mean, and by mlp2 / attention once the
+// mean is known), later overwritten by the mlp2 outputs and the attention score of the same human: 7 424 bytes per human, which is
+// what bounds H (RGL_SARL_MAX_HUMANS).  A workgroup is one wave below kSarlWideFrom humans and four waves sharing one tile above.
+#include "rgl_mfma.h"
+
+namespace {
+
+constexpr int kSarlLayers = 11;         // mlp1.{0,2} mlp2.{0,2} attention.{0,2,4} mlp3.{0,2,4,6}
+constexpr int kT150 = 10, kT100 = 7, kT50 = 4;      // 16-feature tiles of the shipped widths
+constexpr int kParkRegs = 4 * kT100 + 1;            // a human's slot: 28 registers of the wave + its attention score
+constexpr int kParkFloats = kParkRegs * 64;
+
+struct SarlPackJob {
+    const float* src;           // k-major [K][M]
+    const float* bias;          // [M]
+    long long dst;              // float offset of the packed layer: [KT][MT][64][4] fragments, then [MT][16] bias
+    int K, M, KT, MT;
+    int split_tile, split_cols; // k-tiles below split_tile read columns [0, split_cols) from their first feature on, the tiles from
+                                // split_tile on read columns split_cols.. (the concatenations: mean behind mlp1's rows, the
+                                // weighted feature behind the six self features)
+};
+struct SarlPackArgs {
+    SarlPackJob job[kSarlLayers];
+    float* out;
+};
+
+__global__ void sarl_pack_kernel(const SarlPackArgs pa) {
+    const SarlPackJob& j = pa.job[blockIdx.y];
+    const long long n_frag = (long long)j.MT * j.KT * 256, total = n_frag + j.MT * 16;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        float v = 0.f;
+        if (e < n_frag) {
+            const int i = (int)(e & 3), lane = (int)((e >> 2) & 63);
+            const int tt = (int)(e >> 8), mt = tt % j.MT, t = tt / j.MT;
+            const int g = lane >> 4, m = lane & 15;
+            const int kidx = 16 * t + 4 * g + i, row = 16 * mt + m;
+            int col;
+            bool ok;
+            if (t < j.split_tile) {
+                col = kidx;
+                ok = col < j.split_cols;
+            } else {
+                col = j.split_cols + kidx - 16 * j.split_tile;
+                ok = col < j.K;
+            }
+            if (ok && row < j.M) v = j.src[(size_t)col * j.M + row];
+        } else {
+            const int row = (int)(e - n_frag);
+            if (row < j.M) v = j.bias[row];
+        }
+        pa.out[j.dst + e] = v;
+    }
+}
+
+// out = W in + b over one 16-scene tile: KT input tiles, MT output tiles, every output tile an accumulator of its own (MT independent
+// MFMA chains in flight per k-step)
+template <int KT, int MT, bool RELU>
+__device__ __forceinline__ void sarl_layer(const f32x4 (&in)[KT], f32x4 (&out)[MT], const float* __restrict__ wp, unsigned lane) {
+    // the layer's base stays a scalar the compiler cannot see through: the hundreds of fragment addresses of a pass over the network
+    // are loop invariants, and hoisted out of the tile loop they spill; as scalar base + lane offset + immediate they cost nothing
+    const char* w = reinterpret_cast<const char*>(wp);
+    asm volatile("" : "+s"(w));
+    const unsigned lane_off = lane * 16u, bias_off = (lane >> 4) * 16u;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) out[mt] = *reinterpret_cast<const f32x4*>(w + (size_t)(MT * KT * 1024 + 64 * mt) + bias_off);
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        f32x4 a[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) a[mt] = *reinterpret_cast<const f32x4*>(w + (size_t)((t * MT + mt) * 1024) + lane_off);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) out[mt] = mfma4(a[mt][i], in[t][i], out[mt]);
+        load_fence();
+    }
+    if (RELU) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[mt][i] = fmaxf(out[mt][i], 0.f);
+    }
+}
+
+// float offset of packed layer l: a function of the two template parameters of the value kernel alone
+constexpr int sarl_layer_offset(int kt0, bool global, int l) {
+    const int KT[kSarlLayers] = {kt0, kT150, kT100, kT100, global ? 2 * kT100 : kT100, kT100, kT100, 1 + kT50, kT150, kT100, kT100};
+    const int MT[kSarlLayers] = {kT150, kT100, kT100, kT50, kT100, kT100, 1, kT150, kT100, kT100, 1};
+    int off = 0;
+    for (int i = 0; i < l; ++i) off += MT[i] * KT[i] * 256 + MT[i] * 16;
+    return off;
+}
+
+struct SarlValueArgs {
+    const float* packed;
+    const float* rows;          // [S][H][D], or null: the three arrays below
+    const float* self6;         // [S][6]
+    const float* hum7;          // [S][H][7]
+    const float* maps;          // [S / scenes_per_root][H][D - 13]; unread when D == 13
+    float* value;               // [S]
+    float* attention;           // [S][H]
+    int S, H, D, scenes_per_root, n_tiles;
+};
+
+// KT0: 16-feature tiles of a row (input_dim 13 | 29 | 45 | 61); GLOBAL: with_global_state; WAVES: waves of the workgroup, which
+// all work on the same sixteen scenes -- wave w takes the humans h = w, w + WAVES, .. through mlp1 and through mlp2 / attention, and
+// the waves take turns with a tile's softmax, weighted sum and mlp3.  One wave per workgroup while four such workgroups' parking
+// space fits a CU; at larger H a one-wave workgroup would leave SIMDs idle behind its LDS.
+template <int KT0, bool GLOBAL, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueArgs va) {
+    extern __shared__ float park[];         // [H][kParkRegs][64]
+    const int wave = threadIdx.x >> 6;
+    const unsigned lane = threadIdx.x & 63;
+    const int g = lane >> 4, n = lane & 15;
+    const int H = va.H, D = va.D;
+    auto W = [&](auto l) { return va.packed + sarl_layer_offset(KT0, GLOBAL, decltype(l)::value); };
+
+    int turn = 0;
+    for (int tile = blockIdx.x; tile < va.n_tiles; tile += gridDim.x, ++turn) {
+        const int s = tile * 16 + n;
+        const bool live = s < va.S;
+        const size_t sc = (size_t)(live ? s : va.S - 1);       // the partial last tile computes its last scene again, writes nothing
+        const size_t root = sc / (size_t)va.scenes_per_root;
+
+        // ---- mlp1 per human; its outputs parked ----
+        for (int h = wave; h < H; h += WAVES) {
+            f32x4 x[KT0];
+#pragma unroll
+            for (int t = 0; t < KT0; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int f = 16 * t + 4 * g + i;
+                    float v = 0.f;
+                    if (va.rows) {
+                        if (f < D) v = va.rows[(sc * H + h) * D + f];
+                    } else if (f < 6) {
+                        v = va.self6[sc * 6 + f];
+                    } else if (f < 13) {
+                        v = va.hum7[(sc * H + h) * 7 + (f - 6)];
+                    } else if (f < D) {
+                        v = va.maps[(root * H + h) * (size_t)(D - 13) + (f - 13)];
+                    }
+                    x[t][i] = v;
+                }
+            f32x4 h1[kT150], y[kT100];
+            sarl_layer<KT0, kT150, true>(x, h1, W(std::integral_constant<int, 0>{}), lane);
+            sarl_layer<kT150, kT100, true>(h1, y, W(std::integral_constant<int, 1>{}), lane);
+            float* slot = park + (size_t)h * kParkFloats + lane;
+#pragma unroll
+            for (int r = 0; r < kT100; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) slot[(4 * r + i) * 64] = y[r][i];
+        }
+        __syncthreads();
+        f32x4 mean[kT100];
+        if constexpr (GLOBAL) {     // torch.mean over the humans: the sum in human order, divided
+#pragma unroll
+            for (int r = 0; r < kT100; ++r) mean[r] = zero4();
+            for (int h = 0; h < H; ++h) {
+                const float* slot = park + (size_t)h * kParkFloats + lane;
+#pragma unroll
+                for (int r = 0; r < kT100; ++r)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) mean[r][i] += slot[(4 * r + i) * 64];
+            }
+            const float fh = (float)H;
+#pragma unroll
+            for (int r = 0; r < kT100; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) mean[r][i] = mean[r][i] / fh;
+            if (WAVES > 1) __syncthreads();     // every wave has read every slot before any slot changes its content
+        }
+
+        // ---- mlp2 and the attention score per human; the slot now keeps the mlp2 output and the score ----
+        for (int h = wave; h < H; h += WAVES) {
+            float* slot = park + (size_t)h * kParkFloats + lane;
+            constexpr int KA = GLOBAL ? 2 * kT100 : kT100;
+            f32x4 ain[KA];
+#pragma unroll
+            for (int r = 0; r < kT100; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ain[r][i] = slot[(4 * r + i) * 64];
+            if constexpr (GLOBAL) {
+#pragma unroll
+                for (int r = 0; r < kT100; ++r) ain[kT100 + r] = mean[r];
+            }
+            {
+                f32x4 a1[kT100], a2[kT100], sco[1];
+                sarl_layer<KA, kT100, true>(ain, a1, W(std::integral_constant<int, 4>{}), lane);
+                sarl_layer<kT100, kT100, true>(a1, a2, W(std::integral_constant<int, 5>{}), lane);
+                sarl_layer<kT100, 1, false>(a2, sco, W(std::integral_constant<int, 6>{}), lane);
+                if (g == 0) park[(size_t)h * kParkFloats + 4 * kT100 * 64 + n] = sco[0][0];      // output feature 0 of scene n
+            }
+            {
+                f32x4 yin[kT100], m1[kT100], feat[kT50];
+#pragma unroll
+                for (int r = 0; r < kT100; ++r) yin[r] = ain[r];
+                sarl_layer<kT100, kT100, true>(yin, m1, W(std::integral_constant<int, 2>{}), lane);
+                sarl_layer<kT100, kT50, false>(m1, feat, W(std::integral_constant<int, 3>{}), lane);
+#pragma unroll
+                for (int r = 0; r < kT50; ++r)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) slot[(4 * r + i) * 64] = feat[r][i];
+            }
+        }
+        __syncthreads();        // scores and mlp2 outputs of every human are in place (one wave: lanes 0..15 wrote the scores)
+
+        // ---- softmax over the humans (sarl.py:57-63 with an all-ones mask), weighted sum of the mlp2 outputs: one wave's turn ----
+        const bool mine = wave == turn % WAVES;
+        f32x4 joint[1 + kT50];
+        if (mine) {
+            float smax = -INFINITY;
+            for (int h = 0; h < H; ++h) smax = fmaxf(smax, park[(size_t)h * kParkFloats + 4 * kT100 * 64 + n]);
+            float ssum = 0.f;
+            for (int h = 0; h < H; ++h) ssum = f32_add(ssum, expf(f32_sub(park[(size_t)h * kParkFloats + 4 * kT100 * 64 + n], smax)));
+#pragma unroll
+            for (int r = 0; r <= kT50; ++r) joint[r] = zero4();
+            for (int h = 0; h < H; ++h) {
+                const float w = f32_div(expf(f32_sub(park[(size_t)h * kParkFloats + 4 * kT100 * 64 + n], smax)), ssum);
+                if (live && g == 0) va.attention[sc * H + h] = w;
+                const float* slot = park + (size_t)h * kParkFloats + lane;
+#pragma unroll
+                for (int r = 0; r < kT50; ++r)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) joint[1 + r][i] = f32_add(joint[1 + r][i], f32_mul(w, slot[(4 * r + i) * 64]));
+            }
+        }
+        __syncthreads();        // the next tile's parking waits for these reads; mlp3 below touches no LDS
+        if (mine) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {       // the six self features of the first row (sarl.py:42), tile 0 of mlp3's input
+                const int f = 4 * g + i;
+                joint[0][i] = f < 6 ? (va.rows ? va.rows[sc * H * D + f] : va.self6[sc * 6 + f]) : 0.f;
+            }
+            f32x4 p1[kT150], p2[kT100], p3[kT100], val[1];
+            sarl_layer<1 + kT50, kT150, true>(joint, p1, W(std::integral_constant<int, 7>{}), lane);
+            sarl_layer<kT150, kT100, true>(p1, p2, W(std::integral_constant<int, 8>{}), lane);
+            sarl_layer<kT100, kT100, true>(p2, p3, W(std::integral_constant<int, 9>{}), lane);
+            sarl_layer<kT100, 1, false>(p3, val, W(std::integral_constant<int, 10>{}), lane);
+            if (live && g == 0) va.value[sc] = val[0][0];
+        }
+    }
+}
+
+// One thread per (root, human, slot) of the maps: multi_human_rl.py:117-171 in float64, every operation rounded on its own, the
+// other humans walked in list order.  The states are the roots' next human states p + v dt (dt = 0: the states themselves).
+__global__ __launch_bounds__(256) void sarl_maps_kernel(const double* __restrict__ humans64, const float* __restrict__ humans32, int B, int H, double dt,
+                                 int cell_num, double cell_size, int channels, float* __restrict__ maps) {
+#pragma clang fp contract(off)
+    const int n_slots = cell_num * cell_num * channels;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)B * H * n_slots) return;
+    const int slot = (int)(idx % n_slots);
+    const long long bi = idx / n_slots;
+    const int i = (int)(bi % H);
+    const long long b = bi / H;
+    auto HB = [&](int j, int k) {
+        const size_t at = ((size_t)b * H + j) * 5 + k;
+        return humans64 ? humans64[at] : (double)humans32[at];
+    };
+    const double px = HB(i, 0) + HB(i, 2) * dt, py = HB(i, 1) + HB(i, 3) * dt;
+    const double own_angle = atan2(HB(i, 3), HB(i, 2));
+    const double half = (double)cell_num / 2.0;
+    double sum = 0.0;
+    int count = 0;
+    for (int j = 0; j < H; ++j) {
+        if (j == i) continue;
+        const double ox = (HB(j, 0) + HB(j, 2) * dt) - px, oy = (HB(j, 1) + HB(j, 3) * dt) - py;
+        const double rot = atan2(oy, ox) - own_angle;
+        const double dist = sqrt(ox * ox + oy * oy);
+        const double xi = floor(cos(rot) * dist / cell_size + half), yi = floor(sin(rot) * dist / cell_size + half);
+        if (!(xi >= 0.0 && xi < (double)cell_num && yi >= 0.0 && yi < (double)cell_num)) continue;
+        const int cell = cell_num * (int)yi + (int)xi;
+        if (channels == 1) {
+            if (cell == slot) count = 1;
+            continue;
+        }
+        const double vrot = atan2(HB(j, 3), HB(j, 2)) - own_angle;
+        const double speed = sqrt(HB(j, 2) * HB(j, 2) + HB(j, 3) * HB(j, 3));
+        const double ovx = cos(vrot) * speed, ovy = sin(vrot) * speed;
+        // the slot base is 2 * cell for two AND three channels (:159-164)
+        if (channels == 2) {
+            if (slot == 2 * cell) { sum += ovx; ++count; }
+            else if (slot == 2 * cell + 1) { sum += ovy; ++count; }
+        } else {
+            if (slot == 2 * cell) { sum += 1.0; ++count; }
+            else if (slot == 2 * cell + 1) { sum += ovx; ++count; }
+            else if (slot == 2 * cell + 2) { sum += ovy; ++count; }
+        }
+    }
+    maps[idx] = channels == 1 ? (count ? 1.f : 0.f) : (count ? (float)(sum / (double)count) : 0.f);
+}
+
+constexpr int kSelLanes = 16;
+
+// value = reward + gamma^(dt v_pref) V in float64 (multi_human_rl.py:58), the strict `>` walk of :60-64 as a first-maximum
+// reduction over 16 lanes per root, and the attention row of the action it selects
+__global__ void sarl_select_kernel(const float* __restrict__ robot, const float* __restrict__ reward, const float* __restrict__ value,
+                                   const float* __restrict__ attention, int B, int A, int H, double gamma, double dt,
+                                   float* __restrict__ action_values, int* __restrict__ best_action, float* __restrict__ best_value,
+                                   float* __restrict__ best_attention) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = t / kSelLanes, sub = t % kSelLanes;
+    const bool live = b < B;
+    double best = -INFINITY;
+    int ba = -1;
+    if (live) {
+        const double disc = pow(gamma, dt * (double)robot[(size_t)b * 9 + 7]);
+        for (int a = sub; a < A; a += kSelLanes) {
+            const double v = (double)reward[(size_t)b * A + a] + disc * (double)value[(size_t)b * A + a];
+            action_values[(size_t)b * A + a] = (float)v;
+            if (v > best) {
+                best = v;
+                ba = a;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = kSelLanes / 2; m >= 1; m >>= 1) {
+        const double ov = __shfl_xor(best, m);
+        const int oa = __shfl_xor(ba, m);
+        if (oa >= 0 && (ba < 0 || ov > best || (ov == best && oa < ba))) {
+            best = ov;
+            ba = oa;
+        }
+    }
+    if (live) {
+        if (sub == 0) {
+            best_action[b] = ba;
+            if (best_value) best_value[b] = ba >= 0 ? (float)best : 0.f;
+        }
+        if (best_attention)
+            for (int h = sub; h < H; h += kSelLanes)
+                best_attention[(size_t)b * H + h] = ba >= 0 ? attention[((size_t)b * A + ba) * H + h] : 0.f;
+    }
+}
+
+inline long long align_up256(long long x) { return (x + 255) & ~255ll; }
+
+inline int sarl_map_floats(const SarlPlanner& pl) { return pl.om_channel_size ? pl.cell_num * pl.cell_num * pl.om_channel_size : 0; }
+
+// the shapes the value kernel is built for; `H` < 0: the planner alone
+inline int validate_sarl(const SarlPlanner& pl, int H) {
+    const RglMlp* ms[4] = {&pl.mlp1, &pl.mlp2, &pl.attention, &pl.mlp3};
+    for (const RglMlp* m : ms) {
+        const int rc = rgl::validate_mlp(*m, 0, 0);
+        if (rc) return rc;
+    }
+    if (pl.om_channel_size < 0 || pl.om_channel_size > 3) return RGL_ERR_BAD_MODE;
+    if (pl.om_channel_size && (pl.cell_num < 1 || pl.cell_num > 8 || !(pl.cell_size > 0.0))) return RGL_ERR_BAD_SHAPE;
+    const int D = 13 + sarl_map_floats(pl);
+    if (D != 13 && D != 29 && D != 45 && D != 61) return RGL_ERR_BAD_SHAPE;
+    const int att_in = pl.with_global_state ? 200 : 100;
+    auto is = [](const RglMlp& m, int n, int d0, int d1, int d2, int d3, int d4, int relu) {
+        const int want[5] = {d0, d1, d2, d3, d4};
+        if (m.n_layers != n || (m.last_relu != 0) != (relu != 0)) return false;
+        for (int l = 0; l <= n; ++l)
+            if (m.dims[l] != want[l]) return false;
+        return true;
+    };
+    if (!is(pl.mlp1, 2, D, 150, 100, 0, 0, 1) || !is(pl.mlp2, 2, 100, 100, 50, 0, 0, 0) ||
+        !is(pl.attention, 3, att_in, 100, 100, 1, 0, 0) || !is(pl.mlp3, 4, 56, 150, 100, 100, 1, 0))
+        return RGL_ERR_BAD_SHAPE;
+    if (pl.contraction_dtype != RGL_CONTRACT_F32) return RGL_ERR_BAD_MODE;
+    if (H >= 0 && (H < (pl.om_channel_size ? 2 : 1) || H > RGL_SARL_MAX_HUMANS)) return RGL_ERR_BAD_SHAPE;
+    return RGL_OK;
+}
+
+struct SarlLayout {
+    int KT[kSarlLayers], MT[kSarlLayers];
+    long long off[kSarlLayers], total;      // floats
+};
+
+inline SarlLayout sarl_layout(const SarlPlanner& pl) {
+    SarlLayout L;
+    const int D = 13 + sarl_map_floats(pl);
+    const int kt0 = (D + 15) / 16, ka = pl.with_global_state ? 2 * kT100 : kT100;
+    const int KT[kSarlLayers] = {kt0, kT150, kT100, kT100, ka, kT100, kT100, 1 + kT50, kT150, kT100, kT100};
+    const int MT[kSarlLayers] = {kT150, kT100, kT100, kT50, kT100, kT100, 1, kT150, kT100, kT100, 1};
+    for (int l = 0; l < kSarlLayers; ++l) {
+        L.KT[l] = KT[l];
+        L.MT[l] = MT[l];
+        L.off[l] = sarl_layer_offset(kt0, pl.with_global_state != 0, l);
+    }
+    L.total = L.off[kSarlLayers - 1] + (long long)MT[kSarlLayers - 1] * KT[kSarlLayers - 1] * 256 + MT[kSarlLayers - 1] * 16;
+    return L;
+}
+
+int launch_sarl_pack(const SarlPlanner& pl, const SarlLayout& L, float* packed, hipStream_t st) {
+    SarlPackArgs pa;
+    const RglMlp* ms[4] = {&pl.mlp1, &pl.mlp2, &pl.attention, &pl.mlp3};
+    int l = 0;
+    for (int m = 0; m < 4; ++m)
+        for (int k = 0; k < ms[m]->n_layers; ++k, ++l) {
+            SarlPackJob& j = pa.job[l];
+            j.src = ms[m]->weight[k];
+            j.bias = ms[m]->bias[k];
+            j.dst = L.off[l];
+            j.K = ms[m]->dims[k];
+            j.M = ms[m]->dims[k + 1];
+            j.KT = L.KT[l];
+            j.MT = L.MT[l];
+            j.split_tile = j.KT;
+            j.split_cols = j.K;
+        }
+    if (pl.with_global_state) {     // attention.0: [mlp1 row | mean]
+        pa.job[4].split_tile = kT100;
+        pa.job[4].split_cols = 100;
+    }
+    pa.job[7].split_tile = 1;       // mlp3.0: [self6 | weighted feature]
+    pa.job[7].split_cols = 6;
+    pa.out = packed;
+    hipLaunchKernelGGL(sarl_pack_kernel, dim3(16, kSarlLayers), dim3(256), 0, st, pa);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}
+
+constexpr int kSarlWideFrom = 7;     // humans from which a workgroup is four waves: below, four one-wave workgroups' LDS fit a CU
+
+template <int KT0, bool GLOBAL, int WAVES>
+int launch_sarl_value_as(const SarlValueArgs& va, hipStream_t st) {
+    auto kern = sarl_value_kernel<KT0, GLOBAL, WAVES>;
+    const size_t lds = (size_t)va.H * kParkFloats * sizeof(float);
+    if (lds > (size_t)rgl::kLdsBytesPerCu) return RGL_ERR_LDS;
+    if (lds > 64 * 1024)
+        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // persistent: as many workgroups as the LDS lets a CU hold (at most 8 waves), each walking tiles grid apart
+    int per_cu = (int)((size_t)rgl::kLdsBytesPerCu / lds);
+    per_cu = per_cu > 8 / WAVES ? 8 / WAVES : per_cu;
+    int cap = 256 * per_cu;
+    const int asked = env_int("RGL_SARL_GRID_CAP", 0);     // tests: fewer workgroups, so that small launches walk several tiles too
+    if (asked >= 1 && asked < cap) cap = asked;
+    const int grid = va.n_tiles < cap ? va.n_tiles : cap;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, st, va);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}
+
+template <int KT0, bool GLOBAL>
+int launch_sarl_value_waves(const SarlValueArgs& va, hipStream_t st) {
+    return va.H >= kSarlWideFrom ? launch_sarl_value_as<KT0, GLOBAL, 4>(va, st) : launch_sarl_value_as<KT0, GLOBAL, 1>(va, st);
+}
+
+int launch_sarl_value(const SarlPlanner& pl, const SarlLayout& L, const float* packed, const float* rows, const float* self6,
+                      const float* hum7, const float* maps, long long S, int scenes_per_root, int H, float* value, float* attention,
+                      hipStream_t st) {
+    SarlValueArgs va;
+    va.packed = packed;
+    va.rows = rows;
+    va.self6 = self6;
+    va.hum7 = hum7;
+    va.maps = maps;
+    va.value = value;
+    va.attention = attention;
+    va.S = (int)S;
+    va.H = H;
+    va.D = 13 + sarl_map_floats(pl);
+    va.scenes_per_root = scenes_per_root;
+    va.n_tiles = (int)((S + 15) / 16);
+    const bool gs = pl.with_global_state != 0;
+    switch (L.KT[0]) {
+        case 1: return gs ? launch_sarl_value_waves<1, true>(va, st) : launch_sarl_value_waves<1, false>(va, st);
+        case 2: return gs ? launch_sarl_value_waves<2, true>(va, st) : launch_sarl_value_waves<2, false>(va, st);
+        case 3: return gs ? launch_sarl_value_waves<3, true>(va, st) : launch_sarl_value_waves<3, false>(va, st);
+        default: return gs ? launch_sarl_value_waves<4, true>(va, st) : launch_sarl_value_waves<4, false>(va, st);
+    }
+}
+
+constexpr long long kSarlMaxScenes = 1ll << 26;     // S * H * 61 stays far inside size_t; S itself inside int
+
+}  // namespace
+
+extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* humans, int B, int H, double time_step, int cell_num,
+                                       double cell_size, int om_channel_size, float* maps, rgl_stream_t stream) {
+    if ((!humans_f64 && !humans) || !maps) return RGL_ERR_NULL;
+    if (om_channel_size < 1 || om_channel_size > 3) return RGL_ERR_BAD_MODE;
+    if (B < 1 || H < 2 || H + 1 > RGL_MAX_NODES || cell_num < 1 || cell_num > 8 || !(cell_size > 0.0)) return RGL_ERR_BAD_SHAPE;
+    const long long total = (long long)B * H * cell_num * cell_num * om_channel_size;
+    if (total > (1ll << 31) - 256) return RGL_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(sarl_maps_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, humans_f64, humans, B,
+                       H, time_step, cell_num, cell_size, om_channel_size, maps);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}
+
+extern "C" size_t sarl_value_workspace_bytes(const SarlPlanner* planner) {
+    if (!planner || validate_sarl(*planner, -1)) return 0;
+    return (size_t)align_up256(sarl_layout(*planner).total * 4);
+}
+
+extern "C" int sarl_value_f32(const SarlPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
+                              int n_scenes, int scenes_per_root, int H, void* workspace, size_t workspace_bytes, float* value,
+                              float* attention, rgl_stream_t stream) {
+    if (!planner || !workspace || !value || !attention) return RGL_ERR_NULL;
+    const int rc = validate_sarl(*planner, H);
+    if (rc) return rc;
+    const SarlPlanner& pl = *planner;
+    if (!rows && (!self6 || !hum7 || (pl.om_channel_size && !maps))) return RGL_ERR_NULL;
+    if (n_scenes < 1 || n_scenes > kSarlMaxScenes) return RGL_ERR_BAD_SHAPE;
+    if (rows) scenes_per_root = 1;
+    if (scenes_per_root < 1 || n_scenes % scenes_per_root) return RGL_ERR_BAD_SHAPE;
+    if (workspace_bytes < sarl_value_workspace_bytes(planner)) return RGL_ERR_WORKSPACE;
+    const SarlLayout L = sarl_layout(pl);
+    hipStream_t st = (hipStream_t)stream;
+    const int prc = launch_sarl_pack(pl, L, (float*)workspace, st);
+    if (prc) return prc;
+    return launch_sarl_value(pl, L, (const float*)workspace, rows, self6, hum7, maps, n_scenes, scenes_per_root, H, value, attention, st);
+}
+
+extern "C" size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B, int H) {
+    if (!planner || B < 1 || validate_sarl(*planner, H)) return 0;
+    const long long S = (long long)B * planner->num_actions;
+    if (planner->num_actions < 1 || planner->num_actions > RGL_MAX_ACTIONS || S > kSarlMaxScenes) return 0;
+    return (size_t)(align_up256(S * 6 * 4) + align_up256(S * H * 7 * 4) + align_up256(S * 4) + align_up256(S * 4) + align_up256(S * H * 4) +
+                    align_up256((long long)B * H * sarl_map_floats(*planner) * 4 + 4) + align_up256(sarl_layout(*planner).total * 4));
+}
+
+extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, const float* humans, int B, int H, void* workspace,
+                                size_t workspace_bytes, float* action_values, int* best_action, float* best_value,
+                                float* best_attention, rgl_stream_t stream) {
+    if (!planner || !robot || !humans || !workspace || !action_values || !best_action) return RGL_ERR_NULL;
+    if (B < 1) return RGL_ERR_BAD_SHAPE;
+    const SarlPlanner& pl = *planner;
+    int rc = validate_sarl(pl, H);
+    if (rc) return rc;
+    const int A = pl.num_actions;
+    if (A < 1 || A > RGL_MAX_ACTIONS) return RGL_ERR_BAD_SHAPE;
+    if (pl.kinematics != RGL_HOLONOMIC && pl.kinematics != RGL_UNICYCLE) return RGL_ERR_BAD_MODE;
+    if (!pl.actions) return RGL_ERR_NULL;
+    const long long S = (long long)B * A;
+    if (S > kSarlMaxScenes) return RGL_ERR_BAD_SHAPE;
+    if (workspace_bytes < sarl_predict_workspace_bytes(planner, B, H)) return RGL_ERR_WORKSPACE;
+    char* ws = (char*)workspace;
+    float* self6 = (float*)ws;      ws += align_up256(S * 6 * 4);
+    float* hum7 = (float*)ws;       ws += align_up256(S * H * 7 * 4);
+    float* reward = (float*)ws;     ws += align_up256(S * 4);
+    float* value = (float*)ws;      ws += align_up256(S * 4);
+    float* att = (float*)ws;        ws += align_up256(S * H * 4);
+    float* maps = (float*)ws;       ws += align_up256((long long)B * H * sarl_map_floats(pl) * 4 + 4);
+    float* packed = (float*)ws;
+    hipStream_t st = (hipStream_t)stream;
+    // propagate, constant-velocity humans, rotate, reward: path G's first step as it stands
+    GcnPlanner gp = {};
+    gp.kinematics = pl.kinematics;
+    gp.num_actions = A;
+    gp.time_step = pl.time_step;
+    gp.gamma = pl.gamma;
+    gp.actions = pl.actions;
+    gp.root_robot_f64 = pl.root_robot_f64;
+    gp.root_humans_f64 = pl.root_humans_f64;
+    rc = gcn_prepare_f32(&gp, robot, humans, B, H, self6, hum7, reward, stream);
+    if (rc) return rc;
+    if (pl.om_channel_size) {       // once per root and human: without query_env the maps do not depend on the action (:52-55)
+        const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;      // as gcn_prepare_f32 chooses its source
+        rc = sarl_occupancy_maps_f32(r64 ? pl.root_humans_f64 : nullptr, humans, B, H, pl.time_step, pl.cell_num, pl.cell_size,
+                                     pl.om_channel_size, maps, stream);
+        if (rc) return rc;
+    }
+    const SarlLayout L = sarl_layout(pl);
+    rc = launch_sarl_pack(pl, L, packed, st);
+    if (rc) return rc;
+    rc = launch_sarl_value(pl, L, packed, nullptr, self6, hum7, maps, S, A, H, value, att, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sarl_select_kernel, dim3((unsigned)(((long long)B * kSelLanes + 255) / 256)), dim3(256), 0, st, robot, reward, value,
+                       att, B, A, H, pl.gamma, pl.time_step, action_values, best_action, best_value, best_attention);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}

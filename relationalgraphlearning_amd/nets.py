@@ -553,3 +553,75 @@ class ValueNetwork(_GraphCore):
                                 state[:, :, d:].contiguous(), want_A=True)
         self._A_dev = out["A"][0].detach()
         return out["value"]
+
+
+# --------------------------------------------------------------------------------------------------
+# SARL / OM-SARL module (evaluation only)
+# --------------------------------------------------------------------------------------------------
+class SarlValueNetwork(nn.Module):
+    """sarl.ValueNetwork (crowd_nav/policy/sarl.py:9-73): upstream's constructor arguments and state-dict keys
+    (mlp1.{0,2}, mlp2.{0,2}, attention.{0,2,4}, mlp3.{0,2,4,6}); `forward` is sarl_value_f32.  Evaluation only: a forward that
+    would have to record a graph for autograd raises."""
+
+    def __init__(self, input_dim, self_state_dim, mlp1_dims, mlp2_dims, mlp3_dims, attention_dims, with_global_state,
+                 cell_size, cell_num):
+        super().__init__()
+        self.input_dim = input_dim
+        self.self_state_dim = self_state_dim
+        self.global_state_dim = mlp1_dims[-1]
+        self.mlp1 = mlp(input_dim, mlp1_dims, last_relu=True)
+        self.mlp2 = mlp(mlp1_dims[-1], mlp2_dims)
+        self.with_global_state = with_global_state
+        self.attention = mlp(mlp1_dims[-1] * (2 if with_global_state else 1), attention_dims)
+        self.cell_size = cell_size
+        self.cell_num = cell_num
+        self.mlp3 = mlp(mlp2_dims[-1] + self_state_dim, mlp3_dims)
+        self.attention_weights = None
+        self._cache = _PackCache()
+        self._ws = None
+
+    def _pack(self, keep, reuse=None):
+        return tuple(pack_mlp(seq, keep, reuse) for seq in (self.mlp1, self.mlp2, self.attention, self.mlp3))
+
+    def fill_planner(self, pl):
+        """The network's share of a SarlPlanner: the four MLPs, with_global_state and the map shape the row width implies."""
+        pl.mlp1, pl.mlp2, pl.attention, pl.mlp3 = self._cache.get([self], self._pack)
+        pl.with_global_state = int(bool(self.with_global_state))
+        extra = self.input_dim - 13
+        cells = int(self.cell_num) ** 2
+        pl.cell_num = int(self.cell_num)
+        pl.cell_size = float(self.cell_size)
+        pl.om_channel_size = extra // cells if extra > 0 and cells > 0 and extra % cells == 0 else (0 if extra == 0 else -1)
+        pl.contraction_dtype = nat.CONTRACTION_DTYPES["f32"]
+        return pl
+
+    def check_no_grad(self):
+        if _needs_grad(_flat_params(self)):
+            raise NotImplementedError("SARL training is not provided yet: SarlValueNetwork has no backward pass; call it under "
+                                      "torch.no_grad() (evaluation) or freeze its parameters")
+
+    def forward(self, state_input):
+        self.check_no_grad()
+        state = state_input[0] if isinstance(state_input, tuple) else state_input
+        state = _require_device_tensor(state, "rotated joint states")
+        if state.dim() != 3 or state.shape[2] != self.input_dim:
+            raise ValueError("SarlValueNetwork takes (batch, humans, %d) rows, got %s" % (self.input_dim, tuple(state.shape)))
+        S, H = state.shape[0], state.shape[1]
+        dev = state.device
+        with torch.cuda.device(dev):
+            pl = self.fill_planner(nat.SarlPlanner())
+            lib = nat.lib()
+            need = lib.sarl_value_workspace_bytes(C.byref(pl))
+            if need == 0:
+                raise nat.NativeLibraryError("sarl_value_f32: widths outside the shipped SARL shapes (%s)" % nat.ERRORS[-1])
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            if nat.poison_workspaces():
+                self._ws.fill_(255)     # tests: NaN bit patterns wherever the kernel reads what this call has not written
+            value = torch.empty(S, 1, dtype=torch.float32, device=dev)
+            att = torch.empty(S, H, dtype=torch.float32, device=dev)
+            rc = lib.sarl_value_f32(C.byref(pl), state.data_ptr(), None, None, None, S, 1, H, self._ws.data_ptr(), self._ws.numel(),
+                                    value.data_ptr(), att.data_ptr(), _stream())
+        nat.check(rc, "sarl_value_f32")
+        self.attention_weights = att[0].cpu().numpy()       # scene 0's weights, as sarl.py:64 leaves them
+        return value

@@ -2,9 +2,11 @@
 
 Mirrors (reference paths): crowd_sim/envs/policy/policy.py:6-65 (`Policy`),
 crowd_nav/policy/model_predictive_rl.py:15-370 (`ModelPredictiveRL`), crowd_nav/policy/gcn.py:131-157 +
-multi_human_rl.py:12-112 + cadrl.py:70-138 (`GCN`), crowd_nav/policy/policy_factory.py:9-13 (registration).
+multi_human_rl.py:12-112 + cadrl.py:70-138 (`GCN`), crowd_nav/policy/policy_factory.py:9-13 (registration),
 
-`register(policy_factory)` installs the classes under the reference's keys ('model_predictive_rl', 'gcn'),
+crowd_nav/policy/sarl.py:76-99 + multi_human_rl.py:12-171 (`SARL`, evaluation only).
+
+`register(policy_factory)` installs the classes under the reference's keys ('model_predictive_rl', 'gcn', 'sarl'),
 so crowd_nav's train.py / test.py pick them up unchanged.
 """
 import logging
@@ -13,8 +15,8 @@ import numpy as np
 import torch
 
 from . import actions as act
-from .nets import RGL, ValueEstimator, StatePredictor, LinearStatePredictor, ValueNetwork
-from .rollout import TreeSearch, GcnSearch, rotate, prepare_scenes
+from .nets import RGL, ValueEstimator, StatePredictor, LinearStatePredictor, ValueNetwork, SarlValueNetwork
+from .rollout import TreeSearch, GcnSearch, SarlSearch, rotate, prepare_scenes, occupancy_maps
 
 
 class Policy(object):
@@ -605,6 +607,110 @@ class GCN(Policy):
         return rotate(joint, self.kinematics)
 
 
+class SARL(GCN):
+    """SARL / OM-SARL (crowd_nav/policy/sarl.py:76-99 over multi_human_rl.py:12-171): path G's one-step lookahead -- propagate,
+    rotate, reward, action table, greedy action for an empty crowd, all inherited from GCN -- with the attention value network and,
+    with_om, the occupancy maps appended to every human's row.  Evaluation only: no training step, no replay rows."""
+
+    def __init__(self):
+        super().__init__()
+        self.name = 'SARL'
+        self.with_om = None
+        self.cell_num = None
+        self.cell_size = None
+        self.om_channel_size = None
+        self.attention_weights = None
+
+    def configure(self, config):
+        self.set_common_parameters(config)
+        self.cell_num = config.om.cell_num                     # cadrl.py:78-80
+        self.cell_size = config.om.cell_size
+        self.om_channel_size = config.om.om_channel_size
+        sc = config.sarl
+        self.with_om = sc.with_om
+        self.multiagent_training = sc.multiagent_training
+        self.model = SarlValueNetwork(self.input_dim(), self.self_state_dim, sc.mlp1_dims, sc.mlp2_dims, sc.mlp3_dims,
+                                      sc.attention_dims, sc.with_global_state, self.cell_size, self.cell_num)
+        if self.with_om:
+            self.name = 'OM-SARL'
+        self._search = None
+        logging.info('Policy: {} {} global state'.format(self.name, 'w/' if sc.with_global_state else 'w/o'))
+
+    def input_dim(self):
+        return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
+
+    def get_attention_weights(self):
+        return self.attention_weights
+
+    def get_matrix_A(self):
+        raise AttributeError("SARL has no adjacency matrix; see get_attention_weights()")
+
+    def gcn_search(self):
+        key = (self.kinematics, self.time_step, self.gamma)
+        if self._search is None or self._search[0] != key:
+            self._search = (key, SarlSearch(self.model, act.as_array(self.action_space), self.kinematics, self.time_step, self.gamma))
+        return self._search[1]
+
+    def predict(self, state):
+        _check_ready(self)
+        if self.reach_destination(state):
+            return act.stop_action(self.kinematics)
+        if self.action_space is None:
+            self.build_action_space(state.robot_state.v_pref)
+        if not state.human_states:
+            assert self.phase != 'train'                       # multi_human_rl.py:27-31
+            self.attention_weights = list()
+            return self.select_greedy_action(state.robot_state)
+        if self.query_env:
+            raise NotImplementedError("SARL with query_env=True is not provided: the maps and rewards of the search come from the "
+                                      "constant-velocity guess only")
+        probability = np.random.random()
+        if self.phase == 'train' and probability < self.epsilon:
+            max_action = self.action_space[np.random.choice(len(self.action_space))]
+        else:
+            robot, humans = _state_rows(state)
+            r64 = torch.tensor([robot], dtype=torch.float64, device=self.device)
+            h64 = torch.tensor([humans], dtype=torch.float64, device=self.device)
+            with torch.no_grad():
+                search = self.gcn_search()
+                vals, best = search.search(r64.float(), h64.float(), roots64=(r64, h64))
+            self.action_values = [float(v) for v in vals[0].cpu()]
+            idx = int(best[0])
+            if idx < 0:
+                raise ValueError('Value network is not well trained. ')
+            max_action = self.action_space[idx]
+            self.attention_weights = search.last_attention[0].cpu().numpy()     # of the selected action (multi_human_rl.py:60-64)
+        if self.phase == 'train':
+            self.last_state = self.transform(state)
+        return max_action
+
+    def predict_batch(self, robot, humans, roots_are_joint_states=True):
+        """Additive API: robot (B,9), humans (B,H,5) device tensors -> (action index (B,), its value (B,)); the attention weights of
+        the selected actions stay on the search as last_attention (B,H)."""
+        if self.query_env:
+            raise NotImplementedError("SARL with query_env=True is not provided")
+        if self.action_space is None:
+            self.build_action_space(float(robot[0, 7]))
+        with torch.no_grad():
+            search = self.gcn_search()
+            vals, best = search.search(robot, humans)
+        return best, search.last_best_value
+
+    def build_occupancy_maps(self, human_states):
+        """(H, cell_num^2 om_channel_size) float32 device tensor: multi_human_rl.py:117-171 for a list of human states."""
+        rows = [[h.px, h.py, h.vx, h.vy, h.radius] for h in human_states]
+        if len(rows) < 2:
+            raise ValueError("need at least one array to concatenate")         # np.concatenate([]) upstream (:125-126)
+        h64 = torch.tensor([rows], dtype=torch.float64, device=self.device)
+        return occupancy_maps(h64, self.cell_num, self.cell_size, self.om_channel_size)[0]
+
+    def transform(self, state):
+        rotated = super().transform(state)
+        if self.with_om:
+            rotated = torch.cat([rotated, self.build_occupancy_maps(state.human_states)], dim=1)
+        return rotated
+
+
 def _first_strict_maximum(vals):
     """Index of the FIRST maximum of every row, -1 when no value beats -inf (all NaN / -inf): the strict `>` walk of
     multi_human_rl.py:38-64 that leaves max_action None ("Value network is not well trained"), as gcn_argmax_kernel and
@@ -620,4 +726,5 @@ def register(policy_factory):
     """Install the HIP-backed classes under the reference's registry keys."""
     policy_factory['model_predictive_rl'] = ModelPredictiveRL
     policy_factory['gcn'] = GCN
+    policy_factory['sarl'] = SARL
     return policy_factory

@@ -502,6 +502,86 @@ class GcnSearch:
         return vals, best
 
 
+class SarlSearch:
+    """One-step lookahead over the rotation-major action table with the SARL / OM-SARL attention network (sarl_predict_f32:
+    multi_human_rl.py:36-64 with sarl.py:28-73 and, for OM-SARL, the occupancy maps of :117-171)."""
+
+    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
+        if contraction_dtype != "f32":
+            raise ValueError("SARL contraction mode %r: only 'f32' (the reference's arithmetic) is offered" % (contraction_dtype,))
+        self.model = value_network
+        self.actions_np = np.ascontiguousarray(np.asarray(actions, dtype=np.float64))
+        self.kinematics = kinematics
+        self.time_step = float(time_step)
+        self.gamma = float(gamma)
+        self._dev_tables = {}
+        self._ws = _Workspace()
+        self.last_best_value = None
+        self.last_attention = None
+
+    def planner(self, dev, H, roots64=None, B=None):
+        key = str(dev)
+        if key not in self._dev_tables:
+            self._dev_tables[key] = torch.tensor(self.actions_np, dtype=torch.float64, device=dev)
+        pl = self.model.fill_planner(nat.SarlPlanner())
+        pl.kinematics = nat.KINEMATICS[self.kinematics]
+        pl.num_actions = self.actions_np.shape[0]
+        pl.time_step = self.time_step
+        pl.gamma = self.gamma
+        pl.actions = self._dev_tables[key].data_ptr()
+        if roots64 is not None:
+            r64, h64 = _check_roots64(roots64, B, H)
+            pl.root_robot_f64, pl.root_humans_f64 = r64.data_ptr(), h64.data_ptr()
+        return pl
+
+    def search(self, robot, humans, roots64=None):
+        """robot (B,9), humans (B,H,5) -> (action_values (B,A) fp32, best_action (B,) int32), device tensors; the selected action's
+        value and attention weights are kept as last_best_value (B,) / last_attention (B,H)."""
+        if self.model.input_dim > 13 and humans.shape[1] < 2:
+            # upstream: np.concatenate of an empty list (multi_human_rl.py:125-126) -- on the host, before anything is launched
+            raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
+        robot = _require_device_tensor(robot, "robot states")
+        humans = _require_device_tensor(humans, "human states")
+        B, H, A = robot.shape[0], humans.shape[1], self.actions_np.shape[0]
+        dev = robot.device
+        with torch.cuda.device(dev):
+            pl = self.planner(dev, H, roots64, B)
+            lib = nat.lib()
+            need = lib.sarl_predict_workspace_bytes(C.byref(pl), B, H)
+            if need == 0:
+                nat.check(-1, "sarl_predict_f32 (H = %d of at most %d; the widths and map sizes of the shipped shapes)"
+                          % (H, nat.SARL_MAX_HUMANS))
+            ws = self._ws.get(need, dev)
+            vals = torch.empty(B, A, dtype=torch.float32, device=dev)
+            best = torch.empty(B, dtype=torch.int32, device=dev)
+            best_value = torch.empty(B, dtype=torch.float32, device=dev)
+            att = torch.empty(B, H, dtype=torch.float32, device=dev)
+            rc = lib.sarl_predict_f32(C.byref(pl), robot.data_ptr(), humans.data_ptr(), B, H, ws.data_ptr(), ws.numel(),
+                                      vals.data_ptr(), best.data_ptr(), best_value.data_ptr(), att.data_ptr(), _stream())
+        nat.check(rc, "sarl_predict_f32")
+        self.last_best_value = best_value
+        self.last_attention = att
+        return vals, best
+
+
+def occupancy_maps(humans64, cell_num=4, cell_size=1.0, om_channel_size=3, time_step=0.0):
+    """sarl_occupancy_maps_f32: humans (B,H,5) float64 device tensor -> maps (B,H,cell_num^2 om_channel_size) float32 of the states
+    moved on by `time_step` at constant velocity (MultiHumanRL.build_occupancy_maps, multi_human_rl.py:117-171)."""
+    if not (torch.is_tensor(humans64) and humans64.is_cuda and humans64.dtype == torch.float64 and humans64.dim() == 3
+            and humans64.shape[2] == 5):
+        raise nat.NativeLibraryError("occupancy maps take a float64 (B,H,5) CUDA(HIP) tensor (no CPU path)")
+    humans64 = humans64.contiguous()
+    B, H = humans64.shape[0], humans64.shape[1]
+    if H < 2:
+        raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
+    maps = torch.empty(B, H, int(cell_num) ** 2 * int(om_channel_size), dtype=torch.float32, device=humans64.device)
+    with torch.cuda.device(humans64.device):
+        rc = nat.lib().sarl_occupancy_maps_f32(humans64.data_ptr(), None, B, H, float(time_step), int(cell_num), float(cell_size),
+                                               int(om_channel_size), maps.data_ptr(), _stream())
+    nat.check(rc, "sarl_occupancy_maps_f32")
+    return maps
+
+
 def rotate(joint14, kinematics="holonomic"):
     """(R,14) -> (R,13) pairwise relation features on device (CADRL.rotate, cadrl.py:241-276)."""
     joint14 = _require_device_tensor(joint14, "joint states")

@@ -502,6 +502,10 @@ class VectorExplorer(object):
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None, epoch=None,
                        print_failure=False):
+        if update_memory and getattr(self.target_policy, "name", None) in ("SARL", "OM-SARL"):
+            # the rows stored below are path G's 13 relation features; SARL's replay rows carry the occupancy maps too
+            raise NotImplementedError("SARL training is not provided yet: the replay memory does not store SARL's %d-wide rows"
+                                      % self.target_policy.input_dim())
         self.policy.set_phase(phase)
         cases = self._next_cases(phase, k)
         time_limit = self.sim.cfg.time_limit

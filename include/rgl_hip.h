@@ -814,7 +814,8 @@ int crowd_step_nonstop_f64(const CrowdNonstopJob* job);
  *   2 <= H with maps (upstream's np.concatenate raises for a single human), 1 <= H without, H <= RGL_SARL_MAX_HUMANS;
  *   contraction_dtype RGL_CONTRACT_F32 only; n_scenes = B num_actions <= 2^26.
  * ------------------------------------------------------------------------------------------- */
-#define RGL_SARL_MAX_HUMANS 20      /* the value kernel parks a wave's per-human mlp1 outputs in LDS: 7 424 bytes per human */
+#define RGL_SARL_MAX_HUMANS 127     /* RGL_MAX_NODES - 1, the limit of gcn_prepare_f32.  The value kernel parks a tile's per-human
+                                     * mlp1 outputs (7 424 bytes per human): in LDS up to 20 humans, above that in the workspace. */
 
 typedef struct SarlPlanner {
     RglMlp mlp1, mlp2, attention, mlp3;     /* sarl.ValueNetwork.{mlp1, mlp2, attention, mlp3}                          */
@@ -845,14 +846,21 @@ int sarl_occupancy_maps_f32(const double* humans_f64, const float* humans, int B
                             double cell_size, int om_channel_size, float* maps, rgl_stream_t stream);
 
 /* The value network for n_scenes scenes of H humans in one launch (plus one that lays the weights out as MFMA fragments in
- * `workspace`, device, >= sarl_value_workspace_bytes(); 0 = the planner is outside the supported shapes).  Input, either
+ * `workspace`, device, >= sarl_value_workspace_bytes_for(planner, n_scenes, H); 0 = outside the supported shapes).
+ * sarl_value_workspace_bytes(planner) is the packed weights alone: enough for H <= 20, whose parking slots are LDS.  For
+ * 21 <= H <= RGL_SARL_MAX_HUMANS the workspace also holds the parking slots, H x 7 424 bytes for each workgroup of the launch's
+ * persistent grid (at most 512 workgroups), and sarl_value_f32 returns RGL_ERR_WORKSPACE when given less.  The environment switch
+ * RGL_SARL_PARK=global (read per launch, like RGL_SARL_GRID_CAP) takes that form at any H, and the size functions that take H
+ * then report it for small H too.  Input, either
  *   rows   device [n_scenes][H][D]: the rows sarl.ValueNetwork.forward takes (the other three pointers are not read), or
  *   self6  device [n_scenes][6], hum7 device [n_scenes][H][7] as gcn_prepare_f32 writes them, and (D > 13) maps device
  *          [n_scenes / scenes_per_root][H][D - 13]: scene s reads the maps of root s / scenes_per_root.
- * value device [n_scenes], attention device [n_scenes][H] (the softmax weights of sarl.py:57-63).  No activation passes through
- * global memory; the last, partial tile of sixteen scenes is masked.  Reads the four MLPs, with_global_state, om_channel_size,
+ * value device [n_scenes], attention device [n_scenes][H] (the softmax weights of sarl.py:57-63).  Up to 20 humans no
+ * activation passes through global memory; above, the parked ones do, between waves of one workgroup.  The last, partial tile of
+ * sixteen scenes is masked.  Reads the four MLPs, with_global_state, om_channel_size,
  * cell_num and contraction_dtype of `planner`. */
 size_t sarl_value_workspace_bytes(const SarlPlanner* planner);
+size_t sarl_value_workspace_bytes_for(const SarlPlanner* planner, int n_scenes, int H);
 int sarl_value_f32(const SarlPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
                    int n_scenes, int scenes_per_root, int H, void* workspace, size_t workspace_bytes, float* value,
                    float* attention, rgl_stream_t stream);

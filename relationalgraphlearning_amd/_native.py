@@ -72,7 +72,7 @@ class GcnPlanner(C.Structure):
                 ("root_robot_f64", C.c_void_p), ("root_humans_f64", C.c_void_p), ("contraction_dtype", C.c_int), ("reserved", C.c_int)]
 
 
-SARL_MAX_HUMANS = 20
+SARL_MAX_HUMANS = 127
 
 
 class SarlPlanner(C.Structure):
@@ -240,6 +240,7 @@ SIGNATURES = {
     "sarl_occupancy_maps_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
                                           C.c_void_p, C.c_void_p]),
     "sarl_value_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner)]),
+    "sarl_value_workspace_bytes_for": (C.c_size_t, [C.POINTER(SarlPlanner), C.c_int, C.c_int]),
     "sarl_value_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sarl_predict_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner), C.c_int, C.c_int]),
@@ -253,7 +254,7 @@ SIGNATURES = {
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
-            "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32"}
+            "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for"}
 
 _lib = None
 

@@ -10,8 +10,12 @@
 // element-wise over the wave's own tiles.  The A fragments of that k order are laid out once per call by sarl_pack_kernel
 // ([t][mt][lane][i]: one 16-byte load per lane serves four MFMAs) and read from L2: the four MLPs hold 415 KB, more than a CU's LDS.
 // The LDS parks the per-human mlp1 outputs of a tile's scenes (they are read twice: by the mean, and by mlp2 / attention once the
-// mean is known), later overwritten by the mlp2 outputs and the attention score of the same human: 7 424 bytes per human, which is
-// what bounds H (RGL_SARL_MAX_HUMANS).  A workgroup is one wave below kSarlWideFrom humans and four waves sharing one tile above.
+// mean is known), later overwritten by the mlp2 outputs and the attention score of the same human: 7 424 bytes per human, which a
+// CU's LDS holds for up to kSarlLdsHumans humans.  Above that the same slots live in a region of the workspace per workgroup (the
+// kernel's SarlValueGlobalArgs form); what bounds H is then gcn_prepare_f32's H + 1 <= RGL_MAX_NODES (RGL_SARL_MAX_HUMANS).  A
+// workgroup is one wave below kSarlWideFrom humans and four waves sharing one tile above.
+#include <cstring>
+
 #include "rgl_mfma.h"
 
 namespace {
@@ -112,14 +116,34 @@ struct SarlValueArgs {
     float* attention;           // [S][H]
     int S, H, D, scenes_per_root, n_tiles;
 };
+struct SarlValueGlobalArgs : SarlValueArgs {
+    float* park;                // the parking slots of the global form: [grid][H][kParkRegs][64]
+};
+
+// The barrier between a tile's passes over its parking slots.  The slots of the global form are written and read with plain vector
+// stores and loads by waves of ONE workgroup, hence through one CU's L1 and in the order the barrier sets; every wave drains its own
+// stores (and the loads a later store to the same slot must not overtake) before it arrives.
+template <bool GPARK>
+__device__ __forceinline__ void sarl_park_barrier() {
+    if constexpr (GPARK) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
 
 // KT0: 16-feature tiles of a row (input_dim 13 | 29 | 45 | 61); GLOBAL: with_global_state; WAVES: waves of the workgroup, which
 // all work on the same sixteen scenes -- wave w takes the humans h = w, w + WAVES, .. through mlp1 and through mlp2 / attention, and
 // the waves take turns with a tile's softmax, weighted sum and mlp3.  One wave per workgroup while four such workgroups' parking
 // space fits a CU; at larger H a one-wave workgroup would leave SIMDs idle behind its LDS.
-template <int KT0, bool GLOBAL, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueArgs va) {
-    extern __shared__ float park[];         // [H][kParkRegs][64]
+// ARGS = SarlValueGlobalArgs: the form for more humans than a CU's LDS parks (and for any H under RGL_SARL_PARK=global).  `park` is
+// then the workgroup's own region of the workspace instead of its LDS -- the same slots at the same offsets, the same passes and
+// barriers, hence the same bits.  No other workgroup touches the region, and a workgroup reads no slot it has not written for the
+// tile at hand.
+template <int KT0, bool GLOBAL, int WAVES, class ARGS = SarlValueArgs>
+__global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const ARGS va) {
+    constexpr bool GPARK = std::is_same<ARGS, SarlValueGlobalArgs>::value;
+    extern __shared__ float park_lds[];
+    float* park;                            // [H][kParkRegs][64]
+    if constexpr (GPARK) park = va.park + (size_t)blockIdx.x * ((size_t)va.H * kParkFloats);
+    else park = park_lds;
     const int wave = threadIdx.x >> 6;
     const unsigned lane = threadIdx.x & 63;
     const int g = lane >> 4, n = lane & 15;
@@ -162,7 +186,7 @@ __global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueA
 #pragma unroll
                 for (int i = 0; i < 4; ++i) slot[(4 * r + i) * 64] = y[r][i];
         }
-        __syncthreads();
+        sarl_park_barrier<GPARK>();
         f32x4 mean[kT100];
         if constexpr (GLOBAL) {     // torch.mean over the humans: the sum in human order, divided
 #pragma unroll
@@ -179,7 +203,7 @@ __global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueA
             for (int r = 0; r < kT100; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) mean[r][i] = mean[r][i] / fh;
-            if (WAVES > 1) __syncthreads();     // every wave has read every slot before any slot changes its content
+            if (WAVES > 1) sarl_park_barrier<GPARK>();     // every wave has read every slot before any slot changes its content
         }
 
         // ---- mlp2 and the attention score per human; the slot now keeps the mlp2 output and the score ----
@@ -214,7 +238,7 @@ __global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueA
                     for (int i = 0; i < 4; ++i) slot[(4 * r + i) * 64] = feat[r][i];
             }
         }
-        __syncthreads();        // scores and mlp2 outputs of every human are in place (one wave: lanes 0..15 wrote the scores)
+        sarl_park_barrier<GPARK>();        // scores and mlp2 outputs of every human are in place (one wave: lanes 0..15 wrote the scores)
 
         // ---- softmax over the humans (sarl.py:57-63 with an all-ones mask), weighted sum of the mlp2 outputs: one wave's turn ----
         const bool mine = wave == turn % WAVES;
@@ -236,7 +260,7 @@ __global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueA
                     for (int i = 0; i < 4; ++i) joint[1 + r][i] = f32_add(joint[1 + r][i], f32_mul(w, slot[(4 * r + i) * 64]));
             }
         }
-        __syncthreads();        // the next tile's parking waits for these reads; mlp3 below touches no LDS
+        sarl_park_barrier<GPARK>();        // the next tile's parking waits for these reads; mlp3 below touches no LDS
         if (mine) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {       // the six self features of the first row (sarl.py:42), tile 0 of mlp3's input
@@ -253,16 +277,19 @@ __global__ __launch_bounds__(64 * WAVES) void sarl_value_kernel(const SarlValueA
     }
 }
 
-// One thread per (root, human, slot) of the maps: multi_human_rl.py:117-171 in float64, every operation rounded on its own, the
-// other humans walked in list order.  The states are the roots' next human states p + v dt (dt = 0: the states themselves).
-__global__ __launch_bounds__(256) void sarl_maps_kernel(const double* __restrict__ humans64, const float* __restrict__ humans32, int B, int H, double dt,
+constexpr int kMapsMaxHumans = RGL_MAX_NODES - 1;
+
+// One wave per (root, human i) of the maps: multi_human_rl.py:117-171 in float64, every operation rounded on its own.  The lanes
+// first take the other humans j one each -- the cell j falls into (or none) and j's velocity in i's frame, computed once and left in
+// LDS -- then a slot each, walking the j in list order over those records: the sums and counts of a slot form as upstream's lists
+// do.  The states are the roots' next human states p + v dt (dt = 0: the states themselves).
+__global__ __launch_bounds__(64) void sarl_maps_kernel(const double* __restrict__ humans64, const float* __restrict__ humans32, int B, int H, double dt,
                                  int cell_num, double cell_size, int channels, float* __restrict__ maps) {
 #pragma clang fp contract(off)
+    __shared__ double pair_vx[kMapsMaxHumans], pair_vy[kMapsMaxHumans];
+    __shared__ int pair_cell[kMapsMaxHumans];       // -1: j == i, or j outside i's grid
     const int n_slots = cell_num * cell_num * channels;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)B * H * n_slots) return;
-    const int slot = (int)(idx % n_slots);
-    const long long bi = idx / n_slots;
+    const long long bi = blockIdx.x;
     const int i = (int)(bi % H);
     const long long b = bi / H;
     auto HB = [&](int j, int k) {
@@ -272,34 +299,51 @@ __global__ __launch_bounds__(256) void sarl_maps_kernel(const double* __restrict
     const double px = HB(i, 0) + HB(i, 2) * dt, py = HB(i, 1) + HB(i, 3) * dt;
     const double own_angle = atan2(HB(i, 3), HB(i, 2));
     const double half = (double)cell_num / 2.0;
-    double sum = 0.0;
-    int count = 0;
-    for (int j = 0; j < H; ++j) {
-        if (j == i) continue;
-        const double ox = (HB(j, 0) + HB(j, 2) * dt) - px, oy = (HB(j, 1) + HB(j, 3) * dt) - py;
-        const double rot = atan2(oy, ox) - own_angle;
-        const double dist = sqrt(ox * ox + oy * oy);
-        const double xi = floor(cos(rot) * dist / cell_size + half), yi = floor(sin(rot) * dist / cell_size + half);
-        if (!(xi >= 0.0 && xi < (double)cell_num && yi >= 0.0 && yi < (double)cell_num)) continue;
-        const int cell = cell_num * (int)yi + (int)xi;
-        if (channels == 1) {
-            if (cell == slot) count = 1;
-            continue;
+    for (int j = threadIdx.x; j < H; j += 64) {
+        int cell = -1;
+        double ovx = 0.0, ovy = 0.0;
+        if (j != i) {
+            const double ox = (HB(j, 0) + HB(j, 2) * dt) - px, oy = (HB(j, 1) + HB(j, 3) * dt) - py;
+            const double rot = atan2(oy, ox) - own_angle;
+            const double dist = sqrt(ox * ox + oy * oy);
+            const double xi = floor(cos(rot) * dist / cell_size + half), yi = floor(sin(rot) * dist / cell_size + half);
+            if (xi >= 0.0 && xi < (double)cell_num && yi >= 0.0 && yi < (double)cell_num) {
+                cell = cell_num * (int)yi + (int)xi;
+                if (channels != 1) {
+                    const double vrot = atan2(HB(j, 3), HB(j, 2)) - own_angle;
+                    const double speed = sqrt(HB(j, 2) * HB(j, 2) + HB(j, 3) * HB(j, 3));
+                    ovx = cos(vrot) * speed;
+                    ovy = sin(vrot) * speed;
+                }
+            }
         }
-        const double vrot = atan2(HB(j, 3), HB(j, 2)) - own_angle;
-        const double speed = sqrt(HB(j, 2) * HB(j, 2) + HB(j, 3) * HB(j, 3));
-        const double ovx = cos(vrot) * speed, ovy = sin(vrot) * speed;
-        // the slot base is 2 * cell for two AND three channels (:159-164)
-        if (channels == 2) {
-            if (slot == 2 * cell) { sum += ovx; ++count; }
-            else if (slot == 2 * cell + 1) { sum += ovy; ++count; }
-        } else {
-            if (slot == 2 * cell) { sum += 1.0; ++count; }
-            else if (slot == 2 * cell + 1) { sum += ovx; ++count; }
-            else if (slot == 2 * cell + 2) { sum += ovy; ++count; }
-        }
+        pair_cell[j] = cell;
+        pair_vx[j] = ovx;
+        pair_vy[j] = ovy;
     }
-    maps[idx] = channels == 1 ? (count ? 1.f : 0.f) : (count ? (float)(sum / (double)count) : 0.f);
+    __syncthreads();
+    for (int slot = threadIdx.x; slot < n_slots; slot += 64) {
+        double sum = 0.0;
+        int count = 0;
+        for (int j = 0; j < H; ++j) {
+            const int cell = pair_cell[j];
+            if (cell < 0) continue;
+            if (channels == 1) {
+                if (cell == slot) count = 1;
+                continue;
+            }
+            // the slot base is 2 * cell for two AND three channels (:159-164)
+            if (channels == 2) {
+                if (slot == 2 * cell) { sum += pair_vx[j]; ++count; }
+                else if (slot == 2 * cell + 1) { sum += pair_vy[j]; ++count; }
+            } else {
+                if (slot == 2 * cell) { sum += 1.0; ++count; }
+                else if (slot == 2 * cell + 1) { sum += pair_vx[j]; ++count; }
+                else if (slot == 2 * cell + 2) { sum += pair_vy[j]; ++count; }
+            }
+        }
+        maps[(size_t)bi * n_slots + slot] = channels == 1 ? (count ? 1.f : 0.f) : (count ? (float)(sum / (double)count) : 0.f);
+    }
 }
 
 constexpr int kSelLanes = 16;
@@ -447,14 +491,51 @@ int launch_sarl_value_as(const SarlValueArgs& va, hipStream_t st) {
     return RGL_OK;
 }
 
+constexpr int kSarlLdsHumans = 20;      // humans whose slots a CU's LDS holds (148 KB of 160 KB); above, the slots live in the workspace
+constexpr int kSarlGlobalWaves = 4;     // waves of a workgroup of the global form, at any H
+constexpr int kSarlGlobalPerCu = 2;     // workgroups of the global form per CU: what its registers allow (profiles/sarl_dense.txt)
+
+// RGL_SARL_PARK=global (read per launch; tests): the global form at any H.  Anything else: LDS up to kSarlLdsHumans humans.
+inline bool sarl_parks_globally(int H) {
+    if (H > kSarlLdsHumans) return true;
+    const char* e = getenv("RGL_SARL_PARK");
+    return e && !strcmp(e, "global");
+}
+
+inline int sarl_global_grid(long long n_tiles) {
+    int cap = 256 * kSarlGlobalPerCu;
+    const int asked = env_int("RGL_SARL_GRID_CAP", 0);
+    if (asked >= 1 && asked < cap) cap = asked;
+    return n_tiles < cap ? (int)n_tiles : cap;
+}
+
+// bytes of the parking regions a launch over S scenes of H humans uses: one per workgroup of its grid; 0 for the LDS form
+inline long long sarl_park_bytes(long long S, int H) {
+    if (!sarl_parks_globally(H)) return 0;
+    return align_up256((long long)sarl_global_grid((S + 15) / 16) * H * kParkFloats * (long long)sizeof(float));
+}
+
 template <int KT0, bool GLOBAL>
-int launch_sarl_value_waves(const SarlValueArgs& va, hipStream_t st) {
+int launch_sarl_value_global(const SarlValueArgs& va, float* park, hipStream_t st) {
+    SarlValueGlobalArgs ga;
+    static_cast<SarlValueArgs&>(ga) = va;
+    ga.park = park;
+    hipLaunchKernelGGL((sarl_value_kernel<KT0, GLOBAL, kSarlGlobalWaves, SarlValueGlobalArgs>), dim3(sarl_global_grid(va.n_tiles)),
+                       dim3(64 * kSarlGlobalWaves), 0, st, ga);
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
+}
+
+template <int KT0, bool GLOBAL>
+int launch_sarl_value_waves(const SarlValueArgs& va, float* park, hipStream_t st) {
+    if (park) return launch_sarl_value_global<KT0, GLOBAL>(va, park, st);
     return va.H >= kSarlWideFrom ? launch_sarl_value_as<KT0, GLOBAL, 4>(va, st) : launch_sarl_value_as<KT0, GLOBAL, 1>(va, st);
 }
 
+// park / park_bytes: the workspace behind the packed weights, used (and required) where sarl_parks_globally(H)
 int launch_sarl_value(const SarlPlanner& pl, const SarlLayout& L, const float* packed, const float* rows, const float* self6,
                       const float* hum7, const float* maps, long long S, int scenes_per_root, int H, float* value, float* attention,
-                      hipStream_t st) {
+                      float* park, size_t park_bytes, hipStream_t st) {
     SarlValueArgs va;
     va.packed = packed;
     va.rows = rows;
@@ -468,12 +549,14 @@ int launch_sarl_value(const SarlPlanner& pl, const SarlLayout& L, const float* p
     va.D = 13 + sarl_map_floats(pl);
     va.scenes_per_root = scenes_per_root;
     va.n_tiles = (int)((S + 15) / 16);
+    if (!sarl_parks_globally(H)) park = nullptr;
+    else if (!park || park_bytes < (size_t)sarl_park_bytes(S, H)) return RGL_ERR_WORKSPACE;
     const bool gs = pl.with_global_state != 0;
     switch (L.KT[0]) {
-        case 1: return gs ? launch_sarl_value_waves<1, true>(va, st) : launch_sarl_value_waves<1, false>(va, st);
-        case 2: return gs ? launch_sarl_value_waves<2, true>(va, st) : launch_sarl_value_waves<2, false>(va, st);
-        case 3: return gs ? launch_sarl_value_waves<3, true>(va, st) : launch_sarl_value_waves<3, false>(va, st);
-        default: return gs ? launch_sarl_value_waves<4, true>(va, st) : launch_sarl_value_waves<4, false>(va, st);
+        case 1: return gs ? launch_sarl_value_waves<1, true>(va, park, st) : launch_sarl_value_waves<1, false>(va, park, st);
+        case 2: return gs ? launch_sarl_value_waves<2, true>(va, park, st) : launch_sarl_value_waves<2, false>(va, park, st);
+        case 3: return gs ? launch_sarl_value_waves<3, true>(va, park, st) : launch_sarl_value_waves<3, false>(va, park, st);
+        default: return gs ? launch_sarl_value_waves<4, true>(va, park, st) : launch_sarl_value_waves<4, false>(va, park, st);
     }
 }
 
@@ -488,7 +571,7 @@ extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* hu
     if (B < 1 || H < 2 || H + 1 > RGL_MAX_NODES || cell_num < 1 || cell_num > 8 || !(cell_size > 0.0)) return RGL_ERR_BAD_SHAPE;
     const long long total = (long long)B * H * cell_num * cell_num * om_channel_size;
     if (total > (1ll << 31) - 256) return RGL_ERR_BAD_SHAPE;
-    hipLaunchKernelGGL(sarl_maps_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, humans_f64, humans, B,
+    hipLaunchKernelGGL(sarl_maps_kernel, dim3((unsigned)((long long)B * H)), dim3(64), 0, (hipStream_t)stream, humans_f64, humans, B,
                        H, time_step, cell_num, cell_size, om_channel_size, maps);
     RGL_LAUNCH_CHECK();
     return RGL_OK;
@@ -497,6 +580,11 @@ extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* hu
 extern "C" size_t sarl_value_workspace_bytes(const SarlPlanner* planner) {
     if (!planner || validate_sarl(*planner, -1)) return 0;
     return (size_t)align_up256(sarl_layout(*planner).total * 4);
+}
+
+extern "C" size_t sarl_value_workspace_bytes_for(const SarlPlanner* planner, int n_scenes, int H) {
+    if (!planner || n_scenes < 1 || n_scenes > kSarlMaxScenes || validate_sarl(*planner, H)) return 0;
+    return (size_t)(align_up256(sarl_layout(*planner).total * 4) + sarl_park_bytes(n_scenes, H));
 }
 
 extern "C" int sarl_value_f32(const SarlPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
@@ -510,12 +598,14 @@ extern "C" int sarl_value_f32(const SarlPlanner* planner, const float* rows, con
     if (n_scenes < 1 || n_scenes > kSarlMaxScenes) return RGL_ERR_BAD_SHAPE;
     if (rows) scenes_per_root = 1;
     if (scenes_per_root < 1 || n_scenes % scenes_per_root) return RGL_ERR_BAD_SHAPE;
-    if (workspace_bytes < sarl_value_workspace_bytes(planner)) return RGL_ERR_WORKSPACE;
+    const size_t packed_bytes = sarl_value_workspace_bytes(planner);
+    if (workspace_bytes < packed_bytes + (size_t)sarl_park_bytes(n_scenes, H)) return RGL_ERR_WORKSPACE;
     const SarlLayout L = sarl_layout(pl);
     hipStream_t st = (hipStream_t)stream;
     const int prc = launch_sarl_pack(pl, L, (float*)workspace, st);
     if (prc) return prc;
-    return launch_sarl_value(pl, L, (const float*)workspace, rows, self6, hum7, maps, n_scenes, scenes_per_root, H, value, attention, st);
+    return launch_sarl_value(pl, L, (const float*)workspace, rows, self6, hum7, maps, n_scenes, scenes_per_root, H, value, attention,
+                             (float*)((char*)workspace + packed_bytes), workspace_bytes - packed_bytes, st);
 }
 
 extern "C" size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B, int H) {
@@ -523,7 +613,8 @@ extern "C" size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B
     const long long S = (long long)B * planner->num_actions;
     if (planner->num_actions < 1 || planner->num_actions > RGL_MAX_ACTIONS || S > kSarlMaxScenes) return 0;
     return (size_t)(align_up256(S * 6 * 4) + align_up256(S * H * 7 * 4) + align_up256(S * 4) + align_up256(S * 4) + align_up256(S * H * 4) +
-                    align_up256((long long)B * H * sarl_map_floats(*planner) * 4 + 4) + align_up256(sarl_layout(*planner).total * 4));
+                    align_up256((long long)B * H * sarl_map_floats(*planner) * 4 + 4) + align_up256(sarl_layout(*planner).total * 4) +
+                    sarl_park_bytes(S, H));
 }
 
 extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, const float* humans, int B, int H, void* workspace,
@@ -548,7 +639,9 @@ extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, 
     float* value = (float*)ws;      ws += align_up256(S * 4);
     float* att = (float*)ws;        ws += align_up256(S * H * 4);
     float* maps = (float*)ws;       ws += align_up256((long long)B * H * sarl_map_floats(pl) * 4 + 4);
-    float* packed = (float*)ws;
+    float* packed = (float*)ws;     ws += align_up256(sarl_layout(pl).total * 4);
+    float* park = (float*)ws;
+    const size_t park_bytes = workspace_bytes - (size_t)(ws - (char*)workspace);
     hipStream_t st = (hipStream_t)stream;
     // propagate, constant-velocity humans, rotate, reward: path G's first step as it stands
     GcnPlanner gp = {};
@@ -570,7 +663,7 @@ extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, 
     const SarlLayout L = sarl_layout(pl);
     rc = launch_sarl_pack(pl, L, packed, st);
     if (rc) return rc;
-    rc = launch_sarl_value(pl, L, packed, nullptr, self6, hum7, maps, S, A, H, value, att, st);
+    rc = launch_sarl_value(pl, L, packed, nullptr, self6, hum7, maps, S, A, H, value, att, park, park_bytes, st);
     if (rc) return rc;
     hipLaunchKernelGGL(sarl_select_kernel, dim3((unsigned)(((long long)B * kSelLanes + 255) / 256)), dim3(256), 0, st, robot, reward, value,
                        att, B, A, H, pl.gamma, pl.time_step, action_values, best_action, best_value, best_attention);

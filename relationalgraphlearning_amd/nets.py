@@ -611,9 +611,10 @@ class SarlValueNetwork(nn.Module):
         with torch.cuda.device(dev):
             pl = self.fill_planner(nat.SarlPlanner())
             lib = nat.lib()
-            need = lib.sarl_value_workspace_bytes(C.byref(pl))
-            if need == 0:
+            if lib.sarl_value_workspace_bytes(C.byref(pl)) == 0:
                 raise nat.NativeLibraryError("sarl_value_f32: widths outside the shipped SARL shapes (%s)" % nat.ERRORS[-1])
+            # the packed weights and, above 20 humans, the parking region of the launch's grid; 0: H itself is refused below
+            need = lib.sarl_value_workspace_bytes_for(C.byref(pl), S, H) or lib.sarl_value_workspace_bytes(C.byref(pl))
             if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
             if nat.poison_workspaces():

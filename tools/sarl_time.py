@@ -1,7 +1,13 @@
-"""Times the SARL / OM-SARL one-step search on the MI355X: 2 048 roots x 81 actions at H = 5 and H = 19, per launch of
-sarl_predict_f32 (prepare, maps, weight layout, value network, selection), HIP events after a warm-up of every timed shape.
+"""Times the SARL / OM-SARL one-step search on the MI355X: 2 048 roots x 81 actions at H = 5 and H = 19 (--dense: 30, 50 and 127),
+per launch of sarl_predict_f32 (prepare, maps, weight layout, value network, selection), HIP events after a warm-up of every timed
+shape.
 
-    python tools/sarl_time.py [--roots 2048] [--humans 5 19] [--reps 200] [--out FILE]
+    python tools/sarl_time.py [--roots 2048] [--humans 5 19 | --dense] [--no-om] [--reps 200] [--out FILE]
+                              [--no-torch] [--no-value-forward] [--maps-only]
+
+--no-om times SARL without occupancy maps (13-wide rows); --maps-only times sarl_occupancy_maps_f32 alone (three channels), which an
+older build of the library (RGL_HIP_LIBRARY) can be asked for at any H; --no-torch / --no-value-forward leave out the comparison
+lines (an older build has no sarl_value_workspace_bytes_for for the module's forward).
 
 Reports per launch: time, the FLOPs the value kernel executes (its padded 16-wide tiles, counted from the shapes below), that rate
 as a fraction of the f32 MFMA peak (157.3 TFLOP/s), and the FLOPs the network needs unpadded.  The comparison line is the same
@@ -24,6 +30,9 @@ from relationalgraphlearning_amd.rollout import prepare_scenes, occupancy_maps  
 
 PEAK_F32_MFMA = 157.3e12
 DT = 0.25
+
+
+DENSE = [30, 50, 127]
 
 
 def flops_per_scene(H, input_dim=61, with_global_state=True, padded=False):
@@ -87,13 +96,21 @@ def main():
     ap.add_argument("--reps", type=int, default=200)     # a timed window of 0.4 s (our value forward at H = 5) to 4 s
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dense", action="store_true", help="H = 30, 50, 127 instead of --humans")
+    ap.add_argument("--no-om", action="store_true", help="SARL without occupancy maps")
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--no-value-forward", action="store_true")
+    ap.add_argument("--maps-only", action="store_true")
     args = ap.parse_args()
+    if args.dense:
+        args.humans = DENSE
     if not torch.cuda.is_available():
         raise SystemExit("sarl_time.py measures on the MI355X; no device found")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     pol = SARL()
-    pol.configure(policy_config("sarl"))
+    pol.configure(policy_config("sarl", sarl__with_om=not args.no_om))
+    D = pol.input_dim()
     pol.set_phase("test")
     pol.set_device(dev)
     pol.time_step = DT
@@ -106,11 +123,28 @@ def main():
         r64, h64 = torch.tensor(robot, device=dev), torch.tensor(humans, device=dev)
         r32, h32 = r64.float(), h64.float()
         S = args.roots * A
+
+        def maps_alone():
+            occupancy_maps(h64, 4, 1.0, 3, time_step=DT)
+
+        for _ in range(args.warmup):
+            maps_alone()
+        torch.cuda.synchronize()
+        t_maps = [timed(maps_alone, args.reps) for _ in range(3)]
+        maps_ms = float(np.median([x[0] for x in t_maps]))
+        if args.maps_only:
+            line = {"roots": args.roots, "H": H, "maps_ms": maps_ms, "maps_ms_min_max": [min(x[1] for x in t_maps), max(x[2] for x in t_maps)]}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            continue
         with torch.no_grad():
             self6, hum7, reward = prepare_scenes(r32, h32, search.actions_np, "holonomic", DT, roots64=(r64, h64))
-            maps = occupancy_maps(h64, 4, 1.0, 3, time_step=DT)
-            rows = torch.cat([self6[:, None, :].expand(S, H, 6), hum7,
-                              maps[:, None].expand(args.roots, A, H, 48).reshape(S, H, 48)], dim=2).contiguous()
+            parts = [self6[:, None, :].expand(S, H, 6), hum7]
+            if D > 13:
+                maps = occupancy_maps(h64, 4, 1.0, 3, time_step=DT)
+                parts.append(maps[:, None].expand(args.roots, A, H, 48).reshape(S, H, 48))
+            rows = torch.cat(parts, dim=2).contiguous()
+            del parts
             disc = 0.9 ** (DT * 1.0)
 
             def ours():
@@ -125,30 +159,36 @@ def main():
                 best = vals.argmax(dim=1)
                 return vals, best, w.reshape(args.roots, A, H)[torch.arange(args.roots, device=dev), best]
 
-            for fn in (ours, ours_value_only, composed):
+            fns = [ours] + ([] if args.no_value_forward else [ours_value_only]) + ([] if args.no_torch else [composed])
+            for fn in fns:
                 for _ in range(args.warmup):
                     fn()
             torch.cuda.synchronize()
-            # alternate the two so that both see the same neighbours on the machine
-            t_ours, t_val, t_torch = [], [], []
+            # alternate them so that all see the same neighbours on the machine
+            times = {fn: [] for fn in fns}
             for _ in range(3):
-                t_ours.append(timed(ours, args.reps))
-                t_val.append(timed(ours_value_only, args.reps))
-                t_torch.append(timed(composed, args.reps))
+                for fn in fns:
+                    times[fn].append(timed(fn, args.reps))
+            t_ours, t_val, t_torch = times[ours], times.get(ours_value_only), times.get(composed)
             vals, best = search.search(r32, h32, roots64=(r64, h64))
-            tv, tb, _ = composed()
-            agree = float((best.long() == tb).float().mean())
-            dv = float((vals.double() - tv).abs().max())
+            if t_torch:
+                tv, tb, _ = composed()
+                agree = float((best.long() == tb).float().mean())
+                dv = float((vals.double() - tv).abs().max())
         med = lambda t: float(np.median([x[0] for x in t]))      # noqa: E731
-        executed, needed = flops_per_scene(H, padded=True) * S, flops_per_scene(H) * S
-        line = {"roots": args.roots, "actions": A, "H": H, "scenes": S,
+        executed, needed = flops_per_scene(H, D, padded=True) * S, flops_per_scene(H, D) * S
+        line = {"roots": args.roots, "actions": A, "H": H, "input_dim": D, "scenes": S,
                 "search_ms": med(t_ours), "search_ms_min_max": [min(x[1] for x in t_ours), max(x[2] for x in t_ours)],
-                "value_forward_ms": med(t_val), "torch_composed_ms": med(t_torch),
-                "torch_ms_min_max": [min(x[1] for x in t_torch), max(x[2] for x in t_torch)],
-                "executed_gflop": executed / 1e9, "needed_gflop": needed / 1e9,
-                "search_fraction_of_f32_mfma_peak": executed / (med(t_ours) * 1e-3) / PEAK_F32_MFMA,
-                "value_forward_fraction_of_f32_mfma_peak": executed / (med(t_val) * 1e-3) / PEAK_F32_MFMA,
-                "speedup_over_torch": med(t_torch) / med(t_ours), "same_action_fraction": agree, "max_value_difference": dv}
+                "maps_ms": maps_ms, "executed_gflop": executed / 1e9, "needed_gflop": needed / 1e9,
+                "search_fraction_of_f32_mfma_peak": executed / (med(t_ours) * 1e-3) / PEAK_F32_MFMA}
+        if t_val:
+            line.update({"value_forward_ms": med(t_val),
+                         "value_forward_fraction_of_f32_mfma_peak": executed / (med(t_val) * 1e-3) / PEAK_F32_MFMA})
+        if t_torch:
+            line.update({"torch_composed_ms": med(t_torch),
+                         "torch_ms_min_max": [min(x[1] for x in t_torch), max(x[2] for x in t_torch)],
+                         "speedup_over_torch": med(t_torch) / med(t_ours), "same_action_fraction": agree, "max_value_difference": dv})
+        del rows
         print(json.dumps(line), flush=True)
         lines.append(line)
     if args.out:

@@ -804,9 +804,10 @@ typedef struct CrowdNonstopJob {
 int crowd_step_nonstop_f64(const CrowdNonstopJob* job);
 
 /* ---------------------------------------------------------------------------------------------
- * SARL / OM-SARL evaluation (ABI 8, additive): the one-step search of MultiHumanRL.predict (crowd_nav/policy/multi_human_rl.py:
+ * SARL / OM-SARL (ABI 8, additive): the one-step search of MultiHumanRL.predict (crowd_nav/policy/multi_human_rl.py:
  * 12-71) with the attention value network of crowd_nav/policy/sarl.py:28-73 and, with_om, the occupancy maps of
- * build_occupancy_maps (multi_human_rl.py:117-171).  Evaluation only: there is no backward pass.
+ * build_occupancy_maps (multi_human_rl.py:117-171).  The calls of this block evaluate; the value network's gradient is the
+ * training block below (sarl_value_train_f32 / sarl_value_backward_f32).
  *
  * Supported shapes -- every other request returns RGL_ERR_BAD_SHAPE / RGL_ERR_BAD_MODE before anything is launched:
  *   mlp1 D-150-100 (last_relu), mlp2 100-100-50, attention (200 | 100)-100-100-1 (200: with_global_state), mlp3 56-150-100-100-1;
@@ -876,6 +877,32 @@ size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B, int H);
 int sarl_predict_f32(const SarlPlanner* planner, const float* robot, const float* humans, int B, int H, void* workspace,
                      size_t workspace_bytes, float* action_values, int* best_action, float* best_value, float* best_attention,
                      rgl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SARL / OM-SARL training (ABI 8, additive): the value network over replay rows with its gradient with respect to the 22
+ * parameter tensors.  Shapes as above (f32 only, 1 <= H <= RGL_SARL_MAX_HUMANS, 2 <= H with maps), n_scenes * H <= 2^20; anything
+ * else returns RGL_ERR_BAD_SHAPE / RGL_ERR_BAD_MODE / RGL_ERR_NULL before a launch, a workspace below
+ * sarl_train_workspace_bytes(planner, n_scenes, H) (0: outside the supported shapes) RGL_ERR_WORKSPACE.
+ *   rows device [n_scenes][H][D] (what sarl.ValueNetwork.forward takes); there is no gradient with respect to them.
+ * sarl_value_train_f32 is sarl_value_f32 on those rows: the same launches, so `value` [n_scenes] and `attention` [n_scenes][H]
+ * (nullable) hold the same bits at every H -- an online network and its frozen target cannot drift apart by kernel choice.
+ * sarl_value_backward_f32 recomputes the activations row-major in the workspace (about 1 700 floats per scene and human), walks the
+ * pre-activation gradients from grad_value [n_scenes] down to mlp1 and writes every weight and bias gradient in one last launch.
+ * The gradients are OVERWRITTEN, not accumulated.  It reads nothing sarl_value_train_f32 left behind except through `planner`, so
+ * the two calls may use different workspaces of that size.  Every gradient is a sum in a fixed order (no atomics): two calls on the
+ * same inputs give the same bits.  Neither call allocates, synchronises, reads device data on the host or launches on another
+ * stream: both can be recorded into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+#define RGL_SARL_LAYERS 11          /* mlp1.{0,2} mlp2.{0,2} attention.{0,2,4} mlp3.{0,2,4,6}, in this order */
+typedef struct SarlGrads {
+    float* weight[RGL_SARL_LAYERS]; /* device [out][in]: torch's nn.Linear.weight layout */
+    float* bias[RGL_SARL_LAYERS];   /* device [out]                                      */
+} SarlGrads;
+size_t sarl_train_workspace_bytes(const SarlPlanner* planner, int n_scenes, int H);
+int sarl_value_train_f32(const SarlPlanner* planner, const float* rows, int n_scenes, int H, void* workspace, size_t workspace_bytes,
+                         float* value, float* attention, rgl_stream_t stream);
+int sarl_value_backward_f32(const SarlPlanner* planner, const float* rows, const float* grad_value, int n_scenes, int H,
+                            void* workspace, size_t workspace_bytes, const SarlGrads* grads, rgl_stream_t stream);
 
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);

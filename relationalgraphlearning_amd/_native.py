@@ -82,6 +82,13 @@ class SarlPlanner(C.Structure):
                 ("actions", C.c_void_p), ("root_robot_f64", C.c_void_p), ("root_humans_f64", C.c_void_p)]
 
 
+SARL_LAYERS = 11
+
+
+class SarlGrads(C.Structure):
+    _fields_ = [("weight", C.c_void_p * SARL_LAYERS), ("bias", C.c_void_p * SARL_LAYERS)]
+
+
 class MprlPlanner(C.Structure):
     _fields_ = [("value_graph", RglGraph), ("value_head", RglMlp), ("predictor_graph", RglGraph),
                 ("motion_head", RglMlp), ("linear_state_predictor", C.c_int), ("kinematics", C.c_int),
@@ -246,6 +253,11 @@ SIGNATURES = {
     "sarl_predict_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner), C.c_int, C.c_int]),
     "sarl_predict_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sarl_train_workspace_bytes": (C.c_size_t, [C.POINTER(SarlPlanner), C.c_int, C.c_int]),
+    "sarl_value_train_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "sarl_value_backward_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.POINTER(SarlGrads), C.c_void_p]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
@@ -254,7 +266,8 @@ SIGNATURES = {
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
-            "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for"}
+            "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
+            "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32"}
 
 _lib = None
 

@@ -1,6 +1,6 @@
 """Autograd for the HIP forward: `GraphFunction` runs rgl_graph_forward_f32 in forward and
-rgl_graph_backward_f32 in backward, so crowd_nav's trainers (MPRLTrainer / VNRLTrainer,
-crowd_nav/utils/trainer.py:110-161,199-250) can optimise the modules of `nets.py` with torch optimizers.
+rgl_graph_backward_f32 in backward, `SarlValueFunction` sarl_value_train_f32 and sarl_value_backward_f32, so crowd_nav's trainers
+(MPRLTrainer / VNRLTrainer, crowd_nav/utils/trainer.py:110-161,199-250) can optimise the modules of `nets.py` with torch optimizers.
 Gradients flow to parameters only (the states of a replay batch are data)."""
 import ctypes as C
 
@@ -105,3 +105,65 @@ class GraphFunction(torch.autograd.Function):
             for i in range(spec.n_graph_params):
                 grads_out[i] = None
         return (None, None, None) + tuple(grads_out)
+
+
+class SarlValueFunction(torch.autograd.Function):
+    """forward(model, rows (S,H,D), *model.training_parameters()) -> (value (S,1), attention weights (S,H), not differentiable).
+
+    The forward is sarl_value_train_f32 -- sarl_value_f32's launches, so an online network and its frozen target agree bit for bit
+    -- and the backward sarl_value_backward_f32, which recomputes the activations from the CURRENT parameters in the workspace the
+    forward allocated.  Neither synchronises; both can be recorded into a captured training step."""
+
+    @staticmethod
+    def forward(ctx, model, rows, *params):
+        if rows.requires_grad:
+            raise NotImplementedError("gradients with respect to the rows are not provided by the HIP path (the states of a replay "
+                                      "batch are data): detach the input")
+        S, H = rows.shape[0], rows.shape[1]
+        dev = rows.device
+        lib = nat.lib()
+        with torch.cuda.device(dev):
+            pl = model.fill_planner(nat.SarlPlanner())
+            need = lib.sarl_train_workspace_bytes(C.byref(pl), S, H)
+            if need == 0:
+                raise nat.NativeLibraryError("sarl_value_train_f32: %d scenes of %d humans with %d-wide rows are outside the shipped "
+                                             "SARL shapes (%s)" % (S, H, rows.shape[2], nat.ERRORS[-1]))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            if nat.poison_workspaces():
+                ws.fill_(255)
+            value = torch.empty(S, 1, dtype=torch.float32, device=dev)
+            att = torch.empty(S, H, dtype=torch.float32, device=dev)
+            rc = lib.sarl_value_train_f32(C.byref(pl), rows.data_ptr(), S, H, ws.data_ptr(), ws.numel(), value.data_ptr(),
+                                          att.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        nat.check(rc, "sarl_value_train_f32")
+        ctx.model, ctx.ws = model, ws
+        ctx.save_for_backward(rows)
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.mark_non_differentiable(att)
+        return value, att
+
+    @staticmethod
+    def backward(ctx, grad_value, _grad_attention):
+        model, ws = ctx.model, ctx.ws
+        rows, = ctx.saved_tensors
+        params = model.training_parameters()
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("a parameter of the SARL value network was modified in place between forward and backward "
+                               "(e.g. an optimizer step before loss.backward()): gradients would belong to other weights")
+        S, H = rows.shape[0], rows.shape[1]
+        dev = rows.device
+        gv = grad_value.contiguous().to(torch.float32)
+        out = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
+        if nat.poison_workspaces():              # tests: a kernel that reads what nobody wrote turns the gradients into NaN
+            ws.fill_(255)
+            for g in out:
+                g.fill_(float("nan"))
+        grads = nat.SarlGrads()
+        for l in range(nat.SARL_LAYERS):
+            grads.weight[l], grads.bias[l] = out[2 * l].data_ptr(), out[2 * l + 1].data_ptr()
+        with torch.cuda.device(dev):
+            pl = model.fill_planner(nat.SarlPlanner())
+            rc = nat.lib().sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), gv.data_ptr(), S, H, ws.data_ptr(), ws.numel(),
+                                                   C.byref(grads), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        nat.check(rc, "sarl_value_backward_f32")
+        return (None, None) + tuple(out)

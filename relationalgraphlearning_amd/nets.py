@@ -556,12 +556,14 @@ class ValueNetwork(_GraphCore):
 
 
 # --------------------------------------------------------------------------------------------------
-# SARL / OM-SARL module (evaluation only)
+# SARL / OM-SARL module
 # --------------------------------------------------------------------------------------------------
 class SarlValueNetwork(nn.Module):
     """sarl.ValueNetwork (crowd_nav/policy/sarl.py:9-73): upstream's constructor arguments and state-dict keys
-    (mlp1.{0,2}, mlp2.{0,2}, attention.{0,2,4}, mlp3.{0,2,4,6}); `forward` is sarl_value_f32.  Evaluation only: a forward that
-    would have to record a graph for autograd raises."""
+    (mlp1.{0,2}, mlp2.{0,2}, attention.{0,2,4}, mlp3.{0,2,4,6}).  Under `torch.no_grad()` (or with frozen parameters) `forward` is
+    sarl_value_f32.  Training is opt-in: until `enable_training()` a forward that would have to record a graph for autograd raises;
+    after it such a forward is autograd.SarlValueFunction (sarl_value_train_f32, the same launches and bits, and
+    sarl_value_backward_f32 in `backward`), for batches whose crowds all have the padded size."""
 
     def __init__(self, input_dim, self_state_dim, mlp1_dims, mlp2_dims, mlp3_dims, attention_dims, with_global_state,
                  cell_size, cell_num):
@@ -576,9 +578,31 @@ class SarlValueNetwork(nn.Module):
         self.cell_size = cell_size
         self.cell_num = cell_num
         self.mlp3 = mlp(mlp2_dims[-1] + self_state_dim, mlp3_dims)
-        self.attention_weights = None
+        self._attention = None      # scene 0's weights of the last forward: numpy, or the device row of a grad-mode forward
         self._cache = _PackCache()
         self._ws = None
+        self._trains = False
+
+    @property
+    def attention_weights(self):
+        """Scene 0's attention weights of the last forward, as sarl.py:64 leaves them (numpy).  A grad-mode forward keeps them on
+        the device -- it must not synchronise -- and they are copied to the host when read."""
+        if torch.is_tensor(self._attention):
+            self._attention = self._attention.cpu().numpy()
+        return self._attention
+
+    @attention_weights.setter
+    def attention_weights(self, value):
+        self._attention = value
+
+    def enable_training(self, flag=True):
+        """Opt in to (or out of) the backward pass: see the class docstring.  Returns the module."""
+        self._trains = bool(flag)
+        return self
+
+    def training_parameters(self):
+        """The 22 parameter tensors in the order of SarlGrads: weight, bias of mlp1.{0,2} mlp2.{0,2} attention.{0,2,4} mlp3.{0,2,4,6}."""
+        return [p for seq in (self.mlp1, self.mlp2, self.attention, self.mlp3) for lin in _linears(seq) for p in (lin.weight, lin.bias)]
 
     def _pack(self, keep, reuse=None):
         return tuple(pack_mlp(seq, keep, reuse) for seq in (self.mlp1, self.mlp2, self.attention, self.mlp3))
@@ -595,17 +619,38 @@ class SarlValueNetwork(nn.Module):
         pl.contraction_dtype = nat.CONTRACTION_DTYPES["f32"]
         return pl
 
-    def check_no_grad(self):
-        if _needs_grad(_flat_params(self)):
-            raise NotImplementedError("SARL training is not provided yet: SarlValueNetwork has no backward pass; call it under "
-                                      "torch.no_grad() (evaluation) or freeze its parameters")
+    def descriptor(self):
+        """Repack the k-major weight copies now (in place) where the parameters moved: what a trainer calls on a frozen target copy
+        whose captured step does not contain the repack."""
+        return self.fill_planner(nat.SarlPlanner())
 
-    def forward(self, state_input):
-        self.check_no_grad()
-        state = state_input[0] if isinstance(state_input, tuple) else state_input
+    def check_no_grad(self):
+        if not self._trains and _needs_grad(_flat_params(self)):
+            raise NotImplementedError("SARL training is not provided by this module until enable_training() is called: call it "
+                                      "under torch.no_grad() (evaluation), freeze its parameters, or opt in with "
+                                      "model.enable_training() / policy.enable_training()")
+
+    def _check_rows(self, state):
         state = _require_device_tensor(state, "rotated joint states")
         if state.dim() != 3 or state.shape[2] != self.input_dim:
             raise ValueError("SarlValueNetwork takes (batch, humans, %d) rows, got %s" % (self.input_dim, tuple(state.shape)))
+        return state
+
+    def forward(self, state_input):
+        self.check_no_grad()
+        state, lengths = state_input if isinstance(state_input, tuple) else (state_input, None)
+        if _needs_grad(_flat_params(self)):
+            if lengths is not None and torch.is_tensor(state) and state.dim() == 3 and \
+                    not bool((torch.as_tensor(lengths) == state.shape[1]).all()):
+                # the kernels implement the all-ones mask only: a padded row would pass mlp1 and count in the mean (sarl.py:57-63)
+                raise ValueError("mixed crowd sizes are not trained: every sequence of a batch must have the padded length %d, got "
+                                 "lengths %s" % (state.shape[1], torch.as_tensor(lengths).tolist()))
+            from .autograd import SarlValueFunction
+            state = self._check_rows(state)
+            value, att = SarlValueFunction.apply(self, state, *self.training_parameters())
+            self._attention = att[0].detach()       # stays on the device: no synchronisation in a training step
+            return value
+        state = self._check_rows(state)
         S, H = state.shape[0], state.shape[1]
         dev = state.device
         with torch.cuda.device(dev):
@@ -624,5 +669,7 @@ class SarlValueNetwork(nn.Module):
             rc = lib.sarl_value_f32(C.byref(pl), state.data_ptr(), None, None, None, S, 1, H, self._ws.data_ptr(), self._ws.numel(),
                                     value.data_ptr(), att.data_ptr(), _stream())
         nat.check(rc, "sarl_value_f32")
-        self.attention_weights = att[0].cpu().numpy()       # scene 0's weights, as sarl.py:64 leaves them
+        # scene 0's weights, as sarl.py:64 leaves them; a frozen target evaluated inside a step that is being recorded into a
+        # hipGraph cannot copy to the host: the row stays on the device until it is read
+        self._attention = att[0] if torch.cuda.is_current_stream_capturing() else att[0].cpu().numpy()
         return value

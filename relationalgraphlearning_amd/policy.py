@@ -4,7 +4,7 @@ Mirrors (reference paths): crowd_sim/envs/policy/policy.py:6-65 (`Policy`),
 crowd_nav/policy/model_predictive_rl.py:15-370 (`ModelPredictiveRL`), crowd_nav/policy/gcn.py:131-157 +
 multi_human_rl.py:12-112 + cadrl.py:70-138 (`GCN`), crowd_nav/policy/policy_factory.py:9-13 (registration),
 
-crowd_nav/policy/sarl.py:76-99 + multi_human_rl.py:12-171 (`SARL`, evaluation only).
+crowd_nav/policy/sarl.py:76-99 + multi_human_rl.py:12-171 (`SARL`; training after `enable_training()`).
 
 `register(policy_factory)` installs the classes under the reference's keys ('model_predictive_rl', 'gcn', 'sarl'),
 so crowd_nav's train.py / test.py pick them up unchanged.
@@ -610,7 +610,8 @@ class GCN(Policy):
 class SARL(GCN):
     """SARL / OM-SARL (crowd_nav/policy/sarl.py:76-99 over multi_human_rl.py:12-171): path G's one-step lookahead -- propagate,
     rotate, reward, action table, greedy action for an empty crowd, all inherited from GCN -- with the attention value network and,
-    with_om, the occupancy maps appended to every human's row.  Evaluation only: no training step, no replay rows."""
+    with_om, the occupancy maps appended to every human's row.  `enable_training()` opts in to the value network's backward pass
+    and to replay rows (VectorExplorer stores `transform`'s rows for an enabled target); query_env=True stays refused."""
 
     def __init__(self):
         super().__init__()
@@ -641,6 +642,14 @@ class SARL(GCN):
 
     def get_attention_weights(self):
         return self.attention_weights
+
+    def enable_training(self, flag=True):
+        """Opt in to training: SarlValueNetwork.enable_training on the model, and VectorExplorer stores this policy's replay rows."""
+        self.model.enable_training(flag)
+        return self
+
+    def training_enabled(self):
+        return bool(getattr(self.model, "_trains", False))
 
     def get_matrix_A(self):
         raise AttributeError("SARL has no adjacency matrix; see get_attention_weights()")

@@ -566,17 +566,20 @@ class SarlSearch:
 
 def occupancy_maps(humans64, cell_num=4, cell_size=1.0, om_channel_size=3, time_step=0.0):
     """sarl_occupancy_maps_f32: humans (B,H,5) float64 device tensor -> maps (B,H,cell_num^2 om_channel_size) float32 of the states
-    moved on by `time_step` at constant velocity (MultiHumanRL.build_occupancy_maps, multi_human_rl.py:117-171)."""
-    if not (torch.is_tensor(humans64) and humans64.is_cuda and humans64.dtype == torch.float64 and humans64.dim() == 3
+    moved on by `time_step` at constant velocity (MultiHumanRL.build_occupancy_maps, multi_human_rl.py:117-171).  A float32 tensor
+    is widened on the device (the kernel's `humans` argument): the same maps as from its float64 copy."""
+    if not (torch.is_tensor(humans64) and humans64.is_cuda and humans64.dtype in (torch.float64, torch.float32) and humans64.dim() == 3
             and humans64.shape[2] == 5):
-        raise nat.NativeLibraryError("occupancy maps take a float64 (B,H,5) CUDA(HIP) tensor (no CPU path)")
+        raise nat.NativeLibraryError("occupancy maps take a float64 or float32 (B,H,5) CUDA(HIP) tensor (no CPU path)")
     humans64 = humans64.contiguous()
     B, H = humans64.shape[0], humans64.shape[1]
     if H < 2:
         raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
     maps = torch.empty(B, H, int(cell_num) ** 2 * int(om_channel_size), dtype=torch.float32, device=humans64.device)
     with torch.cuda.device(humans64.device):
-        rc = nat.lib().sarl_occupancy_maps_f32(humans64.data_ptr(), None, B, H, float(time_step), int(cell_num), float(cell_size),
+        wide = humans64.dtype == torch.float64
+        rc = nat.lib().sarl_occupancy_maps_f32(humans64.data_ptr() if wide else None, None if wide else humans64.data_ptr(), B, H,
+                                               float(time_step), int(cell_num), float(cell_size),
                                                int(om_channel_size), maps.data_ptr(), _stream())
     nat.check(rc, "sarl_occupancy_maps_f32")
     return maps

@@ -32,7 +32,7 @@ import torch.optim as optim
 from torch.utils.data import DataLoader
 
 from . import _native as nat
-from .nets import invalidate_packed_weights
+from .nets import invalidate_packed_weights, SarlValueNetwork
 
 
 class _ShuffledIndexBatches(object):
@@ -532,6 +532,8 @@ class VNRLTrainer(_TrainerBase):
     def __init__(self, model, memory, device, policy, batch_size, optimizer_str, writer):
         """Train the value network of a path-G policy (crowd_nav/utils/trainer.py:164-186, same arguments and attribute names)."""
         self._adopt(device, memory, batch_size, optimizer_str, writer, model=model, policy=policy, optimizer=None)
+        if isinstance(model, SarlValueNetwork):
+            model.enable_training()               # handing the network to a trainer IS the opt-in to its backward pass
 
     update_target_model = MPRLTrainer.update_target_model
     _same_structure = staticmethod(MPRLTrainer._same_structure)

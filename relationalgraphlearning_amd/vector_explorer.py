@@ -47,7 +47,7 @@ from torch.utils.data import Dataset
 from . import _native as nat
 from .actions import as_array
 from .nets import _require_device_tensor, _stream
-from .rollout import rotate
+from .rollout import rotate, occupancy_maps
 from .sim import UnplacedSceneError
 
 COLLISION, SUCCESS, TIMEOUT = 2, 3, 4          # BatchedCrowdSim info codes
@@ -450,7 +450,7 @@ class VectorExplorer(object):
         # a memory that takes whole chunks (DeviceReplayMemory.push_episodes): the states, rewards and info codes are recorded
         # into (max_steps, B, ...) tensors -- the simulator writes rewards / info / dmin in place -- instead of per-step clones
         record = None
-        if keep_states and hasattr(self.memory, "push_episodes"):
+        if keep_states and hasattr(self.memory, "push_episodes") and not self._sarl_target():
             record = (torch.empty((max_steps,) + tuple(robot32.shape), dtype=torch.float32, device=sim.device),
                       torch.empty((max_steps,) + tuple(humans32.shape), dtype=torch.float32, device=sim.device),
                       torch.empty(max_steps, B, dtype=torch.float32, device=sim.device),
@@ -502,10 +502,13 @@ class VectorExplorer(object):
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None, epoch=None,
                        print_failure=False):
-        if update_memory and getattr(self.target_policy, "name", None) in ("SARL", "OM-SARL"):
-            # the rows stored below are path G's 13 relation features; SARL's replay rows carry the occupancy maps too
-            raise NotImplementedError("SARL training is not provided yet: the replay memory does not store SARL's %d-wide rows"
-                                      % self.target_policy.input_dim())
+        if update_memory and self._sarl_target():
+            if not self.target_policy.training_enabled():
+                # opt-in, like the network's backward pass: SARL's replay rows carry the occupancy maps behind the 13 relation features
+                raise NotImplementedError("SARL training is not provided until policy.enable_training() is called: the replay memory "
+                                          "then stores SARL's %d-wide rows" % self.target_policy.input_dim())
+            if self.memory is None or self.gamma is None:
+                raise ValueError('Memory or gamma value is not set!')
         self.policy.set_phase(phase)
         cases = self._next_cases(phase, k)
         time_limit = self.sim.cfg.time_limit
@@ -595,6 +598,24 @@ class VectorExplorer(object):
         joint = torch.cat([robot.expand(humans.shape[0], 9), humans], dim=1).contiguous()
         return rotate(joint, self.target_policy.kinematics)
 
+    def _sarl_target(self):
+        """The target policy is SARL / OM-SARL: its replay rows come from the host loop (update_memory) whatever the memory's type
+        -- push_episodes has no layout for them."""
+        return getattr(self.target_policy, "name", None) in ("SARL", "OM-SARL")
+
+    def _sarl_rows(self, states):
+        """(T, H, D) rows of an episode's T states, each what `SARL.transform` makes of it: ONE rotate over the T x H pairs and,
+        with maps, ONE sarl_occupancy_maps_f32 over the T crowds (from the float32 states, widened on the device)."""
+        pol = self.target_policy
+        robots = torch.cat([s[0] for s in states], dim=0)                    # (T, 9)
+        humans = torch.stack([s[1] for s in states], dim=0).contiguous()      # (T, H, 5)
+        T, H = humans.shape[0], humans.shape[1]
+        joint = torch.cat([robots[:, None, :].expand(T, H, 9), humans], dim=2).reshape(T * H, 14).contiguous()
+        rows = rotate(joint, pol.kinematics).reshape(T, H, 13)
+        if pol.with_om:
+            rows = torch.cat([rows, occupancy_maps(humans, pol.cell_num, pol.cell_size, pol.om_channel_size)], dim=2)
+        return rows
+
     def _push_chunk(self, run, imitation_learning):
         """What the update_memory loop of run_k_episodes stores for one chunk, as one `memory.push_episodes` call."""
         if self.memory is None or self.gamma is None:
@@ -616,12 +637,16 @@ class VectorExplorer(object):
         for t in range(n - 1, -1, -1):
             togo[t] = rewards[t] + step_discount * togo[t + 1]
         mprl = self.target_policy.name == 'ModelPredictiveRL'
+        sarl_rows = self._sarl_rows(states) if self._sarl_target() and n > 1 else None
         for i in range(n - 1):                                   # the last state has no successor: not stored
             if imitation_learning:
                 value = togo[i]                                  # discounted return from step i
             else:
                 value = 0                                        # RL: the trainer bootstraps from the target network
-            state, next_state = self._transform(states[i]), self._transform(states[i + 1])
+            if sarl_rows is not None:
+                state, next_state = sarl_rows[i], sarl_rows[i + 1]
+            else:
+                state, next_state = self._transform(states[i]), self._transform(states[i + 1])
             value = torch.tensor([value], dtype=torch.float32, device=self.device)
             reward = torch.tensor([rewards[i]], dtype=torch.float32, device=self.device)
             if mprl:

@@ -1,0 +1,344 @@
+"""SARL / OM-SARL training on the device: sarl_value_train_f32 / sarl_value_backward_f32 through the C ABI and through autograd
+against float64 autograd (tests/sarl_train.py), the trainer against upstream's VNRLTrainer fixture, the replay rows and one
+imitation-learning run end to end."""
+import copy
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import sarl_cpu as cpu
+from tests import sarl_train as st
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def make_model(dev, input_dim, with_global_state, weights):
+    from relationalgraphlearning_amd import SarlValueNetwork
+    net = SarlValueNetwork(input_dim, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], with_global_state, 1.0, 4).to(dev)
+    net.load_state_dict({k: v.to(dev) for k, v in cpu.weight_set(weights, input_dim, with_global_state).items()})
+    return net
+
+
+def abi_train(model, rows, targets, ws=None):
+    """(value, attention, {name: gradient}, workspace) of mean((value - target)^2) through the C ABI; the gradient buffers are
+    pre-filled with NaN (the call overwrites), `ws` is reused when given."""
+    from relationalgraphlearning_amd import _native as nat
+    lib = nat.lib()
+    dev = rows.device
+    S, H = rows.shape[0], rows.shape[1]
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with torch.no_grad():
+        pl = model.fill_planner(nat.SarlPlanner())
+    need = lib.sarl_train_workspace_bytes(C.byref(pl), S, H)
+    assert need > 0
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if nat.poison_workspaces():
+            ws.fill_(255)
+    value = torch.empty(S, 1, dtype=torch.float32, device=dev)
+    att = torch.empty(S, H, dtype=torch.float32, device=dev)
+    nat.check(lib.sarl_value_train_f32(C.byref(pl), rows.data_ptr(), S, H, ws.data_ptr(), ws.numel(), value.data_ptr(), att.data_ptr(),
+                                       stream), "sarl_value_train_f32")
+    grad_value = (2.0 / S) * (value - targets)
+    out = {k: torch.full_like(p, float("nan")) for k, p in zip(st.PARAMS, model.training_parameters())}
+    grads = nat.SarlGrads()
+    for l, layer in enumerate(cpu.LAYERS):
+        grads.weight[l], grads.bias[l] = out[layer + ".weight"].data_ptr(), out[layer + ".bias"].data_ptr()
+    nat.check(lib.sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), grad_value.data_ptr(), S, H, ws.data_ptr(), ws.numel(),
+                                          C.byref(grads), stream), "sarl_value_backward_f32")
+    return value, att, out, ws
+
+
+def module_gradients(model, rows, targets):
+    model.enable_training()
+    model.zero_grad()
+    with torch.enable_grad():
+        loss = torch.nn.functional.mse_loss(model(rows), targets)
+        loss.backward()
+    return {k: p.grad.detach().clone() for k, p in zip(st.PARAMS, model.training_parameters())}
+
+
+_references = {}
+
+
+def reference(case):
+    """(rows, targets, float64 gradients) of a fixture case: computed once, shared by every test that asks, never changed."""
+    if case not in _references:
+        S, H, D, gs, w = case
+        seed = st.case_seed(case)
+        rows, targets = st.case_rows(S, H, D, seed), st.case_targets(S, seed)
+        _references[case] = (rows, targets, st.reference_gradients(rows, targets, cpu.weight_set(w, D, gs), gs))
+    return _references[case]
+
+
+def check_gradients(case, grads, what, ref=None):
+    if ref is None:
+        ref = reference(case)[2]
+    dist = st.distances({k: v.cpu() for k, v in grads.items()}, ref)
+    bound = st.gradient_bounds(case, st.max_abs(ref))
+    ratio = np.where(dist > 0, dist / np.maximum(bound, 1e-300), 0.0)
+    print("%s %s: worst distance / bound %.2f (%s)" % (st.case_tag(case), what, float(ratio.max()), st.PARAMS[int(ratio.argmax())]))
+    for k, d, b in zip(st.PARAMS, dist, bound):
+        assert np.isfinite(d) and d <= b, (st.case_tag(case), what, k, d, b)
+
+
+@pytest.mark.parametrize("case", st.gradient_cases(), ids=st.case_tag)
+def test_gradients_against_float64(dev, case):
+    """Through the C ABI (gradient buffers pre-filled with NaN: the call overwrites) and through loss.backward() on the module."""
+    S, H, D, gs, w = case
+    rows, targets, _ = reference(case)
+    model = make_model(dev, D, gs, w)
+    _, _, grads, _ = abi_train(model, rows.to(dev), targets.to(dev))
+    check_gradients(case, grads, "C ABI")
+    by_module = module_gradients(model, rows.to(dev), targets.to(dev))
+    check_gradients(case, by_module, "autograd")
+    assert all(torch.equal(grads[k], by_module[k]) for k in st.PARAMS)
+
+
+POISONED = [(17, 5, D, gs, "sharp") for D, gs in st.VARIANTS] + [(1, 21, 61, True, "sharp"), (17, 1, 13, True, "plain"),
+                                                                (33, 2, 61, True, "plain")]
+
+
+@pytest.mark.parametrize("case", POISONED, ids=st.case_tag)
+def test_gradients_with_poisoned_workspaces(dev, monkeypatch, case):
+    """RGL_DEBUG_POISON_WORKSPACES=1: no workspace byte is read before this call has written it."""
+    monkeypatch.setenv("RGL_DEBUG_POISON_WORKSPACES", "1")
+    S, H, D, gs, w = case
+    rows, targets, _ = reference(case)
+    model = make_model(dev, D, gs, w)
+    check_gradients(case, abi_train(model, rows.to(dev), targets.to(dev))[2], "C ABI, poisoned")
+    check_gradients(case, module_gradients(model, rows.to(dev), targets.to(dev)), "autograd, poisoned")
+
+
+def test_full_gradients_against_upstream(dev):
+    """Upstream's stored float32 gradients of one case, element by element, within the same per-tensor bound."""
+    case = st.FULL_CASE
+    S, H, D, gs, w = case
+    rows, targets, ref = reference(case)
+    upstream = {k: torch.tensor(st.fixture()["full." + k]).double() for k in st.PARAMS}
+    grads = module_gradients(make_model(dev, D, gs, w), rows.to(dev), targets.to(dev))
+    bound = st.gradient_bounds(case, st.max_abs(ref))
+    for k, d, b in zip(st.PARAMS, st.distances({k: v.cpu() for k, v in grads.items()}, upstream), bound):
+        assert d <= b, (k, d, b)
+    check_gradients(case, grads, "autograd", ref)
+
+
+@pytest.mark.parametrize("H", [5, 20, 21])
+def test_training_forward_is_the_evaluation_forward(dev, H):
+    from relationalgraphlearning_amd import _native as nat
+    S, D = 17, 61
+    rows = st.case_rows(S, H, D, 400 + H).to(dev)
+    model = make_model(dev, D, True, "sharp")
+    value, att, _, _ = abi_train(model, rows, torch.zeros(S, 1, device=dev))
+    with torch.no_grad():
+        pl = model.fill_planner(nat.SarlPlanner())
+        ws = torch.empty(nat.lib().sarl_value_workspace_bytes_for(C.byref(pl), S, H), dtype=torch.uint8, device=dev)
+        v0, a0 = torch.empty(S, 1, device=dev), torch.empty(S, H, device=dev)
+        nat.check(nat.lib().sarl_value_f32(C.byref(pl), rows.data_ptr(), None, None, None, S, 1, H, ws.data_ptr(), ws.numel(), v0.data_ptr(),
+                                           a0.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "sarl_value_f32")
+        plain = model(rows)
+        plain_att = model.attention_weights.copy()
+    assert torch.equal(value, v0) and torch.equal(att, a0) and torch.equal(plain, v0)
+    model.enable_training()
+    with torch.enable_grad():
+        tracked = model((rows, torch.full((S,), H)))
+    assert tracked.requires_grad and torch.equal(tracked.detach(), plain)
+    assert torch.is_tensor(model._attention)                  # no host copy in a grad-mode forward ...
+    assert np.array_equal(model.attention_weights, plain_att)   # ... until the weights are read
+    clone = copy.deepcopy(model)                                # update_target_model's copy, after forwards in both modes
+    with torch.no_grad():
+        assert torch.equal(clone(rows), plain)
+
+
+def test_backward_is_deterministic(dev):
+    case = (33, 5, 61, True, "sharp")
+    rows, targets, _ = reference(case)
+    model = make_model(dev, 61, True, "sharp")
+    _, _, first, ws = abi_train(model, rows.to(dev), targets.to(dev))
+    _, _, fresh, _ = abi_train(model, rows.to(dev), targets.to(dev))
+    _, _, reused, _ = abi_train(model, rows.to(dev), targets.to(dev), ws=ws)
+    assert all(torch.equal(first[k], fresh[k]) and torch.equal(first[k], reused[k]) for k in st.PARAMS)
+
+
+def test_refusals(dev):
+    from relationalgraphlearning_amd import _native as nat
+    lib = nat.lib()
+    model = make_model(dev, 61, True, "plain")
+    with torch.no_grad():
+        pl = model.fill_planner(nat.SarlPlanner())
+    assert lib.sarl_train_workspace_bytes(C.byref(pl), 4, 1) == 0 and lib.sarl_train_workspace_bytes(C.byref(pl), 4, 128) == 0
+    assert lib.sarl_train_workspace_bytes(C.byref(pl), 0, 5) == 0
+    need = lib.sarl_train_workspace_bytes(C.byref(pl), 4, 5)
+    rows, ws = torch.zeros(4, 5, 61, device=dev), torch.empty(need, dtype=torch.uint8, device=dev)
+    value, gv = torch.empty(4, 1, device=dev), torch.zeros(4, device=dev)
+    out = [torch.empty_like(p) for p in model.training_parameters()]
+    grads = nat.SarlGrads()
+    for l in range(nat.SARL_LAYERS):
+        grads.weight[l], grads.bias[l] = out[2 * l].data_ptr(), out[2 * l + 1].data_ptr()
+    assert lib.sarl_value_train_f32(C.byref(pl), rows.data_ptr(), 4, 5, ws.data_ptr(), need - 1, value.data_ptr(), None, None) == -4
+    assert lib.sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), gv.data_ptr(), 4, 5, ws.data_ptr(), need - 1, C.byref(grads), None) == -4
+    assert lib.sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), gv.data_ptr(), 4, 128, ws.data_ptr(), need, C.byref(grads), None) == -1
+    assert lib.sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), None, 4, 5, ws.data_ptr(), need, C.byref(grads), None) == -3
+    pl.contraction_dtype = nat.CONTRACTION_DTYPES["bf16x6"]
+    assert lib.sarl_value_backward_f32(C.byref(pl), rows.data_ptr(), gv.data_ptr(), 4, 5, ws.data_ptr(), need, C.byref(grads), None) == -2
+    # a nullable attention pointer
+    pl.contraction_dtype = nat.CONTRACTION_DTYPES["f32"]
+    assert lib.sarl_value_train_f32(C.byref(pl), rows.data_ptr(), 4, 5, ws.data_ptr(), need, value.data_ptr(), None, None) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(value).all()
+
+
+# ---- the trainer -------------------------------------------------------------------------------------------------------------------
+class _Writer(object):
+    def __init__(self):
+        self.scalars = []
+
+    def add_scalar(self, tag, value, step=None):
+        self.scalars.append((tag, value, step))
+
+
+def run_trainer(dev, case, eager=False):
+    import relationalgraphlearning_amd as rga
+    from relationalgraphlearning_amd.trainer import pad_batch
+    spec = st.TRAINER_CASES[case]
+    states, values, rewards, next_states = (t.to(dev) for t in st.trainer_data())
+    model = make_model(dev, st.TRAINER_D, True, spec["weights"])
+    memory = rga.ReplayMemory(1000)
+    for i in range(st.TRAINER_N):
+        memory.push((states[i], values[i], rewards[i], next_states[i]))
+    t = rga.VNRLTrainer(model, memory, dev, None, st.TRAINER_BATCH, spec["optimizer"], _Writer())
+    t.set_learning_rate(1e-3)
+    t.update_target_model(model)
+    if eager:
+        t._capturable = False                     # the same optimizer, every step run as it would be recorded
+    t.data_loader = torch.utils.data.DataLoader(memory, st.TRAINER_BATCH, shuffle=False, collate_fn=pad_batch)
+    losses, captures = [], []
+    if spec["epochs"]:
+        losses.append(t.optimize_epoch(spec["epochs"]))
+        captures.append(len(t._steps))
+    losses.append(t.optimize_batch(spec["batches"], 0))
+    captures.append(len(t._steps))
+    return t, model, losses, captures
+
+
+@pytest.mark.parametrize("case", sorted(st.TRAINER_CASES))
+def test_trainer_reproduces_upstreams_trainer_fixture(dev, case):
+    import relationalgraphlearning_amd as rga
+    t, model, losses, captures = run_trainer(dev, case)
+    want = st.fixture()["tr.%s.losses" % case]
+    print("trainer case %s: losses %s, upstream %s; parameters %.2e from upstream" % (case, losses, want.tolist(),
+                                                                                     st.parameter_distance(model.state_dict(), case)))
+    if st.TRAINER_CASES[case]["optimizer"] == "Adam":
+        assert t._capturable and captures == [1, 2]           # one capture per kind of step serves every later batch
+    assert len(losses) == len(want)
+    for got, w in zip(losses, want):
+        assert abs(got - w) <= st.LOSS_BOUND * max(1.0, abs(w)), (got, w)
+    assert st.parameter_distance(model.state_dict(), case) <= st.PARAMETER_BOUND
+    rows = st.trainer_data()[0][:3].to(dev)
+    with torch.no_grad():                                      # the packed weights follow the trained parameters
+        now = model(rows)
+        rga.invalidate_packed_weights(model)
+        assert torch.equal(now, model(rows))
+
+
+def test_captured_steps_equal_eager_steps(dev):
+    _, captured, _, _ = run_trainer(dev, "A")
+    t, eager, _, captures = run_trainer(dev, "A", eager=True)
+    assert captures == [0, 0]
+    for (k, a), b in zip(captured.state_dict().items(), eager.state_dict().values()):
+        assert torch.equal(a, b), k
+
+
+# ---- replay rows and the whole loop ------------------------------------------------------------------------------------------------
+def make_policy(dev):
+    from tests.test_sarl_gpu import make_policy as make
+    pol = make(dev, "holonomic", 61, True, "plain")
+    pol.enable_training()
+    return pol
+
+
+def explore(dev, memory):
+    from relationalgraphlearning_amd import VectorExplorer
+    from relationalgraphlearning_amd.orca import OrcaPolicy
+    from relationalgraphlearning_amd.sim import BatchedCrowdSim, SimConfig
+    pol = make_policy(dev)
+    # time_limit 4 ends an episode after twelve steps, and a timed-out episode is not stored: the robot starts a metre from the
+    # origin, among humans crossing a six-metre square (inside one another's four-metre grids), so that an episode of the four succeeds
+    cfg = SimConfig(time_limit=4, circle_radius=1.0, scenario="square_crossing", square_width=6)
+    ex = VectorExplorer(BatchedCrowdSim(dev, cfg, human_policy="orca"), OrcaPolicy(safety_space=0.15), memory=memory,
+                        gamma=0.9, target_policy=pol)
+    ex.run_k_episodes(4, "train", update_memory=True, imitation_learning=True)
+    return pol, ex
+
+
+def test_replay_rows(dev, monkeypatch):
+    from relationalgraphlearning_amd import ReplayMemory, DeviceReplayMemory, VectorExplorer
+    from relationalgraphlearning_amd.state import JointState, FullState, ObservableState
+    seen = []
+    original = VectorExplorer.update_memory
+
+    def recording(self, states, actions, rewards, imitation_learning=False):
+        seen.append(([(s[0].clone(), s[1].clone()) for s in states], list(rewards)))
+        return original(self, states, actions, rewards, imitation_learning)
+    monkeypatch.setattr(VectorExplorer, "update_memory", recording)
+    host, device = ReplayMemory(1000), DeviceReplayMemory(1000)
+    pol, ex = explore(dev, host)
+    episodes = list(seen)
+    explore(dev, device)
+    assert len(host) == len(device) > 0 and len(host) == sum(len(s) - 1 for s, _ in episodes)
+    for i in range(len(host)):
+        assert all(torch.equal(a, b) for a, b in zip(host[i], device[i]))
+    d = pow(0.9, 0.25 * 1.0)
+    item = 0
+    for states, rewards in episodes:
+        for t in range(len(states) - 1):
+            state, value, reward, nxt = host[item]
+            for got, (robot, humans) in ((state, states[t]), (nxt, states[t + 1])):
+                r = [float(x) for x in robot[0].cpu()]
+                js = JointState(FullState(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8]),
+                                [ObservableState(*[float(x) for x in h]) for h in humans.cpu()])
+                assert got.shape == (5, 61) and torch.equal(got, pol.transform(js))
+            togo = 0.0
+            for r in reversed(rewards[t:]):
+                togo = r + d * togo
+            assert float(value) == float(np.float32(togo)) and float(reward) == float(np.float32(rewards[t]))
+            item += 1
+
+
+def test_imitation_learning_end_to_end(dev, tmp_path):
+    from relationalgraphlearning_amd import ReplayMemory, VNRLTrainer
+    memory = ReplayMemory(1000)
+    pol, ex = explore(dev, memory)
+    t = VNRLTrainer(pol.model, memory, dev, pol, 16, "Adam", _Writer())
+    t.set_learning_rate(1e-3)
+    t.update_target_model(pol.model)
+
+    def imitation_loss():
+        with torch.no_grad():
+            rows, values = torch.stack([m[0] for m in memory.memory]), torch.stack([m[1] for m in memory.memory])
+            return float(torch.nn.functional.mse_loss(pol.model(rows), values))
+    before = imitation_loss()
+    t.optimize_epoch(2)
+    after = imitation_loss()
+    assert after < before, (before, after)
+    loss = t.optimize_batch(2, 0)
+    assert np.isfinite(loss)
+    path = os.path.join(str(tmp_path), "sarl_trained.pth")
+    pol.save_model(path)
+    other = make_policy(dev)
+    robot, humans = cpu.scenes(31, 5, 5)
+    r, h = torch.tensor(robot, device=dev).float(), torch.tensor(humans, device=dev).float()
+    want_best, want_value = pol.predict_batch(r, h)
+    untrained = other.predict_batch(r, h)[1].clone()
+    other.load_model(path)
+    best, value = other.predict_batch(r, h)
+    assert torch.equal(best, want_best) and torch.equal(value, want_value) and not torch.equal(untrained, value)

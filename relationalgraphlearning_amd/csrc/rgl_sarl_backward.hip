@@ -41,6 +41,21 @@ struct SarlGemmArgs {
     SarlGemmJob job[kMaxJobs];
 };
 
+// A contraction longer than this many k is summed span by span: each span in an accumulator that starts from zero, the spans'
+// totals added in order with the rounding error of every addition carried along and added at the end.  The MFMA rounds once per
+// k, so one accumulator over the 13120 rows of a batch of 2624 scenes walks 2.8e-6 of a weight gradient's largest element away from
+// float64 (mlp1.2.weight), five times upstream's float32 figure; span by span it stays at a span's own error.  Still one wave, one
+// fixed order: two calls give the same bits.  Every product of at most kSarlGemmSpan k -- all but the weight gradients over more
+// than 256 rows -- is one span and keeps the bits it had.
+constexpr int kSarlGemmSpan = 256;
+
+// what the float addition s + x drops (Knuth's TwoSum: additions only, any magnitudes)
+__device__ __forceinline__ float two_sum_error(float s, float x) {          // the caller then sets s = s + x
+    const float t = s + x;
+    const float xr = t - s;
+    return (s - (t - xr)) + (x - xr);
+}
+
 // Lane (g, n) of a wave (g = lane / 16, n = lane % 16) feeds row 16 ti + n of A and column 16 tj + n of B at k = k0 + 4 g + i in
 // step i of a 16-wide k block (the k order of sarl_layer), and owns C rows 16 ti + 4 g + {0..3} of column 16 tj + n.
 __global__ __launch_bounds__(256) void sarl_gemm_kernel(const SarlGemmArgs ga) {
@@ -59,34 +74,58 @@ __global__ __launch_bounds__(256) void sarl_gemm_kernel(const SarlGemmArgs ga) {
         const float b0 = (j.bias && col_ok) ? j.bias[col] : 0.f;
         f32x4 acc = {b0, b0, b0, b0};
         float rs = 0.f;
-        for (int k0 = 0; k0 < j.K; k0 += 16) {
-            float a[4], b[4];
+        f32x4 sum = acc, err = {0.f, 0.f, 0.f, 0.f};
+        float rsum = 0.f, rerr = 0.f;
+        for (int c0 = 0; c0 < j.K; c0 += kSarlGemmSpan) {
+            const int c1 = c0 + kSarlGemmSpan < j.K ? c0 + kSarlGemmSpan : j.K;
+            for (int k0 = c0; k0 < c1; k0 += 16) {
+                float a[4], b[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int k = k0 + 4 * g + i;
-                const bool k_ok = k < j.K;
-                a[i] = (row_ok && k_ok) ? a_row[(size_t)k * j.sak] : 0.f;
-                b[i] = (col_ok && k_ok) ? b_col[(size_t)k * j.sbk] : 0.f;
-            }
+                for (int i = 0; i < 4; ++i) {
+                    const int k = k0 + 4 * g + i;
+                    const bool k_ok = k < j.K;
+                    a[i] = (row_ok && k_ok) ? a_row[(size_t)k * j.sak] : 0.f;
+                    b[i] = (col_ok && k_ok) ? b_col[(size_t)k * j.sbk] : 0.f;
+                }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc = mfma4(a[i], b[i], acc);
-                rs += a[i];
+                for (int i = 0; i < 4; ++i) {
+                    acc = mfma4(a[i], b[i], acc);
+                    rs += a[i];
+                }
             }
+            if (c0 == 0) {              // the only span of every product but a weight gradient over more than kSarlGemmSpan rows
+                sum = acc;
+                rsum = rs;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    err[i] += two_sum_error(sum[i], acc[i]);
+                    sum[i] += acc[i];
+                }
+                rerr += two_sum_error(rsum, rs);
+                rsum += rs;
+            }
+            acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            rs = 0.f;
+        }
+        if (j.K > kSarlGemmSpan) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sum[i] += err[i];
+            rsum += rerr;
         }
         if (col_ok) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 16 * ti + 4 * g + i;
                 if (r >= j.I) continue;
-                float v = acc[i];
+                float v = sum[i];
                 if (j.relu) v = fmaxf(v, 0.f);
                 if (j.mask && !(j.mask[(size_t)r * j.ldmask + col] > 0.f)) v = 0.f;
                 j.C[(size_t)r * j.ldc + col] = v;
             }
         }
         if (j.rowsum && tj == 0) {          // wave-uniform: every lane takes part in the butterfly
-            const float s = kgroups_sum(rs);
+            const float s = kgroups_sum(rsum);
             if (g == 0 && row_ok) j.rowsum[row] = s;
         }
     }

@@ -64,12 +64,12 @@ class Writer(object):
         pass
 
 
-def upstream_trainer_run(case, data):
-    spec = st.TRAINER_CASES[case]
+def upstream_trainer_run(case, data, spec=None):
+    spec = st.TRAINER_CASES[case] if spec is None else spec
     states, values, rewards, next_states = data
     net = upstream_network(st.TRAINER_D, True, cpu.weight_set(spec["weights"], st.TRAINER_D, True))
     memory = ReplayMemory(1000)
-    for i in range(st.TRAINER_N):
+    for i in range(states.shape[0]):
         memory.push((states[i], values[i], rewards[i], next_states[i]))
     tr = VNRLTrainer(net, memory, torch.device("cpu"), None, st.TRAINER_BATCH, spec["optimizer"], Writer())
     tr.set_learning_rate(1e-3)

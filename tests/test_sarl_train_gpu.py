@@ -28,9 +28,10 @@ def make_model(dev, input_dim, with_global_state, weights):
     return net
 
 
-def abi_train(model, rows, targets, ws=None):
+def abi_train(model, rows, targets, ws=None, grad_value=None):
     """(value, attention, {name: gradient}, workspace) of mean((value - target)^2) through the C ABI; the gradient buffers are
-    pre-filled with NaN (the call overwrites), `ws` is reused when given."""
+    pre-filled with NaN (the call overwrites), `ws` is reused when given.  `grad_value` (S, 1), when given, is handed to the
+    backward in place of the MSE's (`targets` is then not read)."""
     from relationalgraphlearning_amd import _native as nat
     lib = nat.lib()
     dev = rows.device
@@ -48,7 +49,9 @@ def abi_train(model, rows, targets, ws=None):
     att = torch.empty(S, H, dtype=torch.float32, device=dev)
     nat.check(lib.sarl_value_train_f32(C.byref(pl), rows.data_ptr(), S, H, ws.data_ptr(), ws.numel(), value.data_ptr(), att.data_ptr(),
                                        stream), "sarl_value_train_f32")
-    grad_value = (2.0 / S) * (value - targets)
+    if grad_value is None:
+        grad_value = (2.0 / S) * (value - targets)
+    assert grad_value.shape == (S, 1) and grad_value.is_contiguous() and grad_value.dtype == torch.float32
     out = {k: torch.full_like(p, float("nan")) for k, p in zip(st.PARAMS, model.training_parameters())}
     grads = nat.SarlGrads()
     for l, layer in enumerate(cpu.LAYERS):
@@ -71,12 +74,16 @@ _references = {}
 
 
 def reference(case):
-    """(rows, targets, float64 gradients) of a fixture case: computed once, shared by every test that asks, never changed."""
+    """(rows, targets, float64 gradients) of a fixture case, single-seed or wide: computed once, shared by every test that asks,
+    never changed."""
     if case not in _references:
         S, H, D, gs, w = case
-        seed = st.case_seed(case)
-        rows, targets = st.case_rows(S, H, D, seed), st.case_targets(S, seed)
-        _references[case] = (rows, targets, st.reference_gradients(rows, targets, cpu.weight_set(w, D, gs), gs))
+        if st.is_wide(case):
+            _references[case] = (st.wide_rows(case), st.wide_targets(case), st.wide_gradients(case))
+        else:
+            seed = st.case_seed(case)
+            rows, targets = st.case_rows(S, H, D, seed), st.case_targets(S, seed)
+            _references[case] = (rows, targets, st.reference_gradients(rows, targets, cpu.weight_set(w, D, gs), gs))
     return _references[case]
 
 
@@ -206,14 +213,15 @@ class _Writer(object):
         self.scalars.append((tag, value, step))
 
 
-def run_trainer(dev, case, eager=False):
+def run_trainer(dev, case, eager=False, spec=None, data=None):
+    """`spec` and `data` replace the case's own and the 48 transitions (tests/test_sarl_train_wide_gpu.py)."""
     import relationalgraphlearning_amd as rga
     from relationalgraphlearning_amd.trainer import pad_batch
-    spec = st.TRAINER_CASES[case]
-    states, values, rewards, next_states = (t.to(dev) for t in st.trainer_data())
+    spec = st.TRAINER_CASES[case] if spec is None else spec
+    states, values, rewards, next_states = (t.to(dev) for t in (st.trainer_data() if data is None else data))
     model = make_model(dev, st.TRAINER_D, True, spec["weights"])
     memory = rga.ReplayMemory(1000)
-    for i in range(st.TRAINER_N):
+    for i in range(states.shape[0]):
         memory.push((states[i], values[i], rewards[i], next_states[i]))
     t = rga.VNRLTrainer(model, memory, dev, None, st.TRAINER_BATCH, spec["optimizer"], _Writer())
     t.set_learning_rate(1e-3)

@@ -708,6 +708,20 @@ typedef struct RglReplayPushJob {
 size_t rgl_replay_push_workspace_bytes(int T, int B);
 int rgl_replay_push_f32(const RglReplayPushJob* job);
 
+/* rgl_replay_push_sarl_f32 (ABI 8, additive) -- the same push with the rows SARL / OM-SARL train on.  `job` is the struct above;
+ * `layout` is not read.  fields = state [capacity][H][D], value [capacity], reward [capacity], next state [capacity][H][D], a
+ * state being what SARL.transform makes of (robot, humans): row h = the 13 features gcn_rotate_f32 makes of [robot | human h]
+ * under `kinematics` and, with maps (channels 1..3, D = 13 + cell_num^2 channels), behind them the slots
+ * sarl_occupancy_maps_f32 gives human h from the float32 human states with time_step = 0 -- the same bits in both parts.
+ * channels = 0: no maps, D = 13, cell_num and cell_size are not read.  Rows are built only for states of which a tuple lands in
+ * the memory; no buffer of rows exists outside the fields.  Workspace: rgl_replay_push_workspace_bytes(T, B).
+ * Errors, in the order of rgl_replay_push_f32 (the map parameters stand where its layout does): RGL_ERR_NULL (`rows` too);
+ * RGL_ERR_BAD_SHAPE as above; channels outside 0..3 RGL_ERR_BAD_MODE, cell_num outside 1..8 or cell_size <= 0
+ * RGL_ERR_BAD_SHAPE (what sarl_occupancy_maps_f32 accepts), maps with H = 1 RGL_ERR_BAD_SHAPE (upstream's np.concatenate of no
+ * other human); the kinematics, the four fields, the runs and the workspace as above.  n_runs = 0: RGL_OK, nothing launched. */
+typedef struct RglReplaySarlRows { int cell_num; double cell_size; int channels; } RglReplaySarlRows;   /* channels 0: no maps, D = 13 */
+int rgl_replay_push_sarl_f32(const RglReplayPushJob* job, const RglReplaySarlRows* rows);
+
 /* ---------------------------------------------------------------------------------------------
  * Epsilon-greedy exploration on device with each case's own numpy stream (ABI 8, additive).  Upstream seeds numpy per case in
  * CrowdSim.reset (crowd_sim/envs/crowd_sim.py:185-191), generate_human consumes doubles, and every predict of the episode

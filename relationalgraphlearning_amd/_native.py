@@ -160,6 +160,10 @@ class RglReplayPushJob(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class RglReplaySarlRows(C.Structure):
+    _fields_ = [("cell_num", C.c_int), ("cell_size", C.c_double), ("channels", C.c_int)]      # channels 0: no maps, D = 13
+
+
 EXPLORE_STATE_WORDS = 625
 
 
@@ -241,6 +245,7 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rgl_replay_push_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "rgl_replay_push_f32": (C.c_int, [C.POINTER(RglReplayPushJob)]),
+    "rgl_replay_push_sarl_f32": (C.c_int, [C.POINTER(RglReplayPushJob), C.POINTER(RglReplaySarlRows)]),
     "crowd_explore_seed_u32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "crowd_explore_select_f64": (C.c_int, [C.POINTER(CrowdExploreJob)]),
     "crowd_step_nonstop_f64": (C.c_int, [C.POINTER(CrowdNonstopJob)]),
@@ -267,7 +272,7 @@ SIGNATURES = {
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
             "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
-            "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32"}
+            "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32"}
 
 _lib = None
 

@@ -1,6 +1,6 @@
 // rotate_row -- CADRL.rotate (cadrl.py:241-276) for one joint row, shared by the translation units that produce path G's pairwise
-// relation features: rgl_tree.hip (gcn_rotate_f32, gcn_prepare_f32) and rgl_replay.hip (the replay memory's "gcn" layout, which must
-// store the bits rollout.rotate produces).
+// relation features: rgl_tree.hip (gcn_rotate_f32, gcn_prepare_f32) and rgl_replay.hip (the replay memory's "gcn" layout and its SARL rows,
+// which must store the bits rollout.rotate produces).
 #pragma once
 #include "rgl_common.h"
 

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "rgl_mfma.h"
+#include "rgl_sarl_maps.h"
 #include "rgl_sarl_shapes.h"
 
 namespace {
@@ -297,54 +298,18 @@ __global__ __launch_bounds__(64) void sarl_maps_kernel(const double* __restrict_
         const size_t at = ((size_t)b * H + j) * 5 + k;
         return humans64 ? humans64[at] : (double)humans32[at];
     };
-    const double px = HB(i, 0) + HB(i, 2) * dt, py = HB(i, 1) + HB(i, 3) * dt;
     const double own_angle = atan2(HB(i, 3), HB(i, 2));
-    const double half = (double)cell_num / 2.0;
     for (int j = threadIdx.x; j < H; j += 64) {
-        int cell = -1;
-        double ovx = 0.0, ovy = 0.0;
-        if (j != i) {
-            const double ox = (HB(j, 0) + HB(j, 2) * dt) - px, oy = (HB(j, 1) + HB(j, 3) * dt) - py;
-            const double rot = atan2(oy, ox) - own_angle;
-            const double dist = sqrt(ox * ox + oy * oy);
-            const double xi = floor(cos(rot) * dist / cell_size + half), yi = floor(sin(rot) * dist / cell_size + half);
-            if (xi >= 0.0 && xi < (double)cell_num && yi >= 0.0 && yi < (double)cell_num) {
-                cell = cell_num * (int)yi + (int)xi;
-                if (channels != 1) {
-                    const double vrot = atan2(HB(j, 3), HB(j, 2)) - own_angle;
-                    const double speed = sqrt(HB(j, 2) * HB(j, 2) + HB(j, 3) * HB(j, 3));
-                    ovx = cos(vrot) * speed;
-                    ovy = sin(vrot) * speed;
-                }
-            }
-        }
+        int cell;
+        double ovx, ovy;
+        sarl_map_pair(HB, i, j, own_angle, dt, cell_num, cell_size, channels, cell, ovx, ovy);
         pair_cell[j] = cell;
         pair_vx[j] = ovx;
         pair_vy[j] = ovy;
     }
     __syncthreads();
-    for (int slot = threadIdx.x; slot < n_slots; slot += 64) {
-        double sum = 0.0;
-        int count = 0;
-        for (int j = 0; j < H; ++j) {
-            const int cell = pair_cell[j];
-            if (cell < 0) continue;
-            if (channels == 1) {
-                if (cell == slot) count = 1;
-                continue;
-            }
-            // the slot base is 2 * cell for two AND three channels (:159-164)
-            if (channels == 2) {
-                if (slot == 2 * cell) { sum += pair_vx[j]; ++count; }
-                else if (slot == 2 * cell + 1) { sum += pair_vy[j]; ++count; }
-            } else {
-                if (slot == 2 * cell) { sum += 1.0; ++count; }
-                else if (slot == 2 * cell + 1) { sum += pair_vx[j]; ++count; }
-                else if (slot == 2 * cell + 2) { sum += pair_vy[j]; ++count; }
-            }
-        }
-        maps[(size_t)bi * n_slots + slot] = channels == 1 ? (count ? 1.f : 0.f) : (count ? (float)(sum / (double)count) : 0.f);
-    }
+    for (int slot = threadIdx.x; slot < n_slots; slot += 64)
+        maps[(size_t)bi * n_slots + slot] = sarl_map_slot(pair_cell, pair_vx, pair_vy, H, slot, channels);
 }
 
 constexpr int kSelLanes = 16;
@@ -537,8 +502,8 @@ constexpr long long kSarlMaxScenes = 1ll << 26;     // S * H * 61 stays far insi
 extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* humans, int B, int H, double time_step, int cell_num,
                                        double cell_size, int om_channel_size, float* maps, rgl_stream_t stream) {
     if ((!humans_f64 && !humans) || !maps) return RGL_ERR_NULL;
-    if (om_channel_size < 1 || om_channel_size > 3) return RGL_ERR_BAD_MODE;
-    if (B < 1 || H < 2 || H + 1 > RGL_MAX_NODES || cell_num < 1 || cell_num > 8 || !(cell_size > 0.0)) return RGL_ERR_BAD_SHAPE;
+    if (sarl_map_params_rc(cell_num, cell_size, om_channel_size) == RGL_ERR_BAD_MODE) return RGL_ERR_BAD_MODE;
+    if (B < 1 || H < 2 || H + 1 > RGL_MAX_NODES || sarl_map_params_rc(cell_num, cell_size, om_channel_size)) return RGL_ERR_BAD_SHAPE;
     const long long total = (long long)B * H * cell_num * cell_num * om_channel_size;
     if (total > (1ll << 31) - 256) return RGL_ERR_BAD_SHAPE;
     hipLaunchKernelGGL(sarl_maps_kernel, dim3((unsigned)((long long)B * H)), dim3(64), 0, (hipStream_t)stream, humans_f64, humans, B,

@@ -14,7 +14,9 @@ time step for all environments at once, so the random stream differs from k sequ
 `DeviceReplayMemory` keeps the experience as the stacked (capacity, ...) tensors alone and is filled by ONE library call per chunk
 of episodes (`push_episodes`, rgl_replay_push_f32): the explorer then records a chunk's states, rewards and info codes into
 preallocated (T, B, ...) tensors instead of per-step clones, and the per-tuple loop of `update_memory` does not run.  It stores
-the same bits in the same slots as `ReplayMemory` filled by `update_memory` (tests/test_replay_push.py).
+the same bits in the same slots as `ReplayMemory` filled by `update_memory` (tests/test_replay_push.py).  For a SARL / OM-SARL target
+after `enable_training()` the call is `push_sarl_episodes` (rgl_replay_push_sarl_f32), which builds `SARL.transform`'s rows -- the
+rotated features and the occupancy maps -- for the states that land in the memory (tests/test_sarl_replay_push.py).
 
 A policy with `acts_in_velocity = True` (orca.OrcaPolicy, the imitation-learning expert of train.py:143-154) returns (B,2)
 velocities from `predict_batch(robot, humans, done=...)`, given the simulator's float64 state; they go to the simulator as
@@ -184,7 +186,8 @@ class DeviceReplayMemory(Dataset):
     device; anything else afterwards is a ValueError (ReplayMemory remains for ragged items).
 
     `push(item)` copies one item into its slot on any torch device.  `push_episodes(...)` stores every transition of a batch of
-    recorded episodes with one library call (rgl_replay_push_f32: device tensors only)."""
+    recorded episodes with one library call (rgl_replay_push_f32: device tensors only), `push_sarl_episodes(...)` the same
+    with SARL / OM-SARL's rows (rgl_replay_push_sarl_f32)."""
 
     def __init__(self, capacity):
         self.capacity = int(capacity)
@@ -270,6 +273,48 @@ class DeviceReplayMemory(Dataset):
         Returns the number of tuples pushed."""
         if layout not in nat.REPLAY_LAYOUTS:
             raise ValueError("unknown layout %r" % (layout,))
+
+        def call(lib, job):
+            job.layout = nat.REPLAY_LAYOUTS[layout]
+            return lib.rgl_replay_push_f32(C.byref(job))
+        return self._push_recorded(robot, humans, rewards, info, kinematics, step_discount, imitation_learning, lengths, outcomes,
+                                   REPLAY_FIELD_SHAPES[layout], call, "rgl_replay_push_f32")
+
+    def push_sarl_episodes(self, robot, humans, rewards, info, kinematics, step_discount, imitation_learning, om=None,
+                           lengths=None, outcomes=None):
+        """`push_episodes` with the rows SARL / OM-SARL train on (rgl_replay_push_sarl_f32): items (state (H,D), value (1,), reward
+        (1,), next state (H,D)), a state being what `SARL.transform` makes of (robot, humans) -- the 13 features of `rotate` under
+        `kinematics` and, with om = (cell_num, cell_size, om_channel_size), D = 13 + cell_num^2 om_channel_size, the slots
+        `occupancy_maps` gives from the float32 human states behind them: the bits `VectorExplorer.update_memory` stores.  om None:
+        D = 13.  Everything else -- the recorded tensors, lengths / outcomes, what synchronises, the return value -- as there."""
+        rows = nat.RglReplaySarlRows()
+        if om is not None:
+            try:
+                cell_num, cell_size, channels = om
+                ok = (int(cell_num) == cell_num and int(channels) == channels and 1 <= cell_num <= 8 and 1 <= channels <= 3
+                      and float(cell_size) > 0.0)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("om must be None or (cell_num 1..8, cell_size > 0, om_channel_size 1..3), not %r" % (om,))
+            rows.cell_num, rows.cell_size, rows.channels = int(cell_num), float(cell_size), int(channels)
+        D = 13 + rows.cell_num ** 2 * rows.channels
+
+        def shapes(H):
+            if om is not None and H < 2:
+                # upstream: np.concatenate of an empty list (multi_human_rl.py:125-126)
+                raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
+            return ((H, D), (1,), (1,), (H, D))
+
+        def call(lib, job):
+            return lib.rgl_replay_push_sarl_f32(C.byref(job), C.byref(rows))
+        return self._push_recorded(robot, humans, rewards, info, kinematics, step_discount, imitation_learning, lengths, outcomes,
+                                   shapes, call, "rgl_replay_push_sarl_f32")
+
+    def _push_recorded(self, robot, humans, rewards, info, kinematics, step_discount, imitation_learning, lengths, outcomes,
+                       field_shapes, call, entry):
+        """What the pushes of recorded episodes share: the argument checks, the slot runs, the workspace and the job.  field_shapes(H)
+        gives the item's field shapes (and refuses an H the layout cannot take); call(lib, job) makes the library call `entry`."""
         if kinematics not in nat.KINEMATICS:
             raise ValueError("unknown kinematics %r" % (kinematics,))
         robot = _require_device_tensor(robot, "recorded robot states")
@@ -284,6 +329,7 @@ class DeviceReplayMemory(Dataset):
         if (tuple(robot.shape) != (T, B, 9) or tuple(humans.shape) != (T, B, H, 5) or tuple(rewards.shape) != (T, B)
                 or tuple(info.shape) != (T, B) or humans.device != robot.device or rewards.device != robot.device):
             raise ValueError("robot (T,B,9), humans (T,B,H,5), rewards (T,B) and info (T,B) must agree and share a device")
+        shapes = field_shapes(H)
         if lengths is None or outcomes is None:
             host = info.cpu().numpy()
             lengths = (host != 5).sum(0)
@@ -296,7 +342,6 @@ class DeviceReplayMemory(Dataset):
             raise ValueError("lengths and outcomes must have one entry per episode")
         stored = ((outcomes == COLLISION) | (outcomes == SUCCESS)) & (lengths > 1)
         n = int((lengths[stored] - 1).sum())
-        shapes = REPLAY_FIELD_SHAPES[layout](H)
         if self._fields is None:
             self._allocate(shapes, torch.float32, robot.device)
         else:
@@ -311,7 +356,7 @@ class DeviceReplayMemory(Dataset):
         job = nat.RglReplayPushJob()
         job.robot, job.humans, job.rewards, job.info = robot.data_ptr(), humans.data_ptr(), rewards.data_ptr(), info.data_ptr()
         job.T, job.B, job.H = T, B, H
-        job.layout, job.kinematics = nat.REPLAY_LAYOUTS[layout], nat.KINEMATICS[kinematics]
+        job.kinematics = nat.KINEMATICS[kinematics]
         job.imitation_learning, job.step_discount, job.capacity = int(bool(imitation_learning)), float(step_discount), self.capacity
         for f, field in enumerate(self._fields):
             job.fields[f] = field.data_ptr()
@@ -321,8 +366,8 @@ class DeviceReplayMemory(Dataset):
         job.workspace, job.workspace_bytes = self._workspace.data_ptr(), self._workspace.numel()
         with torch.cuda.device(robot.device):
             job.stream = _stream()
-            rc = lib.rgl_replay_push_f32(C.byref(job))
-        nat.check(rc, "rgl_replay_push_f32")
+            rc = call(lib, job)
+        nat.check(rc, entry)
         self.position, self._length = position, length
         return n
 
@@ -450,7 +495,8 @@ class VectorExplorer(object):
         # a memory that takes whole chunks (DeviceReplayMemory.push_episodes): the states, rewards and info codes are recorded
         # into (max_steps, B, ...) tensors -- the simulator writes rewards / info / dmin in place -- instead of per-step clones
         record = None
-        if keep_states and hasattr(self.memory, "push_episodes") and not self._sarl_target():
+        if keep_states and hasattr(self.memory, "push_sarl_episodes" if self._sarl_target() else "push_episodes") and (
+                not self._sarl_target() or self.target_policy.training_enabled()):
             record = (torch.empty((max_steps,) + tuple(robot32.shape), dtype=torch.float32, device=sim.device),
                       torch.empty((max_steps,) + tuple(humans32.shape), dtype=torch.float32, device=sim.device),
                       torch.empty(max_steps, B, dtype=torch.float32, device=sim.device),
@@ -599,8 +645,8 @@ class VectorExplorer(object):
         return rotate(joint, self.target_policy.kinematics)
 
     def _sarl_target(self):
-        """The target policy is SARL / OM-SARL: its replay rows come from the host loop (update_memory) whatever the memory's type
-        -- push_episodes has no layout for them."""
+        """The target policy is SARL / OM-SARL: its replay rows carry the occupancy maps (push_sarl_episodes; the host loop of
+        update_memory for a memory without it)."""
         return getattr(self.target_policy, "name", None) in ("SARL", "OM-SARL")
 
     def _sarl_rows(self, states):
@@ -617,12 +663,19 @@ class VectorExplorer(object):
         return rows
 
     def _push_chunk(self, run, imitation_learning):
-        """What the update_memory loop of run_k_episodes stores for one chunk, as one `memory.push_episodes` call."""
+        """What the update_memory loop of run_k_episodes stores for one chunk, as one `memory.push_episodes` call
+        (`push_sarl_episodes` for a SARL / OM-SARL target)."""
         if self.memory is None or self.gamma is None:
             raise ValueError('Memory or gamma value is not set!')
         step_discount = pow(self.gamma, self.sim.cfg.time_step * self.sim.cfg.robot_v_pref)
         mprl = self.target_policy.name == 'ModelPredictiveRL'
         robot, humans, rewards, info = run["recorded"]
+        if self._sarl_target():
+            pol = self.target_policy
+            self.memory.push_sarl_episodes(robot, humans, rewards, info, pol.kinematics, step_discount, imitation_learning,
+                                           om=(pol.cell_num, pol.cell_size, pol.om_channel_size) if pol.with_om else None,
+                                           lengths=run["lengths"], outcomes=run["outcome"])
+            return
         self.memory.push_episodes(robot, humans, rewards, info, "mprl" if mprl else "gcn",
                                   getattr(self.target_policy, "kinematics", None) or "holonomic", step_discount,
                                   imitation_learning, lengths=run["lengths"], outcomes=run["outcome"])

@@ -154,6 +154,21 @@ inline int mlp_max_hidden(const RglMlp& m) {
 
 namespace {
 
+// Workspaces are cut into 256-byte-aligned buffers.  A Carver walks one: take<T>(bytes) is the next buffer, `off` what has been
+// taken so far.  Over a null base it only measures, so a workspace's size query and its pointers are one routine.
+inline long long align_up256(long long x) { return (x + 255) & ~255ll; }
+
+struct Carver {
+    char* base;
+    long long off;
+    template <class T>
+    T* take(long long bytes) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += align_up256(bytes);
+        return p;
+    }
+};
+
 // an integer environment switch, read on every call (a caller that wants it read once per process keeps a `static` of its own)
 inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);

@@ -41,8 +41,6 @@ constexpr int kBlock = 256;
 constexpr int kWave = 64;
 constexpr int kRowFloats = 13;                       // a rotated row
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct ReplayWorkspace {
     int* counts;        // [B] tuples of episode b (0: not stored)
     int* offsets;       // [B + 1] first tuple of episode b; [B] = N
@@ -51,15 +49,12 @@ struct ReplayWorkspace {
 };
 
 inline ReplayWorkspace carve(void* base, int T, int B) {
+    Carver c{(char*)base, 0};
     ReplayWorkspace w;
-    size_t off = 0;
-    w.counts = (int*)((char*)base + off);
-    off = align_up(off + (size_t)B * sizeof(int));
-    w.offsets = (int*)((char*)base + off);
-    off = align_up(off + ((size_t)B + 1) * sizeof(int));
-    w.values = (float*)((char*)base + off);
-    off = align_up(off + (size_t)T * B * sizeof(float));
-    w.bytes = off;
+    w.counts = c.take<int>((long long)B * sizeof(int));
+    w.offsets = c.take<int>(((long long)B + 1) * sizeof(int));
+    w.values = c.take<float>((long long)T * B * sizeof(float));
+    w.bytes = (size_t)c.off;
     return w;
 }
 
@@ -314,10 +309,9 @@ extern "C" size_t rgl_replay_push_workspace_bytes(int T, int B) {
 
 namespace {
 
-// what both pushes do behind their checks: the workspace, the first two launches and the scatter's arguments; `scatter` launches
-// the third
-template <class Scatter>
-inline int push(const RglReplayPushJob* job, const Scatter& scatter) {
+// what both pushes do behind their checks: the workspace and the three launches.  `rows`: the SARL scatter with these maps; null:
+// the scatter of the job's own layout
+inline int push(const RglReplayPushJob* job, const RglReplaySarlRows* rows) {
     if (!job->workspace) return RGL_ERR_NULL;
     const int T = job->T, B = job->B;
     const ReplayWorkspace w = carve(job->workspace, T, B);
@@ -329,7 +323,8 @@ inline int push(const RglReplayPushJob* job, const Scatter& scatter) {
     RGL_LAUNCH_CHECK();
     hipLaunchKernelGGL(replay_offsets_kernel, dim3(1), dim3(kBlock), 0, stream, w.counts, B, w.offsets);
     RGL_LAUNCH_CHECK();
-    ScatterArgs a;
+    SarlScatterArgs sa;
+    ScatterArgs& a = sa.s;
     a.robot = job->robot, a.humans = job->humans, a.rewards = job->rewards, a.values = w.values;
     a.counts = w.counts, a.offsets = w.offsets;
     for (int f = 0; f < RGL_REPLAY_MAX_FIELDS; ++f) a.fields[f] = job->fields[f];
@@ -337,8 +332,20 @@ inline int push(const RglReplayPushJob* job, const Scatter& scatter) {
     a.states = (long long)T * B;
     a.B = B, a.H = job->H, a.n_runs = job->n_runs, a.gcn = job->layout == RGL_REPLAY_GCN;      // (the SARL scatter does not read gcn)
     a.unicycle = job->kinematics == RGL_UNICYCLE, a.imitation_learning = job->imitation_learning != 0;
-    const long long grid = a.states < 65536 ? a.states : 65536;
-    return scatter(a, (unsigned)grid, stream);
+    const dim3 grid((unsigned)(a.states < 65536 ? a.states : 65536));
+    if (!rows) {
+        hipLaunchKernelGGL(replay_scatter_kernel, grid, dim3(kWave), 0, stream, a);
+    } else {
+        sa.cell_num = rows->channels ? rows->cell_num : 0, sa.channels = rows->channels, sa.cell_size = rows->cell_size;
+        sa.group = sarl_group(a.H);
+        const size_t lds = sarl_lds_bytes(a.H, kRowFloats + sa.cell_num * sa.cell_num * sa.channels, sa.channels);
+        if (a.H <= kSarlOneWaveHumans)
+            hipLaunchKernelGGL(replay_sarl_scatter_kernel<1>, grid, dim3(kWave), lds, stream, sa);
+        else
+            hipLaunchKernelGGL(replay_sarl_scatter_kernel<4>, grid, dim3(4 * kWave), lds, stream, sa);
+    }
+    RGL_LAUNCH_CHECK();
+    return RGL_OK;
 }
 
 }  // namespace
@@ -350,11 +357,7 @@ extern "C" int rgl_replay_push_f32(const RglReplayPushJob* job) {
         return RGL_OK;
     });
     if (rc) return rc;
-    return push(job, [](const ScatterArgs& a, unsigned grid, hipStream_t stream) {
-        hipLaunchKernelGGL(replay_scatter_kernel, dim3(grid), dim3(kWave), 0, stream, a);
-        RGL_LAUNCH_CHECK();
-        return RGL_OK;
-    });
+    return push(job, nullptr);
 }
 
 extern "C" int rgl_replay_push_sarl_f32(const RglReplayPushJob* job, const RglReplaySarlRows* rows) {
@@ -367,18 +370,5 @@ extern "C" int rgl_replay_push_sarl_f32(const RglReplayPushJob* job, const RglRe
         return job->H < 2 ? RGL_ERR_BAD_SHAPE : RGL_OK;                             // maps of a single human: no other humans
     });
     if (rc) return rc;
-    return push(job, [&](const ScatterArgs& a, unsigned grid, hipStream_t stream) {
-        SarlScatterArgs sa;
-        sa.s = a;
-        sa.cell_num = rows->channels ? rows->cell_num : 0, sa.channels = rows->channels, sa.cell_size = rows->cell_size;
-        sa.group = sarl_group(a.H);
-        const int D = kRowFloats + sa.cell_num * sa.cell_num * sa.channels;
-        const size_t lds = sarl_lds_bytes(a.H, D, sa.channels);
-        if (a.H <= kSarlOneWaveHumans)
-            hipLaunchKernelGGL(replay_sarl_scatter_kernel<1>, dim3(grid), dim3(kWave), lds, stream, sa);
-        else
-            hipLaunchKernelGGL(replay_sarl_scatter_kernel<4>, dim3(grid), dim3(4 * kWave), lds, stream, sa);
-        RGL_LAUNCH_CHECK();
-        return RGL_OK;
-    });
+    return push(job, rows);
 }

@@ -1,6 +1,6 @@
 // rgl_sarl.hip -- SARL / OM-SARL evaluation: the occupancy maps of MultiHumanRL.build_occupancy_maps
 // (crowd_nav/policy/multi_human_rl.py:117-171), the attention value network of crowd_nav/policy/sarl.py:28-73 and the one-step
-// search of multi_human_rl.py:36-64 around them.  The search's first step (propagate, rotate, reward) is path G's gcn_prepare_f32.
+// search of multi_human_rl.py:36-64 around them.  The search's first and last steps (prepare, select) are the ones path G runs: rgl_onestep.h.
 //
 // The value network is one f32 MFMA launch over all scenes.  A wave owns sixteen scenes; MFMA tile h holds human h of those sixteen
 // scenes as the B operand (column n = scene n), the weights are the A operand.  A 16 x 16 x 4 product leaves output feature
@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "rgl_mfma.h"
+#include "rgl_onestep.h"
 #include "rgl_sarl_maps.h"
 #include "rgl_sarl_shapes.h"
 
@@ -312,50 +313,6 @@ __global__ __launch_bounds__(64) void sarl_maps_kernel(const double* __restrict_
         maps[(size_t)bi * n_slots + slot] = sarl_map_slot(pair_cell, pair_vx, pair_vy, H, slot, channels);
 }
 
-constexpr int kSelLanes = 16;
-
-// value = reward + gamma^(dt v_pref) V in float64 (multi_human_rl.py:58), the strict `>` walk of :60-64 as a first-maximum
-// reduction over 16 lanes per root, and the attention row of the action it selects
-__global__ void sarl_select_kernel(const float* __restrict__ robot, const float* __restrict__ reward, const float* __restrict__ value,
-                                   const float* __restrict__ attention, int B, int A, int H, double gamma, double dt,
-                                   float* __restrict__ action_values, int* __restrict__ best_action, float* __restrict__ best_value,
-                                   float* __restrict__ best_attention) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = t / kSelLanes, sub = t % kSelLanes;
-    const bool live = b < B;
-    double best = -INFINITY;
-    int ba = -1;
-    if (live) {
-        const double disc = pow(gamma, dt * (double)robot[(size_t)b * 9 + 7]);
-        for (int a = sub; a < A; a += kSelLanes) {
-            const double v = (double)reward[(size_t)b * A + a] + disc * (double)value[(size_t)b * A + a];
-            action_values[(size_t)b * A + a] = (float)v;
-            if (v > best) {
-                best = v;
-                ba = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int m = kSelLanes / 2; m >= 1; m >>= 1) {
-        const double ov = __shfl_xor(best, m);
-        const int oa = __shfl_xor(ba, m);
-        if (oa >= 0 && (ba < 0 || ov > best || (ov == best && oa < ba))) {
-            best = ov;
-            ba = oa;
-        }
-    }
-    if (live) {
-        if (sub == 0) {
-            best_action[b] = ba;
-            if (best_value) best_value[b] = ba >= 0 ? (float)best : 0.f;
-        }
-        if (best_attention)
-            for (int h = sub; h < H; h += kSelLanes)
-                best_attention[(size_t)b * H + h] = ba >= 0 ? attention[((size_t)b * A + ba) * H + h] : 0.f;
-    }
-}
-
 struct SarlLayout {
     int KT[kSarlLayers], MT[kSarlLayers];
     long long off[kSarlLayers], total;      // floats
@@ -497,6 +454,44 @@ int launch_sarl_value(const SarlPlanner& pl, const SarlLayout& L, const float* p
 
 constexpr long long kSarlMaxScenes = 1ll << 26;     // S * H * 61 stays far inside size_t; S itself inside int
 
+// sarl_value_f32's workspace: the packed weights | the parking regions of a launch over S scenes of H humans (S = 0: the weights alone)
+struct SarlValueScratch {
+    float* packed;
+    float* park;
+    long long park_bytes, bytes;
+};
+
+inline SarlValueScratch carve_sarl_value(void* base, const SarlPlanner& pl, long long S, int H) {
+    Carver c{(char*)base, 0};
+    SarlValueScratch w;
+    w.packed = c.take<float>(sarl_layout(pl).total * 4);
+    w.park_bytes = sarl_park_bytes(S, H);
+    w.park = c.take<float>(w.park_bytes);
+    w.bytes = c.off;
+    return w;
+}
+
+// sarl_predict_f32's workspace: the one-step buffers | attention weights [S][H] | maps [B][H][map floats] | sarl_value_f32's
+struct SarlPredictScratch {
+    OneStepScratch one;
+    float* attention;
+    float* maps;
+    SarlValueScratch net;
+    long long bytes;
+};
+
+inline SarlPredictScratch carve_sarl_predict(void* base, const SarlPlanner& pl, int B, int H) {
+    const long long S = (long long)B * pl.num_actions;
+    SarlPredictScratch w;
+    w.one = carve_onestep(base, S, H);
+    Carver c{(char*)base, w.one.bytes};
+    w.attention = c.take<float>(S * H * 4);
+    w.maps = c.take<float>((long long)B * H * sarl_map_floats(pl) * 4 + 4);
+    w.net = carve_sarl_value(base ? c.base + c.off : nullptr, pl, S, H);
+    w.bytes = c.off + w.net.bytes;
+    return w;
+}
+
 }  // namespace
 
 extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* humans, int B, int H, double time_step, int cell_num,
@@ -514,12 +509,12 @@ extern "C" int sarl_occupancy_maps_f32(const double* humans_f64, const float* hu
 
 extern "C" size_t sarl_value_workspace_bytes(const SarlPlanner* planner) {
     if (!planner || validate_sarl(*planner, -1)) return 0;
-    return (size_t)align_up256(sarl_layout(*planner).total * 4);
+    return (size_t)carve_sarl_value(nullptr, *planner, 0, 0).bytes;
 }
 
 extern "C" size_t sarl_value_workspace_bytes_for(const SarlPlanner* planner, int n_scenes, int H) {
     if (!planner || n_scenes < 1 || n_scenes > kSarlMaxScenes || validate_sarl(*planner, H)) return 0;
-    return (size_t)(align_up256(sarl_layout(*planner).total * 4) + sarl_park_bytes(n_scenes, H));
+    return (size_t)carve_sarl_value(nullptr, *planner, n_scenes, H).bytes;
 }
 
 extern "C" int sarl_value_f32(const SarlPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
@@ -533,23 +528,21 @@ extern "C" int sarl_value_f32(const SarlPlanner* planner, const float* rows, con
     if (n_scenes < 1 || n_scenes > kSarlMaxScenes) return RGL_ERR_BAD_SHAPE;
     if (rows) scenes_per_root = 1;
     if (scenes_per_root < 1 || n_scenes % scenes_per_root) return RGL_ERR_BAD_SHAPE;
-    const size_t packed_bytes = sarl_value_workspace_bytes(planner);
-    if (workspace_bytes < packed_bytes + (size_t)sarl_park_bytes(n_scenes, H)) return RGL_ERR_WORKSPACE;
+    const SarlValueScratch w = carve_sarl_value(workspace, pl, n_scenes, H);
+    if (workspace_bytes < (size_t)w.bytes) return RGL_ERR_WORKSPACE;
     const SarlLayout L = sarl_layout(pl);
     hipStream_t st = (hipStream_t)stream;
-    const int prc = launch_sarl_pack(pl, L, (float*)workspace, st);
+    const int prc = launch_sarl_pack(pl, L, w.packed, st);
     if (prc) return prc;
-    return launch_sarl_value(pl, L, (const float*)workspace, rows, self6, hum7, maps, n_scenes, scenes_per_root, H, value, attention,
-                             (float*)((char*)workspace + packed_bytes), workspace_bytes - packed_bytes, st);
+    return launch_sarl_value(pl, L, w.packed, rows, self6, hum7, maps, n_scenes, scenes_per_root, H, value, attention, w.park,
+                             (size_t)w.park_bytes, st);
 }
 
 extern "C" size_t sarl_predict_workspace_bytes(const SarlPlanner* planner, int B, int H) {
     if (!planner || B < 1 || validate_sarl(*planner, H)) return 0;
     const long long S = (long long)B * planner->num_actions;
     if (planner->num_actions < 1 || planner->num_actions > RGL_MAX_ACTIONS || S > kSarlMaxScenes) return 0;
-    return (size_t)(align_up256(S * 6 * 4) + align_up256(S * H * 7 * 4) + align_up256(S * 4) + align_up256(S * 4) + align_up256(S * H * 4) +
-                    align_up256((long long)B * H * sarl_map_floats(*planner) * 4 + 4) + align_up256(sarl_layout(*planner).total * 4) +
-                    sarl_park_bytes(S, H));
+    return (size_t)carve_sarl_predict(nullptr, *planner, B, H).bytes;
 }
 
 extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, const float* humans, int B, int H, void* workspace,
@@ -558,6 +551,7 @@ extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, 
     if (!planner || !robot || !humans || !workspace || !action_values || !best_action) return RGL_ERR_NULL;
     if (B < 1) return RGL_ERR_BAD_SHAPE;
     const SarlPlanner& pl = *planner;
+    // validate_sarl bounds H by RGL_MAX_NODES - 1: with the three checks behind it, everything gcn_prepare_f32 asks of a search
     int rc = validate_sarl(pl, H);
     if (rc) return rc;
     const int A = pl.num_actions;
@@ -566,42 +560,25 @@ extern "C" int sarl_predict_f32(const SarlPlanner* planner, const float* robot, 
     if (!pl.actions) return RGL_ERR_NULL;
     const long long S = (long long)B * A;
     if (S > kSarlMaxScenes) return RGL_ERR_BAD_SHAPE;
-    if (workspace_bytes < sarl_predict_workspace_bytes(planner, B, H)) return RGL_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
-    float* self6 = (float*)ws;      ws += align_up256(S * 6 * 4);
-    float* hum7 = (float*)ws;       ws += align_up256(S * H * 7 * 4);
-    float* reward = (float*)ws;     ws += align_up256(S * 4);
-    float* value = (float*)ws;      ws += align_up256(S * 4);
-    float* att = (float*)ws;        ws += align_up256(S * H * 4);
-    float* maps = (float*)ws;       ws += align_up256((long long)B * H * sarl_map_floats(pl) * 4 + 4);
-    float* packed = (float*)ws;     ws += align_up256(sarl_layout(pl).total * 4);
-    float* park = (float*)ws;
-    const size_t park_bytes = workspace_bytes - (size_t)(ws - (char*)workspace);
+    const SarlPredictScratch w = carve_sarl_predict(workspace, pl, B, H);
+    if (workspace_bytes < (size_t)w.bytes) return RGL_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     // propagate, constant-velocity humans, rotate, reward: path G's first step as it stands
-    GcnPlanner gp = {};
-    gp.kinematics = pl.kinematics;
-    gp.num_actions = A;
-    gp.time_step = pl.time_step;
-    gp.gamma = pl.gamma;
-    gp.actions = pl.actions;
-    gp.root_robot_f64 = pl.root_robot_f64;
-    gp.root_humans_f64 = pl.root_humans_f64;
-    rc = gcn_prepare_f32(&gp, robot, humans, B, H, self6, hum7, reward, stream);
+    rc = launch_gcn_prepare(pl.kinematics, A, pl.time_step, pl.actions, pl.root_robot_f64, pl.root_humans_f64, robot, humans, B, H,
+                            w.one.self6, w.one.hum7, w.one.reward, st);
     if (rc) return rc;
     if (pl.om_channel_size) {       // once per root and human: without query_env the maps do not depend on the action (:52-55)
-        const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;      // as gcn_prepare_f32 chooses its source
+        const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;      // as launch_gcn_prepare chooses its source
         rc = sarl_occupancy_maps_f32(r64 ? pl.root_humans_f64 : nullptr, humans, B, H, pl.time_step, pl.cell_num, pl.cell_size,
-                                     pl.om_channel_size, maps, stream);
+                                     pl.om_channel_size, w.maps, stream);
         if (rc) return rc;
     }
     const SarlLayout L = sarl_layout(pl);
-    rc = launch_sarl_pack(pl, L, packed, st);
+    rc = launch_sarl_pack(pl, L, w.net.packed, st);
     if (rc) return rc;
-    rc = launch_sarl_value(pl, L, packed, nullptr, self6, hum7, maps, S, A, H, value, att, park, park_bytes, st);
+    rc = launch_sarl_value(pl, L, w.net.packed, nullptr, w.one.self6, w.one.hum7, w.maps, S, A, H, w.one.value, w.attention, w.net.park,
+                           (size_t)w.net.park_bytes, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(sarl_select_kernel, dim3((unsigned)(((long long)B * kSelLanes + 255) / 256)), dim3(256), 0, st, robot, reward, value,
-                       att, B, A, H, pl.gamma, pl.time_step, action_values, best_action, best_value, best_attention);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return launch_onestep_select(robot, w.one.reward, w.one.value, w.attention, B, A, H, pl.gamma, pl.time_step, action_values,
+                                 best_action, best_value, best_attention, st);
 }

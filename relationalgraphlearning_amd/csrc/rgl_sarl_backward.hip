@@ -247,34 +247,28 @@ inline SarlTrainShape sarl_train_shape(const SarlPlanner& pl) {
 enum { bH1, bAIN, bA1, bA2, bSC, bM1, bFEAT, bATT, bDFEAT, bDSC, bDM1, bDA2, bDA1, bDAIN, bDYM, bDY, bDH1, kRowBuffers };
 enum { bJOINT, bP1, bP2, bP3, bDP3, bDP2, bDP1, bDJOINT, kSceneBuffers };
 
-inline void sarl_train_widths(int KA, int (&row)[kRowBuffers], int (&scene)[kSceneBuffers]) {
-    const int r[kRowBuffers] = {150, KA, 100, 100, 1, 100, 50, 1, 50, 1, 100, 100, 100, KA, 100, 100, 150};
-    const int s[kSceneBuffers] = {56, 150, 100, 100, 100, 100, 150, 56};
-    for (int i = 0; i < kRowBuffers; ++i) row[i] = r[i];
-    for (int i = 0; i < kSceneBuffers; ++i) scene[i] = s[i];
-}
-
-inline long long sarl_backward_bytes(int KA, long long S, int H) {
-    int row[kRowBuffers], scene[kSceneBuffers];
-    sarl_train_widths(KA, row, scene);
-    long long bytes = 0;
-    for (int i = 0; i < kRowBuffers; ++i) bytes += align_up256(S * H * row[i] * 4);
-    for (int i = 0; i < kSceneBuffers; ++i) bytes += align_up256(S * scene[i] * 4);
-    return bytes;
-}
-
-struct SarlTrainLayout {
-    size_t value_bytes, att_bytes, backward_bytes;
-    size_t total() const { return value_bytes + att_bytes + backward_bytes; }
+// [sarl_value_f32's workspace | attention weights of a call that asks for none | the backward's buffers: rb of R = S H rows each,
+// sb of S rows each]; over a null base the sizes alone.  false: unsupported
+struct SarlTrainScratch {
+    size_t value_bytes;
+    float* attention;
+    float *rb[kRowBuffers], *sb[kSceneBuffers];
+    long long bytes;
 };
 
-// [sarl_value_f32's workspace | attention weights of a call that asks for none | the backward's buffers]; false: unsupported
-inline bool sarl_train_layout(const SarlPlanner& pl, int n_scenes, int H, SarlTrainLayout& L) {
+inline bool carve_sarl_train(void* base, const SarlPlanner& pl, int n_scenes, int H, SarlTrainScratch& w) {
     if (n_scenes < 1 || H < 1 || (long long)n_scenes * H > kTrainMaxRows) return false;
-    L.value_bytes = sarl_value_workspace_bytes_for(&pl, n_scenes, H);
-    if (!L.value_bytes) return false;
-    L.att_bytes = (size_t)align_up256((long long)n_scenes * H * 4);
-    L.backward_bytes = (size_t)sarl_backward_bytes(pl.with_global_state ? 200 : 100, n_scenes, H);
+    w.value_bytes = sarl_value_workspace_bytes_for(&pl, n_scenes, H);
+    if (!w.value_bytes) return false;
+    const int KA = pl.with_global_state ? 200 : 100;
+    const int row[kRowBuffers] = {150, KA, 100, 100, 1, 100, 50, 1, 50, 1, 100, 100, 100, KA, 100, 100, 150};
+    const int scene[kSceneBuffers] = {56, 150, 100, 100, 100, 100, 150, 56};
+    const long long S = n_scenes, R = S * H;
+    Carver c{(char*)base, (long long)w.value_bytes};
+    w.attention = c.take<float>(R * 4);
+    for (int i = 0; i < kRowBuffers; ++i) w.rb[i] = c.take<float>(R * row[i] * 4);
+    for (int i = 0; i < kSceneBuffers; ++i) w.sb[i] = c.take<float>(S * scene[i] * 4);
+    w.bytes = c.off;
     return true;
 }
 
@@ -331,20 +325,20 @@ struct SarlGemmLaunch {
 }  // namespace
 
 extern "C" size_t sarl_train_workspace_bytes(const SarlPlanner* planner, int n_scenes, int H) {
-    SarlTrainLayout L;
-    if (!planner || validate_sarl(*planner, H) || !sarl_train_layout(*planner, n_scenes, H, L)) return 0;
-    return L.total();
+    SarlTrainScratch w;
+    if (!planner || validate_sarl(*planner, H) || !carve_sarl_train(nullptr, *planner, n_scenes, H, w)) return 0;
+    return (size_t)w.bytes;
 }
 
 extern "C" int sarl_value_train_f32(const SarlPlanner* planner, const float* rows, int n_scenes, int H, void* workspace,
                                     size_t workspace_bytes, float* value, float* attention, rgl_stream_t stream) {
     if (!planner || !rows || !workspace || !value) return RGL_ERR_NULL;
     SARL_TRY(validate_sarl(*planner, H));
-    SarlTrainLayout L;
-    if (!sarl_train_layout(*planner, n_scenes, H, L)) return RGL_ERR_BAD_SHAPE;
-    if (workspace_bytes < L.total()) return RGL_ERR_WORKSPACE;
-    if (!attention) attention = (float*)((char*)workspace + L.value_bytes);
-    return sarl_value_f32(planner, rows, nullptr, nullptr, nullptr, n_scenes, 1, H, workspace, L.value_bytes, value, attention, stream);
+    SarlTrainScratch w;
+    if (!carve_sarl_train(workspace, *planner, n_scenes, H, w)) return RGL_ERR_BAD_SHAPE;
+    if (workspace_bytes < (size_t)w.bytes) return RGL_ERR_WORKSPACE;
+    if (!attention) attention = w.attention;
+    return sarl_value_f32(planner, rows, nullptr, nullptr, nullptr, n_scenes, 1, H, workspace, w.value_bytes, value, attention, stream);
 }
 
 extern "C" int sarl_value_backward_f32(const SarlPlanner* planner, const float* rows, const float* grad_value, int n_scenes, int H,
@@ -353,21 +347,17 @@ extern "C" int sarl_value_backward_f32(const SarlPlanner* planner, const float* 
     for (int l = 0; l < kLayers; ++l)
         if (!grads->weight[l] || !grads->bias[l]) return RGL_ERR_NULL;
     SARL_TRY(validate_sarl(*planner, H));
-    SarlTrainLayout L;
-    if (!sarl_train_layout(*planner, n_scenes, H, L)) return RGL_ERR_BAD_SHAPE;
-    if (workspace_bytes < L.total()) return RGL_ERR_WORKSPACE;
+    SarlTrainScratch w;
+    if (!carve_sarl_train(workspace, *planner, n_scenes, H, w)) return RGL_ERR_BAD_SHAPE;
+    if (workspace_bytes < (size_t)w.bytes) return RGL_ERR_WORKSPACE;
     const SarlTrainShape sh = sarl_train_shape(*planner);
     const long long S = n_scenes, R = S * H;
     const int KA = sh.KA, D = sh.D;
     const bool global = planner->with_global_state != 0;
     hipStream_t st = (hipStream_t)stream;
 
-    int roww[kRowBuffers], scenew[kSceneBuffers];
-    sarl_train_widths(KA, roww, scenew);
-    float *rb[kRowBuffers], *sb[kSceneBuffers];
-    char* p = (char*)workspace + L.value_bytes + L.att_bytes;
-    for (int i = 0; i < kRowBuffers; ++i) { rb[i] = (float*)p; p += align_up256(R * roww[i] * 4); }
-    for (int i = 0; i < kSceneBuffers; ++i) { sb[i] = (float*)p; p += align_up256(S * scenew[i] * 4); }
+    float* const* rb = w.rb;
+    float* const* sb = w.sb;
     const float* y = rb[bAIN];              // mlp1's outputs: the first 100 columns of the attention input, row stride KA
 
     // ---- the activations again ----

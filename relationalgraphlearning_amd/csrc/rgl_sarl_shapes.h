@@ -4,8 +4,6 @@
 
 namespace {
 
-inline long long align_up256(long long x) { return (x + 255) & ~255ll; }
-
 inline int sarl_map_floats(const SarlPlanner& pl) { return pl.om_channel_size ? pl.cell_num * pl.cell_num * pl.om_channel_size : 0; }
 
 // the shapes the value kernel is built for; `H` < 0: the planner alone

@@ -1,5 +1,5 @@
 // rgl_tree.hip -- the model-predictive rollout on device (path M) and the one-step search of
-// path G.  Level-synchronous: every tree level is a handful of launches over ALL parents of
+// path G (its prepare and select steps: rgl_onestep.h).  Level-synchronous: every tree level is a handful of launches over ALL parents of
 // that level, no host round trip, no allocation (caller-provided workspace) -> capturable in a
 // hipGraph.
 //
@@ -7,8 +7,7 @@
 // action_clip, V_planning, estimate_reward), state_predictor.py:41-60,109-118,
 // crowd_sim/envs/utils/utils.py:4-26, multi_human_rl.py:36-96, cadrl.py:113-138,241-276.
 #include "rgl_scene_body.h"
-#include "rgl_rotate.h"
-#include "rgl_tail.h"
+#include "rgl_onestep.h"
 
 #include <cstdlib>
 
@@ -91,127 +90,6 @@ __global__ void gcn_rotate_kernel(const float* __restrict__ in14, float* __restr
     for (int k = 0; k < 13; ++k) out13[(size_t)i * 13 + k] = o[k];
 }
 
-// One thread per (scene, action, human): propagate, rotate; thread h == 0 also does compute_reward.
-__global__ void gcn_prepare_kernel(const float* __restrict__ robot, const float* __restrict__ humans,
-                                   const double* __restrict__ robot64, const double* __restrict__ humans64,
-                                   const double* __restrict__ actions, int B, int H, int A, int kinematics, double dt,
-                                   float* __restrict__ self6, float* __restrict__ hum7, float* __restrict__ reward) {
-    // python-float arithmetic: every float64 product and sum below is rounded on its own (a contracted end-point clearance turns an
-    // exact contact, clearance 0, into a collision)
-#pragma clang fp contract(off)
-    // blockDim.x is a multiple of H: the H threads of a (root, action) pair sit in one workgroup, each contributes ITS human's
-    // end-point clearance (one float64 sqrt per thread) and thread h == 0 takes the minimum -- it used to walk all H itself
-    extern __shared__ double clearance[];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < (long long)B * A * H;
-    const long long cidx = live ? idx : 0;
-    const int h = (int)(cidx % H);
-    const long long sa = cidx / H;
-    const int a = (int)(sa % A), b = (int)(sa / A);
-    const float* r = robot + (size_t)b * 9;
-    const double* r64 = robot64 ? robot64 + (size_t)b * 9 : nullptr;        // the float64 state the fp32 row was rounded from
-    auto R = [&](int i) { return r64 ? r64[i] : (double)r[i]; };
-    const double a0 = actions[2 * a], a1 = actions[2 * a + 1];
-    // CADRL.propagate in float64, as python floats
-    double nr[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) nr[i] = R(i);
-    if (kinematics == RGL_HOLONOMIC) {
-        nr[0] = R(0) + a0 * dt;
-        nr[1] = R(1) + a1 * dt;
-        nr[2] = a0;
-        nr[3] = a1;
-    } else {
-        const double th = R(8) + a1;
-        nr[2] = a0 * cos(th);
-        nr[3] = a0 * sin(th);
-        nr[0] = R(0) + nr[2] * dt;
-        nr[1] = R(1) + nr[3] * dt;
-        nr[8] = th;
-    }
-    const float* hu = humans + ((size_t)b * H + h) * 5;
-    const double* hb64 = humans64 ? humans64 + (size_t)b * H * 5 : nullptr;
-    auto HB = [&](int j, int i) { return hb64 ? hb64[j * 5 + i] : (double)humans[((size_t)b * H + j) * 5 + i]; };
-    float s[14], o[13];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) s[i] = (float)nr[i];
-    s[9] = (float)(HB(h, 0) + HB(h, 2) * dt);
-    s[10] = (float)(HB(h, 1) + HB(h, 3) * dt);
-    s[11] = hb64 ? (float)HB(h, 2) : hu[2];
-    s[12] = hb64 ? (float)HB(h, 3) : hu[3];
-    s[13] = hb64 ? (float)HB(h, 4) : hu[4];
-    rotate_row(s, kinematics == RGL_UNICYCLE, o);
-    if (live) {
-        float* h7 = hum7 + ((size_t)sa * H + h) * 7;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) h7[i] = o[6 + i];
-    }
-    {   // compute_reward (multi_human_rl.py:73-96): END-point distance of my human, float64
-        const double hx = HB(h, 0) + HB(h, 2) * dt;
-        const double hy = HB(h, 1) + HB(h, 3) * dt;
-        const double ddx = nr[0] - hx, ddy = nr[1] - hy;
-        clearance[threadIdx.x] = sqrt(ddx * ddx + ddy * ddy) - nr[4] - HB(h, 4);
-    }
-    __syncthreads();
-    if (live && h == 0) {
-        float* s6 = self6 + (size_t)sa * 6;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) s6[i] = o[i];
-        bool collision = false;
-        double dmin = INFINITY;
-        for (int j = 0; j < H; ++j) {
-            const double d = clearance[threadIdx.x + j];
-            if (d < 0.0) collision = true;
-            if (d < dmin) dmin = d;
-        }
-        const double gx = nr[0] - nr[5], gy = nr[1] - nr[6];
-        const bool reaching = sqrt(gx * gx + gy * gy) < nr[4];
-        double rew;
-        if (collision) rew = -0.25;
-        else if (reaching) rew = 1.0;
-        else if (dmin < 0.2) rew = (dmin - 0.2) * 0.5 * dt;
-        else rew = 0.0;
-        reward[sa] = (float)rew;
-    }
-}
-
-// 16 lanes per root (kRootLanes): the A action values side by side, then a first-maximum reduction -- one thread walking 81 actions
-// cost 25 us per call
-__global__ void gcn_argmax_kernel(const float* __restrict__ robot, const float* __restrict__ reward,
-                                  const float* __restrict__ value, int B, int A, double gamma, double dt,
-                                  float* __restrict__ action_values, int* __restrict__ best_action, float* __restrict__ best_value) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = t / kRootLanes, sub = t % kRootLanes;
-    const bool live = b < B;
-    double best = -INFINITY;
-    int ba = -1;
-    if (live) {
-        const double disc = pow(gamma, dt * (double)robot[(size_t)b * 9 + 7]);
-        for (int a = sub; a < A; a += kRootLanes) {
-            const double v = (double)reward[(size_t)b * A + a] + disc * (double)value[(size_t)b * A + a];
-            action_values[(size_t)b * A + a] = (float)v;
-            if (v > best) {
-                best = v;
-                ba = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int m = kRootLanes / 2; m >= 1; m >>= 1) {
-        const double ov = __shfl_xor(best, m);
-        const int oa = __shfl_xor(ba, m);
-        const bool take = oa >= 0 && (ba < 0 || ov > best || (ov == best && oa < ba));
-        if (take) {
-            best = ov;
-            ba = oa;
-        }
-    }
-    if (live && sub == 0) {
-        best_action[b] = ba;
-        if (best_value) best_value[b] = ba >= 0 ? (float)best : 0.f;      // = action_values[b][ba]: what callers used to gather
-    }
-}
-
 inline dim3 grid_for(long long n, int block = kBlock) { return dim3((unsigned)((n + block - 1) / block)); }
 
 // ------------------------------------------------------------------------------------------------
@@ -223,8 +101,6 @@ struct LevelLayout {
     long long reward_clip;      // level 0 only (-1 elsewhere): the root rewards as upstream's action_clip reads them
 };
 
-inline long long align_up(long long x) { return (x + 255) & ~255ll; }
-
 inline int plan_levels(const MprlPlanner& pl, int B, int H, LevelLayout* lv, long long* total,
                        long long* scratch_off = nullptr, long long* scratch_bytes = nullptr) {
     const int A = pl.num_actions, D = pl.planning_depth;
@@ -233,18 +109,18 @@ inline int plan_levels(const MprlPlanner& pl, int B, int H, LevelLayout* lv, lon
     for (int l = 0; l < D; ++l) {
         LevelLayout& L = lv[l];
         L.P = P;
-        L.robot = off;        off = align_up(off + (l == 0 ? 0 : P * 9 * 4));          // level 0 reads the caller's arrays
+        L.robot = off;        off = align_up256(off + (l == 0 ? 0 : P * 9 * 4));          // level 0 reads the caller's arrays
         L.humans = -1;                                                               // = previous level's humans_next
-        L.humans_next = off;  off = align_up(off + P * H * 5 * 4);
-        L.child_robot = off;  off = align_up(off + P * A * 9 * 4);
-        L.reward = off;       off = align_up(off + P * A * 4);
+        L.humans_next = off;  off = align_up256(off + P * H * 5 * 4);
+        L.child_robot = off;  off = align_up256(off + P * A * 9 * 4);
+        L.reward = off;       off = align_up256(off + P * A * 4);
         L.reward_clip = -1;
-        if (l == 0) { L.reward_clip = off; off = align_up(off + P * A * 4); }
-        L.child_value = off;  off = align_up(off + P * A * 4);
-        L.value1 = off;       off = align_up(off + P * A * 4);
-        L.keep = off;         off = align_up(off + P * W * 4);
-        L.backup = off;       off = align_up(off + P * W * 4);
-        L.best_slot = off;    off = align_up(off + P * 4);
+        if (l == 0) { L.reward_clip = off; off = align_up256(off + P * A * 4); }
+        L.child_value = off;  off = align_up256(off + P * A * 4);
+        L.value1 = off;       off = align_up256(off + P * A * 4);
+        L.keep = off;         off = align_up256(off + P * W * 4);
+        L.backup = off;       off = align_up256(off + P * W * 4);
+        L.best_slot = off;    off = align_up256(off + P * 4);
         if (l > 0) lv[l].humans = lv[l - 1].humans_next;
         if (l + 1 < D) P *= W;
         if (P > (1ll << 31) / (A * 9)) return RGL_ERR_BAD_SHAPE;
@@ -253,9 +129,9 @@ inline int plan_levels(const MprlPlanner& pl, int B, int H, LevelLayout* lv, lon
     const long long sb = (long long)rgl::value_children_workspace_bytes(&pl, (int)P, H);
     if (scratch_off) *scratch_off = off;
     if (scratch_bytes) *scratch_bytes = sb;
-    off = align_up(off + sb);
+    off = align_up256(off + sb);
     // split-f16 image of the state predictor's scene kernel, packed once per search unless the caller hands one in
-    off = align_up(off + (long long)rgl::scene_image_bytes(&pl));
+    off = align_up256(off + (long long)rgl::scene_image_bytes(&pl));
     *total = off;
     return RGL_OK;
 }
@@ -485,7 +361,7 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
                                                        (size_t)scratch_bytes, st, image_mode) == 0);
     const float* sp_image = pl.predictor_image;
     if (!sp_image && rgl::scene_image_bytes(&pl)) {
-        float* img = (float*)(ws + align_up(scratch_off + scratch_bytes));
+        float* img = (float*)(ws + align_up256(scratch_off + scratch_bytes));
         if (rgl::pack_scene_image(&pl, img, st) == RGL_OK) sp_image = img;
     }
     TailArgs tail{};
@@ -648,18 +524,6 @@ extern "C" int gcn_rotate_f32(const float* joint14, float* rotated13, int n_rows
     return RGL_OK;
 }
 
-static int launch_gcn_prepare(const GcnPlanner& pl, const float* robot, const float* humans, int B, int H, float* self6, float* hum7,
-                              float* reward, hipStream_t st) {
-    const long long S = (long long)B * pl.num_actions;
-    const int prep_threads = (H >= kBlock ? 1 : kBlock / H) * H;        // whole (root, action) groups per workgroup
-    const bool r64 = pl.root_robot_f64 && pl.root_humans_f64;
-    hipLaunchKernelGGL(gcn_prepare_kernel, grid_for(S * H, prep_threads), dim3(prep_threads), prep_threads * sizeof(double), st, robot,
-                       humans, r64 ? pl.root_robot_f64 : nullptr, r64 ? pl.root_humans_f64 : nullptr, pl.actions, B, H, pl.num_actions,
-                       pl.kinematics, pl.time_step, self6, hum7, reward);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
-}
-
 // propagate + rotate + compute_reward for the B x A candidate scenes of a one-step search on their own (ABI 5): the first launch of
 // gcn_predict_f32 (cadrl.py:113-138,241-276, multi_human_rl.py:46-51,73-96), exported for GCN.compute_reward / tests
 extern "C" int gcn_prepare_f32(const GcnPlanner* planner, const float* robot, const float* humans, int B, int H,
@@ -667,18 +531,42 @@ extern "C" int gcn_prepare_f32(const GcnPlanner* planner, const float* robot, co
     if (!planner || !robot || !humans || !self6 || !hum7 || !reward) return RGL_ERR_NULL;
     if (B < 1 || H < 1 || H + 1 > RGL_MAX_NODES) return RGL_ERR_BAD_SHAPE;
     const int rc = validate_actions(planner->num_actions, planner->actions, planner->kinematics, true);
-    return rc ? rc : launch_gcn_prepare(*planner, robot, humans, B, H, self6, hum7, reward, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_gcn_prepare(planner->kinematics, planner->num_actions, planner->time_step, planner->actions, planner->root_robot_f64,
+                              planner->root_humans_f64, robot, humans, B, H, self6, hum7, reward, (hipStream_t)stream);
 }
+
+namespace {
 
 constexpr long long kGcnImageBytes = 64 * 1024;      // >= scene_image_bytes_for(): Wa + 4 layer matrices + motion-head slots as 6-byte weights
 
+// gcn_predict_f32's workspace: rotated features, rewards, values | the scratch of the MFMA forward (embeddings [S][32], [S][H][32],
+// value rows [S][64]) | room for the scene kernel's three-piece bf16 weight image (RGL_CONTRACT_BF16X6: packed per call, 4 layer
+// matrices at most)
+struct GcnPredictScratch {
+    OneStepScratch one;
+    void* fwd;
+    float* image;
+    size_t fwd_bytes;
+    long long bytes;
+};
+
+inline GcnPredictScratch carve_gcn_predict(void* base, long long S, int H) {
+    GcnPredictScratch w;
+    w.one = carve_onestep(base, S, H);
+    Carver c{(char*)base, w.one.bytes};
+    w.fwd = c.take<char>(S * (32 + (long long)H * 32 + 64) * 4);
+    w.fwd_bytes = (size_t)(c.off - w.one.bytes);
+    w.image = c.take<float>(kGcnImageBytes);
+    w.bytes = c.off;
+    return w;
+}
+
+}  // namespace
+
 extern "C" size_t gcn_predict_workspace_bytes(int B, int H, int A) {
     if (B < 1 || H < 1 || A < 1) return 0;
-    const long long S = (long long)B * A;
-    // rotated features, rewards, values + the scratch of the MFMA forward (embeddings [S][32], [S][H][32], value rows [S][64])
-    // + room for the scene kernel's three-piece bf16 weight image (RGL_CONTRACT_BF16X6: packed per call, 4 layer matrices at most)
-    return (size_t)(align_up(S * 6 * 4) + align_up(S * H * 7 * 4) + align_up(S * 4) + align_up(S * 4) +
-                    align_up(S * (32 + (long long)H * 32 + 64) * 4) + kGcnImageBytes);
+    return (size_t)carve_gcn_predict(nullptr, (long long)B * A, H).bytes;
 }
 
 extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, const float* humans, int B, int H,
@@ -696,43 +584,34 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
     if (rc) return rc;
     if (pl.contraction_dtype != RGL_CONTRACT_F32 && pl.contraction_dtype != RGL_CONTRACT_BF16X6) return RGL_ERR_BAD_MODE;
     const int A = pl.num_actions;
-    if (workspace_bytes < gcn_predict_workspace_bytes(B, H, A)) return RGL_ERR_WORKSPACE;
     const long long S = (long long)B * A;
-    char* ws = (char*)workspace;
-    float* self6 = (float*)ws;              ws += align_up(S * 6 * 4);
-    float* hum7 = (float*)ws;               ws += align_up(S * H * 7 * 4);
-    float* reward = (float*)ws;             ws += align_up(S * 4);
-    float* value = (float*)ws;              ws += align_up(S * 4);
-    void* fwd_ws = ws;
-    const size_t fwd_bytes = (size_t)align_up(S * (32 + (long long)H * 32 + 64) * 4);
+    const GcnPredictScratch w = carve_gcn_predict(workspace, S, H);
+    if (workspace_bytes < (size_t)w.bytes) return RGL_ERR_WORKSPACE;
+    float *self6 = w.one.self6, *hum7 = w.one.hum7, *reward = w.one.reward, *value = w.one.value;
     hipStream_t st = (hipStream_t)stream;
     // RGL_CONTRACT_BF16X6: the graph's Wa / W_l as three-piece bf16 fragments for the scene kernel's value-rows mode, packed here
     // (one ~4 us launch beside a forward of hundreds; the weights may have changed since the last call)
     const float* rows_image = nullptr;
     if (pl.contraction_dtype == RGL_CONTRACT_BF16X6) {
         const size_t ib = rgl::scene_image_bytes_for(pl.graph, nullptr);
-        if (ib && ib <= kGcnImageBytes) {
-            float* img = (float*)(ws + fwd_bytes);
-            if (rgl::pack_scene_image_for(pl.graph, nullptr, img, st) == RGL_OK) rows_image = img;
-        }
+        if (ib && ib <= kGcnImageBytes && rgl::pack_scene_image_for(pl.graph, nullptr, w.image, st) == RGL_OK) rows_image = w.image;
     }
-    rc = launch_gcn_prepare(pl, robot, humans, B, H, self6, hum7, reward, st);
+    rc = launch_gcn_prepare(pl.kinematics, A, pl.time_step, pl.actions, pl.root_robot_f64, pl.root_humans_f64, robot, humans, B, H, self6,
+                            hum7, reward, st);
     if (rc) return rc;
     // the B x A rotated scenes: one wave per scene on the MFMA kernel where it covers the model (the shipped ValueNetwork: 6 / 7
     // inputs, 64-32 embeddings, head 150-100-100-1), else the general kernel
-    rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, fwd_ws, fwd_bytes,
+    rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, w.fwd, w.fwd_bytes,
                                    st, rows_image);
     if (rc == 1)      // other embedding MLPs (x_dim 32: what this workspace is sized for): the tile kernels of rgl_tile_pipeline.hip
-        rc = rgl::launch_tiles_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, value, nullptr, fwd_ws,
-                                       fwd_bytes, st);
+        rc = rgl::launch_tiles_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, value, nullptr, w.fwd,
+                                       w.fwd_bytes, st);
     if (rc == 1) {
         if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
         rc = rgl::launch_generic_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, nullptr, value,
                                          nullptr, st);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(gcn_argmax_kernel, grid_for((long long)B * kRootLanes, 256), dim3(256), 0, st, robot, reward, value, B, A, pl.gamma,
-                       pl.time_step, action_values, best_action, best_value);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return launch_onestep_select(robot, reward, value, nullptr, B, A, H, pl.gamma, pl.time_step, action_values, best_action, best_value,
+                                 nullptr, st);
 }

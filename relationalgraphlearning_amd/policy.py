@@ -487,7 +487,9 @@ class GCN(Policy):
             self.build_action_space(state.robot_state.v_pref)
         if not state.human_states:
             assert self.phase != 'train'                       # multi_human_rl.py:27-31
+            self._before_decision(crowd=False)
             return self.select_greedy_action(state.robot_state)
+        self._before_decision(crowd=True)
         probability = np.random.random()
         if self.phase == 'train' and probability < self.epsilon:
             max_action = self.action_space[np.random.choice(len(self.action_space))]
@@ -495,11 +497,13 @@ class GCN(Policy):
             robot, humans = _state_rows(state)
             r64 = torch.tensor([robot], dtype=torch.float64, device=self.device)
             h64 = torch.tensor([humans], dtype=torch.float64, device=self.device)
+            search = None
             with torch.no_grad():
                 if self.query_env:
                     vals, best = self._search_querying_env(robot, r64)
                 else:
-                    vals, best = self.gcn_search().search(r64.float(), h64.float(), roots64=(r64, h64))
+                    search = self.gcn_search()
+                    vals, best = search.search(r64.float(), h64.float(), roots64=(r64, h64))
                     # keep the visual-debug hook: adjacency of the LAST action's graph, as the sequential loop leaves it
                     self._refresh_adjacency(robot, humans)
             self.action_values = [float(v) for v in vals[0].cpu()]
@@ -507,9 +511,16 @@ class GCN(Policy):
             if idx < 0:
                 raise ValueError('Value network is not well trained. ')
             max_action = self.action_space[idx]
+            self._after_decision(search)
         if self.phase == 'train':
             self.last_state = self.transform(state)
         return max_action
+
+    def _before_decision(self, crowd):
+        """Hook of `predict`: an empty crowd (crowd=False, before the greedy action) or a crowd about to be searched."""
+
+    def _after_decision(self, search):
+        """Hook of `predict`: a searched action was chosen; `search` made the search (None: the simulator was queried)."""
 
     def predict_batch(self, robot, humans, roots_are_joint_states=True):
         """Additive API: robot (B,9), humans (B,H,5) device tensors -> (action index (B,), its value (B,))."""
@@ -660,50 +671,25 @@ class SARL(GCN):
             self._search = (key, SarlSearch(self.model, act.as_array(self.action_space), self.kinematics, self.time_step, self.gamma))
         return self._search[1]
 
-    def predict(self, state):
-        _check_ready(self)
-        if self.reach_destination(state):
-            return act.stop_action(self.kinematics)
-        if self.action_space is None:
-            self.build_action_space(state.robot_state.v_pref)
-        if not state.human_states:
-            assert self.phase != 'train'                       # multi_human_rl.py:27-31
+    def _before_decision(self, crowd):
+        if not crowd:
             self.attention_weights = list()
-            return self.select_greedy_action(state.robot_state)
-        if self.query_env:
+        elif self.query_env:
             raise NotImplementedError("SARL with query_env=True is not provided: the maps and rewards of the search come from the "
                                       "constant-velocity guess only")
-        probability = np.random.random()
-        if self.phase == 'train' and probability < self.epsilon:
-            max_action = self.action_space[np.random.choice(len(self.action_space))]
-        else:
-            robot, humans = _state_rows(state)
-            r64 = torch.tensor([robot], dtype=torch.float64, device=self.device)
-            h64 = torch.tensor([humans], dtype=torch.float64, device=self.device)
-            with torch.no_grad():
-                search = self.gcn_search()
-                vals, best = search.search(r64.float(), h64.float(), roots64=(r64, h64))
-            self.action_values = [float(v) for v in vals[0].cpu()]
-            idx = int(best[0])
-            if idx < 0:
-                raise ValueError('Value network is not well trained. ')
-            max_action = self.action_space[idx]
-            self.attention_weights = search.last_attention[0].cpu().numpy()     # of the selected action (multi_human_rl.py:60-64)
-        if self.phase == 'train':
-            self.last_state = self.transform(state)
-        return max_action
+
+    def _after_decision(self, search):
+        self.attention_weights = search.last_attention[0].cpu().numpy()     # of the selected action (multi_human_rl.py:60-64)
+
+    def _refresh_adjacency(self, robot, humans):
+        pass                                                                # no graph, no adjacency: get_matrix_A refuses
 
     def predict_batch(self, robot, humans, roots_are_joint_states=True):
         """Additive API: robot (B,9), humans (B,H,5) device tensors -> (action index (B,), its value (B,)); the attention weights of
         the selected actions stay on the search as last_attention (B,H)."""
         if self.query_env:
             raise NotImplementedError("SARL with query_env=True is not provided")
-        if self.action_space is None:
-            self.build_action_space(float(robot[0, 7]))
-        with torch.no_grad():
-            search = self.gcn_search()
-            vals, best = search.search(robot, humans)
-        return best, search.last_best_value
+        return super().predict_batch(robot, humans, roots_are_joint_states)
 
     def build_occupancy_maps(self, human_states):
         """(H, cell_num^2 om_channel_size) float32 device tensor: multi_human_rl.py:117-171 for a list of human states."""
@@ -722,7 +708,7 @@ class SARL(GCN):
 
 def _first_strict_maximum(vals):
     """Index of the FIRST maximum of every row, -1 when no value beats -inf (all NaN / -inf): the strict `>` walk of
-    multi_human_rl.py:38-64 that leaves max_action None ("Value network is not well trained"), as gcn_argmax_kernel and
+    multi_human_rl.py:38-64 that leaves max_action None ("Value network is not well trained"), as onestep_select_kernel and
     mprl_root_kernel do it.  torch.argmax guarantees neither the first index on ties nor a refusal of NaN rows."""
     clean = torch.where(torch.isnan(vals), torch.full_like(vals, float("-inf")), vals)
     m = clean.max(dim=1, keepdim=True).values

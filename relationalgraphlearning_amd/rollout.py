@@ -451,64 +451,11 @@ class TreeSearch:
         return traj
 
 
-class GcnSearch:
-    """One-step lookahead over the rotation-major action table with the path-G ValueNetwork."""
+class _OneStepSearch:
+    """What the one-step searches share (multi_human_rl.py:36-64: prepare, value network, select): the action table per device, the
+    float64 roots and the outputs.  A subclass fills its planner's network, asks for its workspace and makes its call."""
 
-    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
-        if contraction_dtype not in ("f32", "bf16x6"):
-            raise ValueError("path G contraction mode %r: 'f32' (the reference's arithmetic) or 'bf16x6'" % (contraction_dtype,))
-        self.contraction_dtype = contraction_dtype     # "bf16x6": the graph's weight products as six bf16 MFMA terms (GcnPlanner, ABI 8)
-        self.model = value_network
-        self.actions_np = np.ascontiguousarray(np.asarray(actions, dtype=np.float64))
-        self.kinematics = kinematics
-        self.time_step = float(time_step)
-        self.gamma = float(gamma)
-        self._dev_tables = {}
-        self._ws = _Workspace()
-
-    def search(self, robot, humans, roots64=None):
-        """robot (B,9), humans (B,H,5) -> (action_values (B,A) fp32, best_action (B,) int32), device tensors.
-        `roots64`: the float64 (robot, humans) the fp32 arrays were rounded from (propagate / compute_reward read them)."""
-        robot = _require_device_tensor(robot, "robot states")
-        humans = _require_device_tensor(humans, "human states")
-        B, H, A = robot.shape[0], humans.shape[1], self.actions_np.shape[0]
-        dev = robot.device
-        key = str(dev)
-        if key not in self._dev_tables:
-            self._dev_tables[key] = torch.tensor(self.actions_np, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            pl = nat.GcnPlanner()
-            with batched_transposes():
-                pl.graph = self.model.descriptor()
-                pl.value_head = self.model.head_descriptor()
-            pl.kinematics = nat.KINEMATICS[self.kinematics]
-            pl.num_actions = A
-            pl.time_step = self.time_step
-            pl.gamma = self.gamma
-            pl.contraction_dtype = nat.CONTRACTION_DTYPES[self.contraction_dtype]
-            pl.actions = self._dev_tables[key].data_ptr()
-            if roots64 is not None:
-                r64, h64 = _check_roots64(roots64, B, H)
-                pl.root_robot_f64, pl.root_humans_f64 = r64.data_ptr(), h64.data_ptr()
-            lib = nat.lib()
-            ws = self._ws.get(lib.gcn_predict_workspace_bytes(B, H, A), dev)
-            vals = torch.empty(B, A, dtype=torch.float32, device=dev)
-            best = torch.empty(B, dtype=torch.int32, device=dev)
-            best_value = torch.empty(B, dtype=torch.float32, device=dev)
-            rc = lib.gcn_predict_f32(C.byref(pl), robot.data_ptr(), humans.data_ptr(), B, H, ws.data_ptr(), ws.numel(),
-                                     vals.data_ptr(), best.data_ptr(), best_value.data_ptr(), _stream())
-        nat.check(rc, "gcn_predict_f32")
-        self.last_best_value = best_value        # value of the chosen action per root, from the argmax kernel itself (no gather launches)
-        return vals, best
-
-
-class SarlSearch:
-    """One-step lookahead over the rotation-major action table with the SARL / OM-SARL attention network (sarl_predict_f32:
-    multi_human_rl.py:36-64 with sarl.py:28-73 and, for OM-SARL, the occupancy maps of :117-171)."""
-
-    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
-        if contraction_dtype != "f32":
-            raise ValueError("SARL contraction mode %r: only 'f32' (the reference's arithmetic) is offered" % (contraction_dtype,))
+    def __init__(self, value_network, actions, kinematics, time_step, gamma):
         self.model = value_network
         self.actions_np = np.ascontiguousarray(np.asarray(actions, dtype=np.float64))
         self.kinematics = kinematics
@@ -517,13 +464,12 @@ class SarlSearch:
         self._dev_tables = {}
         self._ws = _Workspace()
         self.last_best_value = None
-        self.last_attention = None
 
-    def planner(self, dev, H, roots64=None, B=None):
+    def _fill_search(self, pl, dev, B, H, roots64):
+        """The fields GcnPlanner and SarlPlanner share: kinematics, action table, time step, gamma, float64 roots."""
         key = str(dev)
         if key not in self._dev_tables:
             self._dev_tables[key] = torch.tensor(self.actions_np, dtype=torch.float64, device=dev)
-        pl = self.model.fill_planner(nat.SarlPlanner())
         pl.kinematics = nat.KINEMATICS[self.kinematics]
         pl.num_actions = self.actions_np.shape[0]
         pl.time_step = self.time_step
@@ -534,6 +480,57 @@ class SarlSearch:
             pl.root_robot_f64, pl.root_humans_f64 = r64.data_ptr(), h64.data_ptr()
         return pl
 
+    def _outputs(self, B, dev):
+        """(action_values (B,A) fp32, best_action (B,) int32, best_value (B,) fp32), for the select step to fill."""
+        return (torch.empty(B, self.actions_np.shape[0], dtype=torch.float32, device=dev),
+                torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float32, device=dev))
+
+
+class GcnSearch(_OneStepSearch):
+    """One-step lookahead over the rotation-major action table with the path-G ValueNetwork."""
+
+    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
+        if contraction_dtype not in ("f32", "bf16x6"):
+            raise ValueError("path G contraction mode %r: 'f32' (the reference's arithmetic) or 'bf16x6'" % (contraction_dtype,))
+        self.contraction_dtype = contraction_dtype     # "bf16x6": the graph's weight products as six bf16 MFMA terms (GcnPlanner, ABI 8)
+        super().__init__(value_network, actions, kinematics, time_step, gamma)
+
+    def search(self, robot, humans, roots64=None):
+        """robot (B,9), humans (B,H,5) -> (action_values (B,A) fp32, best_action (B,) int32), device tensors.
+        `roots64`: the float64 (robot, humans) the fp32 arrays were rounded from (propagate / compute_reward read them)."""
+        robot = _require_device_tensor(robot, "robot states")
+        humans = _require_device_tensor(humans, "human states")
+        B, H, dev = robot.shape[0], humans.shape[1], robot.device
+        with torch.cuda.device(dev):
+            pl = nat.GcnPlanner()
+            with batched_transposes():
+                pl.graph = self.model.descriptor()
+                pl.value_head = self.model.head_descriptor()
+            pl.contraction_dtype = nat.CONTRACTION_DTYPES[self.contraction_dtype]
+            self._fill_search(pl, dev, B, H, roots64)
+            lib = nat.lib()
+            ws = self._ws.get(lib.gcn_predict_workspace_bytes(B, H, pl.num_actions), dev)
+            vals, best, best_value = self._outputs(B, dev)
+            rc = lib.gcn_predict_f32(C.byref(pl), robot.data_ptr(), humans.data_ptr(), B, H, ws.data_ptr(), ws.numel(),
+                                     vals.data_ptr(), best.data_ptr(), best_value.data_ptr(), _stream())
+        nat.check(rc, "gcn_predict_f32")
+        self.last_best_value = best_value        # value of the chosen action per root, from the select kernel itself (no gather launches)
+        return vals, best
+
+
+class SarlSearch(_OneStepSearch):
+    """One-step lookahead over the rotation-major action table with the SARL / OM-SARL attention network (sarl_predict_f32:
+    multi_human_rl.py:36-64 with sarl.py:28-73 and, for OM-SARL, the occupancy maps of :117-171)."""
+
+    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
+        if contraction_dtype != "f32":
+            raise ValueError("SARL contraction mode %r: only 'f32' (the reference's arithmetic) is offered" % (contraction_dtype,))
+        super().__init__(value_network, actions, kinematics, time_step, gamma)
+        self.last_attention = None
+
+    def planner(self, dev, H, roots64=None, B=None):
+        return self._fill_search(self.model.fill_planner(nat.SarlPlanner()), dev, B, H, roots64)
+
     def search(self, robot, humans, roots64=None):
         """robot (B,9), humans (B,H,5) -> (action_values (B,A) fp32, best_action (B,) int32), device tensors; the selected action's
         value and attention weights are kept as last_best_value (B,) / last_attention (B,H)."""
@@ -542,8 +539,7 @@ class SarlSearch:
             raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
         robot = _require_device_tensor(robot, "robot states")
         humans = _require_device_tensor(humans, "human states")
-        B, H, A = robot.shape[0], humans.shape[1], self.actions_np.shape[0]
-        dev = robot.device
+        B, H, dev = robot.shape[0], humans.shape[1], robot.device
         with torch.cuda.device(dev):
             pl = self.planner(dev, H, roots64, B)
             lib = nat.lib()
@@ -552,9 +548,7 @@ class SarlSearch:
                 nat.check(-1, "sarl_predict_f32 (H = %d of at most %d; the widths and map sizes of the shipped shapes)"
                           % (H, nat.SARL_MAX_HUMANS))
             ws = self._ws.get(need, dev)
-            vals = torch.empty(B, A, dtype=torch.float32, device=dev)
-            best = torch.empty(B, dtype=torch.int32, device=dev)
-            best_value = torch.empty(B, dtype=torch.float32, device=dev)
+            vals, best, best_value = self._outputs(B, dev)
             att = torch.empty(B, H, dtype=torch.float32, device=dev)
             rc = lib.sarl_predict_f32(C.byref(pl), robot.data_ptr(), humans.data_ptr(), B, H, ws.data_ptr(), ws.numel(),
                                       vals.data_ptr(), best.data_ptr(), best_value.data_ptr(), att.data_ptr(), _stream())

@@ -1,4 +1,4 @@
-"""Host replay of path G's steps (csrc/rgl_tree.hip: rotate_row, gcn_prepare_kernel, gcn_argmax_kernel) in numpy: every float32
+"""Host replay of path G's steps (csrc/rgl_rotate.h: rotate_row; csrc/rgl_onestep.h: gcn_prepare_kernel, onestep_select_kernel) in numpy: every float32
 operation an individually rounded float32 operation, every float64 operation a plain numpy float64 operation.
 
 This module is the DEFINITION of those steps for the tests.  It is written from the reference's arithmetic

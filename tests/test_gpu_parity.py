@@ -2159,7 +2159,7 @@ def test_path_g_bf16x6_weight_products_at_size(dev):
 def test_path_g_at_size_against_the_batched_oracle(H, B, kin, dev):
     """path G beyond the five fixture scenes -- B x 81 rotated scenes at H = 5 / 19 (and a dense H = 49 crowd)
     through gcn_predict_f32 (gcn_prepare_kernel, row_mlp2_pair_kernel<6,7>, scene_graph_kernel, robot_head_kernel<150,100,100>,
-    gcn_argmax_kernel) against the batched restatement of the reference's loop, which tests/test_oracle_golden.py pins on fixture F7.
+    onestep_select_kernel) against the batched restatement of the reference's loop, which tests/test_oracle_golden.py pins on fixture F7.
     test_scene_kernel_split_and_unsplit_forced re-runs this test with the scene kernel forced into each of its organisations."""
     import bench
     robot, humans = bench.synth_scenes(2000 + H, B, H)

@@ -322,3 +322,159 @@ def test_planner_speed_bound_and_path_g_contraction_modes():
         assert GcnSearch(None, arr, contraction_dtype=mode).contraction_dtype == mode
     with pytest.raises(ValueError):
         GcnSearch(None, arr, contraction_dtype="f16")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# workspace sizes: recorded from the build before the one-step searches shared their carve (csrc/rgl_onestep.h).  Every size
+# function is its entry point's carve over a null base, so a buffer dropped, added or reordered by a rewrite shows here.
+# ---------------------------------------------------------------------------------------------------------------------------
+SIZE_CASES = [(1, 1), (1, 2), (17, 5), (2048, 19), (3, 21), (2, 127)]        # (B, H); A = 81
+GCN_PREDICT_BYTES = {
+    (1, 1): 112384,
+    (1, 2): 125184,
+    (17, 5): 1713152,
+    (2048, 19): 560766976,
+    (3, 21): 963072,
+    (2, 127): 3343104,
+}
+SARL_BYTES = {      # (input_dim, with_global_state, RGL_SARL_PARK, B, H): (predict, value, value_for B * 81 scenes, train B scenes)
+    (13, False, None, 1, 1): (459008, 452864, 452864, 465152),
+    (13, False, None, 1, 2): (461568, 452864, 452864, 471808),
+    (13, False, None, 17, 5): (718336, 452864, 452864, 987904),
+    (13, False, None, 2048, 19): (106621440, 452864, 452864, 225634560),
+    (13, False, None, 3, 21): (3119104, 452864, 2947328, 975360),
+    (13, False, None, 2, 127): (11488768, 452864, 10824192, 2830848),
+    (13, False, 'global', 1, 1): (503552, 452864, 497408, 472576),
+    (13, False, 'global', 1, 2): (550656, 452864, 541952, 486656),
+    (13, False, 'global', 17, 5): (3947776, 452864, 3682304, 1062144),
+    (13, False, 'global', 2048, 19): (178842112, 452864, 72673536, 243689728),
+    (13, False, 'global', 3, 21): (3119104, 452864, 2947328, 975360),
+    (13, False, 'global', 2, 127): (11488768, 452864, 10824192, 2830848),
+    (13, True, None, 1, 1): (509184, 503040, 503040, 516352),
+    (13, True, None, 1, 2): (511744, 503040, 503040, 523520),
+    (13, True, None, 17, 5): (768512, 503040, 503040, 1106176),
+    (13, True, None, 2048, 19): (106671616, 503040, 503040, 256814336),
+    (13, True, None, 3, 21): (3169280, 503040, 2997504, 1075712),
+    (13, True, None, 2, 127): (11538944, 503040, 10874368, 3084288),
+    (13, True, 'global', 1, 1): (553728, 503040, 547584, 523776),
+    (13, True, 'global', 1, 2): (600832, 503040, 592128, 538368),
+    (13, True, 'global', 17, 5): (3997952, 503040, 3732480, 1180416),
+    (13, True, 'global', 2048, 19): (178892288, 503040, 72723712, 274869504),
+    (13, True, 'global', 3, 21): (3169280, 503040, 2997504, 1075712),
+    (13, True, 'global', 2, 127): (11538944, 503040, 10874368, 3084288),
+    (61, False, None, 1, 2): (492544, 483584, 483584, 502528),
+    (61, False, None, 17, 5): (765184, 483584, 483584, 1018624),
+    (61, False, None, 2048, 19): (114123264, 483584, 483584, 225665280),
+    (61, False, None, 3, 21): (3161856, 483584, 2978048, 1006080),
+    (61, False, None, 2, 127): (11568128, 483584, 10854912, 2861568),
+    (61, False, 'global', 1, 2): (581632, 483584, 572672, 517376),
+    (61, False, 'global', 17, 5): (3994624, 483584, 3713024, 1092864),
+    (61, False, 'global', 2048, 19): (186343936, 483584, 72704256, 243720448),
+    (61, False, 'global', 3, 21): (3161856, 483584, 2978048, 1006080),
+    (61, False, 'global', 2, 127): (11568128, 483584, 10854912, 2861568),
+    (61, True, None, 1, 2): (542720, 533760, 533760, 554240),
+    (61, True, None, 17, 5): (815360, 533760, 533760, 1136896),
+    (61, True, None, 2048, 19): (114173440, 533760, 533760, 256845056),
+    (61, True, None, 3, 21): (3212032, 533760, 3028224, 1106432),
+    (61, True, None, 2, 127): (11618304, 533760, 10905088, 3115008),
+    (61, True, 'global', 1, 2): (631808, 533760, 622848, 569088),
+    (61, True, 'global', 17, 5): (4044800, 533760, 3763200, 1211136),
+    (61, True, 'global', 2048, 19): (186394112, 533760, 72754432, 274900224),
+    (61, True, 'global', 3, 21): (3212032, 533760, 3028224, 1106432),
+    (61, True, 'global', 2, 127): (11618304, 533760, 10905088, 3115008),
+}
+REPLAY_BYTES = {
+    (1, 1): 768,
+    (6, 300): 9984,
+    (17, 5): 1024,
+    (40, 2048): 344320,
+    (200, 257): 208384,
+}
+TREE_BYTES = {      # (planning_depth, B, H): bytes; width 2, 81 actions, clipped, empty descriptors
+    (1, 1, 1): 248064,
+    (1, 1, 2): 248320,
+    (1, 17, 5): 735232,
+    (1, 2048, 19): 78247936,
+    (1, 3, 21): 257536,
+    (1, 2, 127): 109568,
+    (2, 1, 1): 257792,
+    (2, 1, 2): 257792,
+    (2, 17, 5): 1414144,
+    (2, 2048, 19): 164640768,
+    (2, 3, 21): 366080,
+    (2, 2, 127): 231936,
+    (3, 1, 1): 279040,
+    (3, 1, 2): 279552,
+    (3, 17, 5): 2770176,
+    (3, 2048, 19): 337426432,
+    (3, 3, 21): 622592,
+    (3, 2, 127): 475136,
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones(monkeypatch):
+    from tests.test_sarl_dense_cpu import planner as sarl_planner
+    monkeypatch.delenv("RGL_SARL_GRID_CAP", raising=False)
+    monkeypatch.delenv("RGL_SARL_PARK", raising=False)
+    lib = nat.lib()
+    assert {k: lib.gcn_predict_workspace_bytes(k[0], k[1], 81) for k in SIZE_CASES} == GCN_PREDICT_BYTES
+    seen = set()
+    for (D, gs, park, B, H), want in SARL_BYTES.items():
+        if park:
+            monkeypatch.setenv("RGL_SARL_PARK", park)
+        else:
+            monkeypatch.delenv("RGL_SARL_PARK", raising=False)
+        pl = sarl_planner(D, gs)
+        ref = ctypes.byref(pl)
+        got = (lib.sarl_predict_workspace_bytes(ref, B, H), lib.sarl_value_workspace_bytes(ref),
+               lib.sarl_value_workspace_bytes_for(ref, B * 81, H), lib.sarl_train_workspace_bytes(ref, B, H))
+        assert got == want, (D, gs, park, B, H, got, want)
+        seen.add((D, gs, park, (B, H)))
+    monkeypatch.delenv("RGL_SARL_PARK", raising=False)
+    assert seen == {(D, gs, park, c) for D in (13, 61) for gs in (False, True) for park in (None, "global") for c in SIZE_CASES
+                    if D == 13 or c[1] >= 2}                                # maps of a single human: no such search
+    assert {k: lib.rgl_replay_push_workspace_bytes(*k) for k in REPLAY_BYTES} == REPLAY_BYTES
+    for (depth, B, H), want in TREE_BYTES.items():
+        pl = nat.MprlPlanner()
+        pl.planning_depth, pl.planning_width, pl.num_actions, pl.do_action_clip = depth, 2, 81, 1
+        assert lib.mprl_tree_workspace_bytes(ctypes.byref(pl), B, H) == want, (depth, B, H)
+    assert {(B, H) for _, B, H in TREE_BYTES} == set(SIZE_CASES)
+
+
+def test_predict_entry_points_refuse_one_byte_less():
+    """gcn_predict_f32 and sarl_predict_f32 with a workspace of their size query less one byte: RGL_ERR_WORKSPACE, the last check
+    before the first launch, so every other argument is in order (pointers set and never read).  With the full size the check is
+    passed -- the call goes on to its launches, which this test only lets happen where there is no device to run them
+    (tests/test_path_g_steps.py and tests/test_sarl_dense_gpu.py make the same two calls on real buffers)."""
+    from tests.test_sarl_dense_cpu import planner as sarl_planner
+    lib = nat.lib()
+    p = ctypes.c_void_p(4096)
+    keep = ctypes.create_string_buffer(16)
+    addr = ctypes.addressof(keep)
+    WORKSPACE = -4
+
+    def mlp(dims):
+        m = nat.RglMlp()
+        m.n_layers = len(dims) - 1
+        for l, d in enumerate(dims):
+            m.dims[l] = d
+        for l in range(len(dims) - 1):
+            m.weight[l], m.bias[l] = addr, addr
+        return m
+
+    g = nat.GcnPlanner()
+    g.num_actions, g.kinematics, g.time_step, g.gamma, g.actions = 81, 0, 0.25, 0.9, p
+    g.graph.x_dim, g.graph.num_layer, g.graph.similarity = 32, 0, nat.SIMILARITY["gaussian"]
+    g.graph.w_r, g.graph.w_h, g.value_head = mlp([6, 64, 32]), mlp([7, 64, 32]), mlp([32, 150, 100, 100, 1])
+    s = sarl_planner(61, True)
+    s.kinematics, s.time_step, s.gamma, s.actions = 0, 0.25, 0.9, p
+    no_device = not torch.cuda.is_available()
+    for B, H in SIZE_CASES[1:]:
+        calls = ((lib.gcn_predict_workspace_bytes(B, H, 81),
+                  lambda n: lib.gcn_predict_f32(ctypes.byref(g), p, p, B, H, p, n, p, p, p, None)),
+                 (lib.sarl_predict_workspace_bytes(ctypes.byref(s), B, H),
+                  lambda n: lib.sarl_predict_f32(ctypes.byref(s), p, p, B, H, p, n, p, p, p, p, None)))
+        for need, call in calls:
+            assert need > 0 and call(need - 1) == WORKSPACE and call(0) == WORKSPACE
+            if no_device:
+                assert call(need) not in (WORKSPACE, 0, -1, -2, -3)          # past every check: the first launch finds no device

@@ -1,5 +1,7 @@
-"""Path G's prepare, rotate and argmax steps (csrc/rgl_tree.hip: rotate_row, gcn_prepare_kernel, gcn_argmax_kernel) against the host
-replay (tests/path_g_steps.py), BIT FOR BIT wherever no libm is involved.
+"""Path G's prepare, rotate and select steps (csrc/rgl_rotate.h: rotate_row; csrc/rgl_onestep.h: gcn_prepare_kernel,
+onestep_select_kernel) against the host replay (tests/path_g_steps.py), BIT FOR BIT wherever no libm is involved.  The select step
+is the one SARL's search runs too: the decision tests run it behind both networks, and with SARL also hold the attention row it
+gathers.
 
 The device's atan2f / cosf / sinf are not the host's, so the tests read the device's own trig back through probe rows -- a row with
 velocity (1, 0) returns c and -sn exactly, a unicycle row with theta = 0 returns -rot -- hand it to the replay, and demand bits for
@@ -16,11 +18,12 @@ import torch
 import relationalgraphlearning_amd as rga
 from oracle import rgl_oracle as orc
 from relationalgraphlearning_amd import _native as nat
-from relationalgraphlearning_amd.nets import _stream
-from relationalgraphlearning_amd.rollout import GcnSearch, prepare_scenes
+from relationalgraphlearning_amd.nets import _stream, batched_transposes
+from relationalgraphlearning_amd.rollout import GcnSearch, SarlSearch, prepare_scenes
 from tests import path_g_steps as pg
 from tests.helpers import JS, make_gcn_policy, make_mprl_policy
 from tests.test_gpu_parity import report
+from tests.test_sarl_gpu import make_policy as make_sarl_policy
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -259,19 +262,54 @@ def test_reward_thresholds_of_path_m(dev):
 # ---------------------------------------------------------------------------------------------------------------------------
 # gcn_predict_f32's decision
 # ---------------------------------------------------------------------------------------------------------------------------
-def constant_search(c, table, dev, kinematics="holonomic"):
-    """A one-step search whose ValueNetwork answers c for every scene: last layer's weight zero, bias c."""
-    pol = make_gcn_policy(device=dev)
+NETWORKS = ("gcn", "sarl")
+
+
+def constant_search(c, table, dev, kinematics="holonomic", network="gcn"):
+    """A one-step search whose value network answers c for every scene: last layer's weight zero, bias c.  "sarl": the attention
+    network on 13-wide rows (no maps), whose attention weights stay what the scenes make them."""
+    if network == "sarl":
+        pol = make_sarl_policy(dev, kinematics, 13, True, "plain")
+        last = [m for m in pol.model.mlp3 if isinstance(m, torch.nn.Linear)][-1]
+    else:
+        pol = make_gcn_policy(device=dev)
+        last = pol.model.value_net[-1]
     with torch.no_grad():
-        pol.model.value_net[-1].weight.zero_()
-        pol.model.value_net[-1].bias.fill_(c)
-    return pol, GcnSearch(pol.model, table, kinematics, DT, GAMMA)
+        last.weight.zero_()
+        last.bias.fill_(c)
+    return pol, (SarlSearch if network == "sarl" else GcnSearch)(pol.model, table, kinematics, DT, GAMMA)
+
+
+def scene_attention(search, robot, humans, dev):
+    """(B, A, H) attention weights of sarl_value_f32 on the B x A candidate scenes of prepare_scenes, evaluated on their own."""
+    r, h = torch.tensor(robot).to(dev), torch.tensor(humans).to(dev)
+    self6, hum7, _ = prepare_scenes(r, h, search.actions_np, search.kinematics, DT)
+    S, H = hum7.shape[0], hum7.shape[1]
+    rows = torch.cat([self6[:, None, :].expand(S, H, 6), hum7], dim=2).contiguous()
+    value = torch.empty(S, dtype=torch.float32, device=dev)
+    att = torch.empty(S, H, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        pl = search.planner(dev, H)
+        ws = torch.empty(nat.lib().sarl_value_workspace_bytes_for(C.byref(pl), S, H), dtype=torch.uint8, device=dev)
+        nat.check(nat.lib().sarl_value_f32(C.byref(pl), rows.data_ptr(), None, None, None, S, 1, H, ws.data_ptr(), ws.numel(),
+                                           value.data_ptr(), att.data_ptr(), _stream()), "sarl_value_f32")
+        torch.cuda.synchronize()
+    return att.cpu().numpy().reshape(robot.shape[0], -1, H)
 
 
 def run_search(search, robot, humans, dev):
+    """(action_values, best_action, best_value) of one search.  SARL: last_attention must be, bit for bit, row best_action of the
+    attention the value network returns for the candidate scenes on their own, and all zeros where no action was chosen."""
     vals, best = search.search(torch.tensor(robot).to(dev), torch.tensor(humans).to(dev))
     torch.cuda.synchronize()
-    return vals.cpu().numpy(), best.cpu().numpy(), search.last_best_value.cpu().numpy()
+    best = best.cpu().numpy()
+    if isinstance(search, SarlSearch):
+        att = scene_attention(search, robot, humans, dev)
+        want = np.where(best[:, None] >= 0, att[np.arange(len(best)), np.maximum(best, 0)], F32(0))
+        got = search.last_attention.cpu().numpy()
+        assert same_bits(got, want), ("last_attention", int((pg.bits(got) != pg.bits(want)).sum()))
+        assert (np.abs(want[best >= 0].astype(F64).sum(1) - 1.0) < 1e-5).all()                  # softmax rows, not a cleared buffer
+    return vals.cpu().numpy(), best, search.last_best_value.cpu().numpy()
 
 
 def replay_decision(robot, humans, table, c, disc=None):
@@ -288,45 +326,51 @@ def assert_decision(got, want, tag):
     assert same_bits(got[2], want[2]), (tag, "best_value")
 
 
-@pytest.mark.parametrize("A", [1, 2, 15, 16, 17, 31, 32, 33, 81, 256])
-def test_every_action_slot_can_win(A, dev):
+@pytest.mark.parametrize("A,network", [pytest.param(A, "gcn", id=str(A)) for A in (1, 2, 15, 16, 17, 31, 32, 33, 81, 256)]
+                         + [pytest.param(33, "sarl", id="33-sarl")])
+def test_every_action_slot_can_win(A, network, dev):
     """A scenes in one launch, scene b's goal on the end point of action b of a dyadic table, robot radius 1/64: only action b
     reaches.  best_action is arange(A), best_value float32(1 + disc * c), every action value the replay's, bit for bit; with
     dt * v_pref = 0 (disc = 1) and = 1 (disc = gamma)."""
     table = pg.dyadic_table(A)
     c = 0.375
-    _, search = constant_search(c, table, dev)
+    _, search = constant_search(c, table, dev, network=network)
     for v_pref, disc in ((0.0, 1.0), (4.0, GAMMA)):
         robot, humans = pg.lane_scenes(table, list(range(A)), 5, v_pref)
         want = replay_decision(robot, humans, table, c)
         assert np.array_equal(want[1], np.arange(A)) and (want[2] == F32(1.0 + disc * F64(F32(c)))).all()
         assert ((want[0] == want[0].max(1, keepdims=True)).sum(1) == 1).all()
         assert_decision(run_search(search, robot, humans, dev), want, (A, v_pref))
-    report("path G decision, A = %d: every action wins its scene (16 lanes x %d slots), values bit for bit at disc = 1 and gamma" % (A, -(-A // 16)))
+    report("%s decision, A = %d: every action wins its scene (16 lanes x %d slots), values bit for bit at disc = 1 and gamma"
+           % (network, A, -(-A // 16)))
 
 
-def test_ties_go_to_the_lower_index(dev):
+@pytest.mark.parametrize("network", NETWORKS)
+def test_ties_go_to_the_lower_index(network, dev):
     """Duplicate table rows k1 < k2, both reaching: k2 in a lower lane than k1 (17 / 32), in the same lane (3 / 19), neighbours
     (5 / 6), both in the last slots (64 / 80); a scene where nothing reaches answers action 0."""
     dup = [(17, 32), (3, 19), (5, 6), (64, 80)]
     table = pg.dyadic_table(81, dup)
     c = -0.125
-    _, search = constant_search(c, table, dev)
+    _, search = constant_search(c, table, dev, network=network)
     targets = [k1 for k1, _ in dup] + [k2 for _, k2 in dup] + [-1]
     robot, humans = pg.lane_scenes(table, targets, 5, 4.0)
     want = replay_decision(robot, humans, table, c)
     assert want[1].tolist() == [17, 3, 5, 64, 17, 3, 5, 64, 0]
     assert ((want[0] == want[0].max(1, keepdims=True)).sum(1)).tolist() == [2] * 8 + [81]
     assert_decision(run_search(search, robot, humans, dev), want, "ties")
-    report("path G decision, exact ties across lanes, within a lane and between neighbours: the lower index wins; 81 equal values: action 0")
+    report("%s decision, exact ties across lanes, within a lane and between neighbours: the lower index wins; 81 equal values: action 0"
+           % network)
 
 
-@pytest.mark.parametrize("c,action", [(float("nan"), -1), (float("inf"), 0), (float("-inf"), -1)], ids=["nan", "inf", "-inf"])
-def test_non_finite_values(c, action, dev):
-    """V = NaN: no action beats -inf -> -1, best_value 0, NaN action values; GCN.predict raises as upstream does, predict_batch
-    returns -1.  V = +inf: action 0.  V = -inf: -1."""
+@pytest.mark.parametrize("c,action,network", [pytest.param(c, action, network, id=("" if network == "gcn" else "sarl-") + name)
+                                              for network in NETWORKS
+                                              for name, c, action in (("nan", float("nan"), -1), ("inf", float("inf"), 0), ("-inf", float("-inf"), -1))])
+def test_non_finite_values(c, action, network, dev):
+    """V = NaN: no action beats -inf -> -1, best_value 0, NaN action values; GCN.predict (SARL inherits it) raises as upstream
+    does, predict_batch returns -1.  V = +inf: action 0.  V = -inf: -1.  SARL: the attention row of a root without an action is zeros."""
     table = holonomic_table()
-    pol, search = constant_search(c, table, dev)
+    pol, search = constant_search(c, table, dev, network=network)
     robot, humans, _ = pg.probe_scenes(np.random.RandomState(47), 17, 5)
     want = replay_decision(robot, humans, table, c)
     assert (want[1] == action).all() and (action >= 0 or (want[2] == 0).all())
@@ -343,6 +387,39 @@ def test_non_finite_values(c, action, dev):
             pol.predict(JS(robot[b], humans[b]))
     else:
         assert pol.predict(JS(robot[b], humans[b])) == pol.action_space[0]
+
+
+@pytest.mark.parametrize("network", NETWORKS)
+def test_predict_runs_in_exactly_its_workspace(network, dev):
+    """gcn_predict_f32 / sarl_predict_f32 on a buffer of exactly their size query: the decision of the search object (which hands
+    over a buffer of its own), bit for bit; one byte less: RGL_ERR_WORKSPACE (tests/test_host_cpu.py holds the sizes themselves)."""
+    table = holonomic_table()
+    _, search = constant_search(0.375, table, dev, network=network)
+    robot, humans, _ = pg.probe_scenes(np.random.RandomState(49), 17, 5)
+    want = run_search(search, robot, humans, dev)
+    r, h = torch.tensor(robot).to(dev), torch.tensor(humans).to(dev)
+    B, H, A = 17, 5, table.shape[0]
+    lib = nat.lib()
+    vals, best, best_value = search._outputs(B, dev)
+    att = torch.empty(B, H, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        if network == "sarl":
+            pl = search.planner(dev, H)
+            need = lib.sarl_predict_workspace_bytes(C.byref(pl), B, H)
+            call = lambda ws, n: lib.sarl_predict_f32(C.byref(pl), r.data_ptr(), h.data_ptr(), B, H, ws.data_ptr(), n, vals.data_ptr(),
+                                                      best.data_ptr(), best_value.data_ptr(), att.data_ptr(), _stream())
+        else:
+            pl = search._fill_search(nat.GcnPlanner(), dev, B, H, None)
+            with batched_transposes():
+                pl.graph, pl.value_head = search.model.descriptor(), search.model.head_descriptor()
+            need = lib.gcn_predict_workspace_bytes(B, H, A)
+            call = lambda ws, n: lib.gcn_predict_f32(C.byref(pl), r.data_ptr(), h.data_ptr(), B, H, ws.data_ptr(), n, vals.data_ptr(),
+                                                     best.data_ptr(), best_value.data_ptr(), _stream())
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert call(ws, need - 1) == -4
+        nat.check(call(ws, need), "predict")
+        torch.cuda.synchronize()
+    assert_decision((vals.cpu().numpy(), best.cpu().numpy(), best_value.cpu().numpy()), want, network)
 
 
 @pytest.mark.parametrize("B", [1, 15, 16, 17, 1000])

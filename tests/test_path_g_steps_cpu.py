@@ -220,7 +220,7 @@ def decision_rows():
 
 
 def test_policys_first_strict_maximum_is_decides_rule():
-    """policy._first_strict_maximum (what query_env's search and the documentation of gcn_argmax_kernel promise) against the
+    """policy._first_strict_maximum (what query_env's search and the documentation of onestep_select_kernel promise) against the
     replay's strict `>` walk from -inf: ties, the two zeros, infinities, NaNs, all-NaN and all -inf rows; float32 and float64."""
     rows = decision_rows()
     want, _ = pg.first_strict_maximum(rows)

@@ -406,6 +406,36 @@ typedef struct RglDeepChildrenPlan {
 } RglDeepChildrenPlan;
 int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan);
 
+/* rgl_plan_value_children (ABI 8, additive) -- which kernel family takes a stand-alone mprl_value_children_f32 call for P parents
+ * (crowds of H humans, planner->num_actions children each): the one host function that decides it for the call itself, written
+ * into a plain struct.  HOST ONLY: no device call, no launch; reads the dimensions and modes of `planner` (no pointer of it is
+ * read) and the process's environment switches.  workspace_at_hand: the call has a workspace of
+ * mprl_value_children_workspace_bytes;  image_at_hand: it has a packed value-estimator image (MprlPlanner.children_image).
+ *   family        RGL_CHILDREN_*: REFUSED (the call returns `refusal` and launches nothing), FUSED (one launch, values directly),
+ *                 RANK1 / DEEP / TILE (stage 1, then the stage-2 head -- inside the deep launch where it fuses the head), SCENE
+ *                 (one wave per child, then the head), TILES_FORWARD (the tile pipeline), GENERIC (the general kernel)
+ *   refusal       REFUSED: RGL_ERR_BAD_MODE (an unknown contraction mode, f16 without the deep kernel's three-layer form,
+ *                 RGL_REQUIRE_MFMA_CHILDREN=1 where only the general kernel is left); 0 otherwise
+ *   fused_mode    FUSED: 0 the f32 form, 2 the bf16x6 form;   own_image  FUSED: bf16x6 was asked for, its form does not fit a CU,
+ *                 the f32 form runs on an image the call packs itself
+ *   f16           DEEP: the f16-input contractions
+ *   pair_image    RANK1 / DEEP / TILE and their head copy their weights from the packed image (at hand, staged, not bf16x6: that
+ *                 image is in the fused kernel's layout only); with it and the shipped head the deep launch runs stage 2 itself
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (P or H < 1). */
+#define RGL_CHILDREN_REFUSED 0
+#define RGL_CHILDREN_FUSED 1
+#define RGL_CHILDREN_RANK1 2
+#define RGL_CHILDREN_DEEP 3
+#define RGL_CHILDREN_TILE 4
+#define RGL_CHILDREN_SCENE 5
+#define RGL_CHILDREN_TILES_FORWARD 6
+#define RGL_CHILDREN_GENERIC 7
+typedef struct RglValueChildrenPlan {
+    int family, refusal, fused_mode, own_image, f16, pair_image;
+} RglValueChildrenPlan;
+int rgl_plan_value_children(const MprlPlanner* planner, int P, int H, int workspace_at_hand, int image_at_hand,
+                            RglValueChildrenPlan* plan);
+
 /* rgl_plan_scene_forward (ABI 8, additive) -- the form in which the one-wave-per-scene MFMA forward (scene_graph_kernel<NT, SK, WAVES,
  * CH, SPLIT, EMB, BX> of rgl_scene.hip) takes n_scenes scenes of H humans, scenes_per_crowd sibling scenes per crowd: the state
  * predictor of a tree level (motion_head 1), path G's value rows, the module forwards of rgl_graph_forward_f32 and the children the

@@ -54,14 +54,21 @@ inline int validate_graph(const RglGraph& g, int H) {
     return RGL_OK;
 }
 
-// ---- internal launchers (one translation unit each; a return value of 1 means "outside this kernel's envelope") -------------
+// ---- internal launchers (one translation unit each) ------------------------------------------------------------------------------
+// The result rule, for every launcher below: an `int` is RGL_OK, a negative RGL_ERR_* or a hipError_t -- never "not mine".  Whether a
+// kernel takes a call is a host-only question of its own, asked BEFORE the launcher is called: a `bool ..._covers(..)` (a few integer
+// operations: ask, then call), or -- where the plan is the larger part of the host work (the tile pipeline) -- a `bool* taken` that
+// the launcher sets; it has launched nothing when it says false.  A launcher called although the answer was no returns
+// RGL_ERR_BAD_MODE.
 int validate_forward_call(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                           const float* humans, int n_scenes, int scenes_per_crowd, int H, const float* value_out,
                           const float* humans_next);                                                                // rgl_generic.hip
-// module forwards (values and / or next humans of S scenes) through the one-wave-per-scene MFMA kernel; 0 bytes / 1 = the
-// kernel does not cover the configuration
+// module forwards (values and / or next humans of S scenes) through the one-wave-per-scene MFMA kernel; 0 bytes = the kernel does
+// not cover the configuration.  scene_forward_covers: it does, and this workspace holds its rows
 size_t scene_forward_workspace_bytes(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, int S, int crowds_per,
                                      int H);                                                                        // rgl_scene.hip
+bool scene_forward_covers(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, int S, int crowds_per, int H,
+                          size_t workspace_bytes);      // (0: no workspace)                                        // rgl_scene.hip
 int launch_scene_forward(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                          const float* humans, int S, int crowds_per, int H, float* value_out, float* humans_next, void* workspace,
                          size_t workspace_bytes, hipStream_t stream, const float* value_rows_image = nullptr);      // rgl_scene.hip
@@ -77,9 +84,14 @@ int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_
 int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_out, int f16, const RglMlp* head,
                          int* head_done);                                                                           // rgl_deep.hip
 int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_out);                                // rgl_tile.hip
-// host only, no launch: whether the two kernels asked before the deep one take a call of these sizes (their own plans' answers)
+// their questions (host only, their own plans' answers), asked by route_value_children alone
 bool rank1_children_covers(const RglGraph* g, int P, int A, int H);                                                 // rgl_rank1.hip
-bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, int mode);                   // rgl_fused.hip
+bool deep_children_covers(const RglGraph* g, int P, int A, int H, bool f16);                                        // rgl_deep.hip
+bool tile_children_covers(const RglGraph* g, int P, int A, int H);                                                  // rgl_tile.hip
+// the fused kernel's form of `mode` itself (no second form is tried); prologue_scene_floats >= 0: and its level-prologue form, with
+// a scene region of that many LDS floats
+bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, FusedImageMode mode,
+                           int prologue_scene_floats = -1);                                                         // rgl_fused.hip
 // stage 2, rows [M][64] -> value; for the rows of a call's P * A children (launch_head_children) the head kernel's workgroups own
 // whole parents and run the call's tail for them (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
 int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value, hipStream_t stream);   // rgl_head.hip
@@ -88,11 +100,18 @@ int launch_head_children(const RglGraph* g, const RglMlp* head, const ChildrenCa
 // parameter state (c.image = MprlPlanner::children_image), else once per tree search (c.image_ready = 1 on the per-level calls)
 // or by the call itself, at the END of the workspace it is given.
 // kModeBx: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
-int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode);       // rgl_fused.hip
+// own_image: the call packs the image of `mode` itself whatever c.image / c.image_ready offer (ChildrenRoute::own_image)
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode, bool own_image);   // rgl_fused.hip
+// P = the largest launch; asked first: fused_children_covers(.., mode) and a workspace of fused_children_workspace_bytes
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, FusedImageMode mode);   // P = the largest launch; 1 = the fused kernel does not apply   // rgl_fused_image.hip
+                         hipStream_t stream, FusedImageMode mode);                                                  // rgl_fused_image.hip
 size_t fused_children_workspace_bytes(int P, int A, int H);                                                         // rgl_fused.hip
 const float* fused_workspace_image(const void* workspace, size_t workspace_bytes);   // where pack_children_images put the image   // rgl_fused_image.hip
+// The ladder of the kernels above, as ONE host function: what a call of these sizes will do.  Launches nothing, reads no device
+// data.  prologue_scene_floats >= 0: the call carries a LevelPrologue with a scene region of that many LDS floats
+// workspace_bytes: 0 = none
+ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, bool image_at_hand,
+                                   int prologue_scene_floats = -1);                                                 // rgl_fast.hip
 int launch_value_children(const MprlPlanner* pl, ChildrenCall c);                                                  // rgl_fast.hip
 size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);                                        // rgl_fast.hip
 // `level`: the parents and crowds, and their independent next-state / reward work; when the MFMA scene kernel runs, it executes that
@@ -102,11 +121,11 @@ size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);     
 int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, float* humans_next, void* workspace,
                           size_t workspace_bytes, hipStream_t stream, int* children_done, const float* sp_image);   // rgl_scene.hip
 // the level prologue of the fused children kernel (RGL_LEVEL_PROLOGUE) for the parents, crowds and reward work of `children`;
-// 1 = the state predictor is outside the prologue's form
-int level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& children, float* humans_next, const float* sp_image,
-                        LevelPrologue* out);                                                                        // rgl_scene.hip
+// false = the state predictor is outside the prologue's form (host only: nothing is launched either way)
+bool level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& children, float* humans_next, const float* sp_image,
+                         LevelPrologue* out);                                                                       // rgl_scene.hip
 // its form check and LDS layout alone (host only, no array): the scene region's floats, the crowds a chunk's row buffer holds
-int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds);   // rgl_scene.hip
+bool level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds);   // rgl_scene.hip
 int fused_prologue_region_floats();      // LDS floats the prologue's scene region may take in the fused children kernel   // rgl_fused.hip
 // true: launch_value_children takes a LevelPrologue of `scene_floats` LDS floats for these P parents (the bf16x6 fused kernel of
 // 17..20-node crowds with a softmax similarity, and a workspace it can run in)
@@ -117,21 +136,27 @@ size_t scene_image_bytes_for(const RglGraph& g, const RglMlp* motion_head);     
 int pack_scene_image_for(const RglGraph& g, const RglMlp* motion_head, float* image, hipStream_t stream);
 
 int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c);                                           // rgl_scene.hip
+bool scene_children_covers(const MprlPlanner* pl, int H);      // ... given a stage-2 head and a workspace of scene_children_workspace_bytes
 size_t scene_children_workspace_bytes(int P, int A, int H);                                                        // rgl_scene.hip
 
-// the backward pass of large batches as MFMA tile kernels; 1 = outside its envelope / below its batch threshold
+// the backward pass of large batches as MFMA tile kernels; *taken = false (RGL_OK, nothing launched): outside its envelope, below
+// its batch threshold, or the workspace cannot hold its intermediates -- RGL_ERR_BAD_MODE instead with RGL_BACKWARD_MFMA=2 (tests)
 int launch_backward_mfma(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                          const float* humans, int n_scenes, int H, int detach_graph, const float* d_value,
                          const float* d_humans_next, const float* d_H, float* grad_out, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, int only_choice);                                                                     // rgl_tile_pipeline.hip
+                         hipStream_t stream, int only_choice, bool* taken);                                        // rgl_tile_pipeline.hip
 
 // forward of models outside the shipped shapes (other embedding MLPs, x_dim = 64) on the tile kernels of rgl_tile_pipeline.hip instead
-// of the general VALU kernel: embedded_gaussian / gaussian, one adjacency, 1-3 layers, N <= 64.  0 bytes / 1 = not covered.
+// of the general VALU kernel: embedded_gaussian / gaussian, one adjacency, 1-3 layers, N <= 64.  0 bytes = not covered; *taken =
+// false (RGL_OK, nothing launched) = not covered, switched off (RGL_TILES_FORWARD=0) or the workspace is short.  tiles_forward_covers:
+// the same answer without a launch (for heads whose outputs are wanted: null otherwise)
 size_t tiles_forward_workspace_bytes(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, int S, int crowds_per,
                                      int H, int want_H);
 int launch_tiles_forward(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, const float* robot,
                          const float* humans, int S, int crowds_per, int H, float* H_out, float* value_out, float* humans_next,
-                         void* workspace, size_t workspace_bytes, hipStream_t stream);                               // rgl_tile_pipeline.hip
+                         void* workspace, size_t workspace_bytes, hipStream_t stream, bool* taken);                  // rgl_tile_pipeline.hip
+bool tiles_forward_covers(const RglGraph* g, const RglMlp* value_head, const RglMlp* motion_head, int S, int crowds_per, int H,
+                          bool want_H, size_t workspace_bytes);      // (0: no workspace)                            // rgl_tile_pipeline.hip
 
 #ifdef RGL_PHASE_TIMING
 // what a unit's rgl_debug_read_*_phase_cycles export does: its 16 counters (HIP_SYMBOL(g_phase_cycles)) out, zeroed on request

@@ -884,8 +884,7 @@ int launch_deep_t(const DeepPlan& pl, const HeadArgs& ha, hipStream_t st) {
 template <int NT>
 int launch_deep_nt(const DeepPlan& pl, const HeadArgs& ha, bool f16, bool skip, hipStream_t st) {
     const bool soft = pl.a.sim == SIM_SOFTMAX;
-    if (!deep_form_exists(pl, f16)) return 1;
-    if (f16) {
+    if (f16) {      // (softmax only: deep_form_exists, asked by the caller)
         return skip ? launch_deep_t<NT, true, true, true>(pl, ha, st) : launch_deep_t<NT, true, false, true>(pl, ha, st);
     }
     if (soft) return skip ? launch_deep_t<NT, false, true, true>(pl, ha, st) : launch_deep_t<NT, false, false, true>(pl, ha, st);
@@ -902,8 +901,12 @@ extern "C" int rgl_debug_read_deep_phase_cycles(unsigned long long* out16, int r
 
 namespace rgl {
 
-// Returns RGL_OK after launching, a negative / hip error code on failure, or 1 when the request is outside this
-// kernel's envelope (the caller then picks another kernel).
+// host only: does launch_deep_children take the call, in the f16 form if asked so?  (route_value_children)
+bool deep_children_covers(const RglGraph* g, int P, int A, int H, bool f16) {
+    const DeepPlan pl = plan_deep(*g, P, A, H);
+    return pl.ok && deep_form_exists(pl, f16);
+}
+
 // `head` / `head_done` (optional): with the shipped value head and the call's packed image at hand the kernel also runs stage 2 -- and
 // the search's tail steps, c.tail / c.tail_done as in launch_head_children -- over the rows of the parents each workgroup owns; *head_done
 // = 1 then, and c.child_value holds the children's values (RGL_DEEP_FUSE_HEAD=0: never, the caller launches robot_head_kernel as before).
@@ -911,7 +914,7 @@ int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
     const int P = c.P, A = c.A;
     if (head_done) *head_done = 0;
     DeepPlan pl = plan_deep(*g, P, A, c.H);
-    if (!pl.ok) return 1;
+    if (!pl.ok || !deep_form_exists(pl, f16 != 0)) return RGL_ERR_BAD_MODE;      // deep_children_covers was not asked
     pl.a.child_robot = c.child_robot;
     pl.a.humans = c.humans_next;
     pl.a.rows_out = rows_out;
@@ -943,28 +946,20 @@ int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
 
 }  // namespace rgl
 
-// What launch_value_children does for a stand-alone call of P parents with a workspace of value_children_workspace_bytes, up to the
-// point where the deep kernel would be launched: the same order of preference (rgl_fast.hip), the same functions.
+// A stand-alone call of P parents with a workspace of value_children_workspace_bytes: whether its route (route_value_children, the
+// function launch_value_children itself follows) ends at the deep kernel, and then the form plan_deep gives the launch.
 extern "C" int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan) {
     if (!planner || !plan) return RGL_ERR_NULL;
     if (P < 1 || H < 1) return RGL_ERR_BAD_SHAPE;
     *plan = RglDeepChildrenPlan{};
     const RglGraph& g = planner->value_graph;
-    const int A = planner->num_actions;
-    const bool want_f16 = planner->contraction_dtype == RGL_CONTRACT_F16;
-    const bool want_b6 = planner->contraction_dtype == RGL_CONTRACT_BF16X6;
-    if (planner->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return RGL_OK;
-    if (head_variant(planner->value_head) < 0) return RGL_OK;              // no stage-2 kernel: the call is not staged
-    if (!want_f16) {                                                       // the kernels asked before this one
-        if (rgl::fused_children_covers(&g, &planner->value_head, P, A, H, want_b6 ? rgl::kModeBx : rgl::kModeF32)) return RGL_OK;
-        if (rgl::rank1_children_covers(&g, P, A, H)) return RGL_OK;
-    }
-    if (want_f16 && g.num_layer != 3) return RGL_OK;                       // RGL_ERR_BAD_MODE in the call
-    DeepPlan pl = plan_deep(g, P, A, H);
-    if (!pl.ok || !deep_form_exists(pl, want_f16)) return RGL_OK;
+    const rgl::ChildrenRoute r = rgl::route_value_children(planner, P, H, ~(size_t)0, image_at_hand != 0);
+    if (r.family != rgl::kChildrenDeep) return RGL_OK;
+    const bool want_f16 = r.f16;
+    DeepPlan pl = plan_deep(g, P, planner->num_actions, H);
     pl.a.fuse_head = 0;
     pl.a.parents_per_wg = 1;
-    if (deep_fuses_head(&planner->value_head, true, image_at_hand && !want_b6)) {      // (a three-piece bf16 image is not this head's)
+    if (deep_fuses_head(&planner->value_head, true, r.pair_image)) {
         pl.lds_bytes = deep_fused_lds_bytes(pl.lds_bytes);
         pl.a.fuse_head = 1;
         pl.a.parents_per_wg = deep_standalone_parents_per_wg(P, pl.lds_bytes);

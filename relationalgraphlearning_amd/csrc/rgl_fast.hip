@@ -1,5 +1,7 @@
-// rgl_fast.hip -- "value of the sibling children" (mprl_value_children_f32): choice of the stage-1 kernel and the two-stage
-// launch.  The f32-MFMA kernels themselves live in
+// rgl_fast.hip -- "value of the sibling children" (mprl_value_children_f32): which kernel family takes a call, decided ONCE on the
+// host (route_value_children: the ladder fused -> rank-1 -> deep -> tile -> scene -> tile pipeline -> general kernel, each rung the
+// owning unit's own `.._covers` question), and the launch that follows it (launch_value_children: the route plus a switch).  A
+// launcher's int is RGL_OK or an error, never "not mine" (rgl_common.h).  The f32-MFMA kernels themselves live in
 //   rgl_rank1.hip  shared-crowd rank-1 form, L = 2, N <= 32 (the shipped configuration)
 //   rgl_deep.hip   shared-crowd form for L in {2, 3}, N <= 60, optional f16-input MFMA contractions
 //   rgl_tile.hip   every child's graph in full, any depth, N <= 64 (softmax similarities)
@@ -28,65 +30,101 @@ size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H) {
     return H + 1 <= 32 ? ((m + 255) & ~(size_t)255) + fused_children_workspace_bytes(0, pl->num_actions, H) + (fused > m ? fused - m : 0) : m;
 }
 
-// V(child) for the A children of each of P parents; children of one parent share humans_next[p].
-int launch_value_children(const MprlPlanner* pl, ChildrenCall c) {
-    if (c.tail_done) *c.tail_done = 0;
-    const int P = c.P, A = c.A, H = c.H;
-    const int hv = head_variant(pl->value_head);
+// Which kernel takes the value-of-children call of P parents -- the ladder, written once: launch_value_children switches on the
+// answer, rgl_plan_value_children / rgl_plan_deep_children / fused_prologue_fits report it.  Every condition is the owning unit's
+// own question (.._covers: its plan's answer); nothing is launched, no device data is read.
+ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, bool image_at_hand,
+                                   int prologue_scene_floats) {
+    ChildrenRoute r{};
+    auto refuse = [&](int code) { r.family = kChildrenRefused; r.refusal = code; return r; };
+    auto take = [&](ChildrenFamily f) { r.family = f; return r; };
+    const RglGraph* g = &pl->value_graph;
+    const RglMlp* head = &pl->value_head;
+    const int A = pl->num_actions;
     const bool want_f16 = pl->contraction_dtype == RGL_CONTRACT_F16;
     // RGL_CONTRACT_BF16X6 (round 5): f32-WIDTH products (three bf16 pieces per operand, six terms) on the matrix pipe where a kernel
     // offers them -- the first 64 input features of the fused kernel's last head matrix; plain f32 everywhere else
     const bool want_b6 = pl->contraction_dtype == RGL_CONTRACT_BF16X6;
-    if (pl->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return RGL_ERR_BAD_MODE;      // (2, the split-f16 mode of ABI 4..7, is gone)
-    const bool staged = hv >= 0 && c.workspace && c.workspace_bytes >= value_children_workspace_bytes(pl, P, H);
-    // stage 1, in order of preference: rank-1 (L = 2, N <= 32), shared-crowd deep (L in {2,3}, N <= 60), tiles (softmax
-    // similarities, any depth, N <= 64); everything else, or a head without a stage-2 kernel: the general kernel
-    int rc = 1;                                            // 1 = no stage-1 kernel launched yet
-    if (staged && !want_f16) {
-        // one fused kernel over 16-child tiles (L = 2, N <= 32, default head): values come out directly, no stage 2
-        rc = launch_fused_children(&pl->value_graph, &pl->value_head, c, want_b6 ? kModeBx : kModeF32);
-        if (rc != 1) return rc;
-    }
-    if (c.prologue) return RGL_ERR_BAD_MODE;               // the caller skipped the level's other launches: fused_prologue_fits did not hold
+    if (pl->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return refuse(RGL_ERR_BAD_MODE);      // (2, the split-f16 mode of ABI 4..7, is gone)
+    r.staged = head_variant(*head) >= 0 && workspace_bytes >= value_children_workspace_bytes(pl, P, H);
     // packed weight image of the value estimator (the caller's, or this search's at the end of the workspace): the two-stage pair
     // copies its weight images from it instead of building them from the raw matrices (most of a small launch)
-    c.image = (!staged || want_b6) ? nullptr                     // (a three-piece bf16 image is in the fused kernel's layout only)
-              : c.image ? c.image
-              : c.image_ready ? fused_workspace_image(c.workspace, c.workspace_bytes) : nullptr;
-    if (staged) {
-        const RglGraph* g = &pl->value_graph;
-        float* rows = (float*)c.workspace;
-        if (!want_f16) rc = launch_rank1_children(g, c, rows);
-        if (rc == 1) {
-            int head_done = 0;
-            rc = launch_deep_children(g, c, rows, want_f16 && g->num_layer == 3, &pl->value_head, &head_done);
-            if (want_f16 && (rc == 1 || g->num_layer != 3)) return RGL_ERR_BAD_MODE;
-            if (rc != 1 && head_done) return rc;           // stage 2 (and the tail) ran inside the launch
-            if (rc == 1 && c.tail_done) *c.tail_done = 0;
-        }
-        if (rc == 1) rc = launch_tile_children(g, c, rows);
-        if (rc == 1 && !want_f16) {
-            // every child's graph in full, one wave per child: the remaining similarity functions and layerwise graphs
-            rc = launch_scene_children(pl, c);
-            if (rc != 1) return rc;
+    r.pair_image = r.staged && !want_b6 && image_at_hand;      // (a three-piece bf16 image is in the fused kernel's layout only)
+    const bool prologue = prologue_scene_floats >= 0;
+    if (r.staged && !want_f16) {
+        // one fused kernel over 16-child tiles (L = 2, N <= 32, default head): values come out directly, no stage 2
+        r.fused_mode = want_b6 ? kModeBx : kModeF32;
+        if (fused_children_covers(g, head, P, A, H, r.fused_mode, prologue_scene_floats)) return take(kChildrenFused);
+        // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch), and of 17..20 with a
+        // plain-weight similarity (unpacked row pass: 172 944 bytes), do not fit a CU with it -- they run the f32 form of this kernel on
+        // an f32 image the call packs itself (the caller's image is in the other layout; tests/test_bf16x6_kernels.py pins the envelope)
+        if (want_b6 && !prologue && fused_children_covers(g, head, P, A, H, kModeF32)) {
+            r.fused_mode = kModeF32;
+            r.own_image = true;
+            return take(kChildrenFused);
         }
     }
-    if (want_f16 && rc == 1) return RGL_ERR_BAD_MODE;
-    if (rc == 1) {
-        // outside the shipped shapes (other embedding MLPs, x_dim = 64): the tile kernels, the children of a parent sharing its crowd's rows
-        rc = launch_tiles_forward(&pl->value_graph, &pl->value_head, nullptr, c.child_robot, c.humans_next, P * A, A, H, nullptr,
-                                  c.child_value, nullptr, c.workspace, c.workspace_bytes, c.stream);
-        if (rc != 1) return rc;
+    if (prologue) return refuse(RGL_ERR_BAD_MODE);      // the caller skipped the level's other launches: only the prologue form runs them
+    // stage 1, in order of preference: rank-1 (L = 2, N <= 32), shared-crowd deep (L in {2,3}, N <= 60), tiles (softmax
+    // similarities, any depth, N <= 64); everything else, or a head without a stage-2 kernel: the general kernel
+    if (r.staged) {
+        if (!want_f16 && rank1_children_covers(g, P, A, H)) return take(kChildrenRank1);
+        if (want_f16) {      // the deep kernel's three-layer form or nothing
+            r.f16 = true;
+            return g->num_layer == 3 && deep_children_covers(g, P, A, H, true) ? take(kChildrenDeep) : refuse(RGL_ERR_BAD_MODE);
+        }
+        if (deep_children_covers(g, P, A, H, false)) return take(kChildrenDeep);
+        if (tile_children_covers(g, P, A, H)) return take(kChildrenTile);
+        // every child's graph in full, one wave per child: the remaining similarity functions and layerwise graphs (`staged`: a
+        // stage-2 head, and a workspace that holds scene_children_workspace_bytes)
+        if (scene_children_covers(pl, H)) return take(kChildrenScene);
     }
-    if (rc == 1) {
-        // RGL_REQUIRE_MFMA_CHILDREN=1 (tests): refuse instead of running the general VALU kernel
-        static const bool require = [] { const char* e = getenv("RGL_REQUIRE_MFMA_CHILDREN"); return e && e[0] == '1'; }();
-        if (require) return RGL_ERR_BAD_MODE;
-        return launch_generic_forward(&pl->value_graph, &pl->value_head, nullptr, c.child_robot, c.humans_next, P * A, A, H,
-                                      nullptr, nullptr, c.child_value, nullptr, c.stream);
+    if (want_f16) return refuse(RGL_ERR_BAD_MODE);
+    // outside the shipped shapes (other embedding MLPs, x_dim = 64): the tile kernels, the children of a parent sharing its crowd's rows
+    if (tiles_forward_covers(g, head, nullptr, P * A, A, H, false, workspace_bytes)) return take(kChildrenTilesForward);
+    // RGL_REQUIRE_MFMA_CHILDREN=1 (tests): refuse instead of running the general VALU kernel
+    static const bool require = [] { const char* e = getenv("RGL_REQUIRE_MFMA_CHILDREN"); return e && e[0] == '1'; }();
+    return require ? refuse(RGL_ERR_BAD_MODE) : take(kChildrenGeneric);
+}
+
+// V(child) for the A children of each of P parents; children of one parent share humans_next[p].
+int launch_value_children(const MprlPlanner* pl, ChildrenCall c) {
+    if (c.tail_done) *c.tail_done = 0;      // the launcher that runs the tail sets it
+    const RglGraph* g = &pl->value_graph;
+    const RglMlp* head = &pl->value_head;
+    const ChildrenRoute r = route_value_children(pl, c.P, c.H, c.workspace ? c.workspace_bytes : 0, c.image || c.image_ready,
+                                                 c.prologue ? c.prologue->scene_floats : -1);
+    if (r.family == kChildrenFused) return launch_fused_children(g, head, c, r.fused_mode, r.own_image);
+    c.image = !r.pair_image ? nullptr : c.image ? c.image : fused_workspace_image(c.workspace, c.workspace_bytes);
+    float* rows = (float*)c.workspace;
+    int rc = RGL_OK, head_done = 0;
+    switch (r.family) {
+        case kChildrenRefused: return r.refusal;
+        case kChildrenRank1: rc = launch_rank1_children(g, c, rows); break;
+        case kChildrenDeep: rc = launch_deep_children(g, c, rows, r.f16, head, &head_done); break;      // (may run stage 2 and the tail itself)
+        case kChildrenTile: rc = launch_tile_children(g, c, rows); break;
+        case kChildrenScene: return launch_scene_children(pl, c);
+        case kChildrenTilesForward: {
+            bool taken = false;
+            rc = launch_tiles_forward(g, head, nullptr, c.child_robot, c.humans_next, c.P * c.A, c.A, c.H, nullptr, c.child_value, nullptr,
+                                      c.workspace, c.workspace_bytes, c.stream, &taken);
+            return (rc || taken) ? rc : RGL_ERR_BAD_MODE;
+        }
+        default:
+            return launch_generic_forward(g, head, nullptr, c.child_robot, c.humans_next, c.P * c.A, c.A, c.H, nullptr, nullptr,
+                                          c.child_value, nullptr, c.stream);
     }
-    if (rc) return rc;
-    return launch_head_children(&pl->value_graph, &pl->value_head, c, (const float*)c.workspace);
+    if (rc || head_done) return rc;
+    return launch_head_children(g, head, c, rows);      // stage 2
 }
 
 }  // namespace rgl
+
+extern "C" int rgl_plan_value_children(const MprlPlanner* planner, int P, int H, int workspace_at_hand, int image_at_hand,
+                                       RglValueChildrenPlan* plan) {
+    if (!planner || !plan) return RGL_ERR_NULL;
+    if (P < 1 || H < 1) return RGL_ERR_BAD_SHAPE;
+    const rgl::ChildrenRoute r = rgl::route_value_children(planner, P, H, workspace_at_hand ? ~(size_t)0 : 0, image_at_hand != 0);
+    *plan = RglValueChildrenPlan{r.family, r.refusal, r.fused_mode, r.own_image, r.f16, r.pair_image};
+    return RGL_OK;
+}

@@ -200,8 +200,9 @@ size_t fused_children_workspace_bytes(int P, int A, int H) {
     return ((main_bytes + 255) & ~(size_t)255) + kImageBytes;
 }
 
-// 1 = outside this kernel's envelope
-int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode) {
+// The caller has asked route_value_children: the form of `mode` covers the call (with its prologue, if it carries one), the workspace
+// holds value_children_workspace_bytes, and own_image says whose image the kernel reads.
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode, bool own_image) {
     const int P = c.P, A = c.A, H = c.H;
     if (c.tail_done) *c.tail_done = 0;
     // the search's tail: selection always; the back-up chain + root step at the deepest level when handing whole roots to
@@ -209,21 +210,9 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenC
     const TailArgs* ta = (c.tail && c.tail->enabled && !fused_tail_disabled()) ? c.tail : nullptr;
     int chain = 0;
     const int unit = ta ? tail_ownership(*ta, P, fused_cu_count() / 2, &chain) : 1;
-    FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);
-    if (c.prologue) {
-        if (!prologue_form(fp, c.prologue->scene_floats)) return RGL_ERR_BAD_MODE;      // fused_prologue_fits was not asked
-        fp.pro = c.prologue;
-    }
-    // the bf16 hybrid image is larger: crowds of 21..32 agents (lane = feature row pass, larger wave scratch), and of 17..20 with a
-    // plain-weight similarity (unpacked row pass: 172 944 bytes), do not fit a CU with it -- they run the f32 form of this kernel on
-    // an f32 image packed here (the caller's image is in the other layout; tests/test_bf16x6_kernels.py pins the envelope)
-    bool own_image = false;
-    if (!fp.ok && mode) {
-        fp = plan_fused(*g, *head, P, A, H, unit, kModeF32);
-        own_image = fp.ok;
-    }
-    if (!fp.ok) return 1;
-    if (!c.workspace || c.workspace_bytes < fused_children_workspace_bytes(P, A, H)) return 1;
+    FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);      // (.ok does not depend on `unit`: the route asked with 1)
+    if (!fp.ok) return RGL_ERR_BAD_MODE;
+    fp.pro = c.prologue;
     if (own_image || (!c.image_ready && !c.image)) {
         int rc = launch_pack_image(fp.a, image_of(c.workspace, c.workspace_bytes), fp.mode(), c.stream);
         if (rc) return rc;
@@ -262,15 +251,14 @@ int fused_prologue_region_floats() {
 }
 
 bool fused_prologue_fits(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, int scene_floats) {
-    if (pl->contraction_dtype != RGL_CONTRACT_BF16X6 || head_variant(pl->value_head) < 0) return false;
     if (P < kPrologueMinParentsPerCu * fused_cu_count() - (fused_cu_count() - 1)) return false;     // ceil(P / CUs) < 4
-    if (workspace_bytes < value_children_workspace_bytes(pl, P, H)) return false;         // launch_value_children's `staged`
-    return prologue_form(plan_fused(pl->value_graph, pl->value_head, P, pl->num_actions, H, 1, kModeBx), scene_floats);
+    return scene_floats >= 0 && route_value_children(pl, P, H, workspace_bytes, false, scene_floats).family == kChildrenFused;
 }
 
-// host only: would launch_fused_children take the call?  (rgl_plan_deep_children)
-bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, int mode) {
-    return plan_fused(*g, *head, P, A, H, 1, mode).ok || (mode && plan_fused(*g, *head, P, A, H, 1, kModeF32).ok);      // (its f32 form)
+// host only (route_value_children): does the form of `mode` take the call -- and, with a prologue, is it the prologue's form?
+bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, FusedImageMode mode, int prologue_scene_floats) {
+    const FusedPlan fp = plan_fused(*g, *head, P, A, H, 1, mode);
+    return prologue_scene_floats >= 0 ? prologue_form(fp, prologue_scene_floats) : fp.ok;
 }
 
 }  // namespace rgl
@@ -281,7 +269,7 @@ extern "C" int rgl_plan_prologue_embedding(const MprlPlanner* planner, int P, in
     if (P < 1 || H < 1 || crowds_per < 1 || unit < 1 || P % crowds_per) return RGL_ERR_BAD_SHAPE;
     *plan = RglPrologueEmbeddingPlan{};
     int scene_floats = 0, chunk_crowds = 0;
-    if (!level_prologue_enabled() || rgl::level_prologue_layout(planner, crowds_per, P, H, &scene_floats, &chunk_crowds)) return RGL_OK;
+    if (!level_prologue_enabled() || !rgl::level_prologue_layout(planner, crowds_per, P, H, &scene_floats, &chunk_crowds)) return RGL_OK;
     if (!rgl::fused_prologue_fits(planner, P, H, ~(size_t)0, scene_floats)) return RGL_OK;
     const FusedPlan fp = plan_fused(planner->value_graph, planner->value_head, P, planner->num_actions, H, unit, kModeBx);
     const int k = fp.a.parents_per_wg;

@@ -162,11 +162,11 @@ const float* fused_workspace_image(const void* workspace, size_t workspace_bytes
     return image_of(const_cast<void*>(workspace), workspace_bytes);
 }
 
-// 1 = the fused kernel does not apply (or the workspace cannot hold its images)
+// asked first: fused_children_covers(.., mode) and a workspace of fused_children_workspace_bytes
 int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
                          hipStream_t stream, FusedImageMode mode) {
     FusedPlan fp = plan_fused(*g, *head, P, A, H, 1, mode);
-    if (!fp.ok || !workspace || workspace_bytes < fused_children_workspace_bytes(P, A, H)) return 1;
+    if (!fp.ok || !workspace || workspace_bytes < fused_children_workspace_bytes(P, A, H)) return RGL_ERR_BAD_MODE;
     return launch_pack_image(fp.a, image_of(workspace, workspace_bytes), fp.mode(), stream);
 }
 

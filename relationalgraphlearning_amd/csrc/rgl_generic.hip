@@ -418,17 +418,18 @@ extern "C" int rgl_graph_forward_f32(const RglGraph* graph, const RglMlp* value_
                                             humans_next);
         if (rc) return rc;
         if (n_scenes == 0) return RGL_OK;
+        bool taken = false;
         if (tiles_forward_mode() == 2) {      // RGL_TILES_FORWARD=2 (tests): the tile kernels first, also for the shipped shapes
             rc = rgl::launch_tiles_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, nullptr,
-                                           value_out, humans_next, workspace, workspace_bytes, (hipStream_t)stream);
-            if (rc != 1) return rc;
+                                           value_out, humans_next, workspace, workspace_bytes, (hipStream_t)stream, &taken);
+            if (rc || taken) return rc;
         }
-        rc = rgl::launch_scene_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, value_out,
-                                       humans_next, workspace, workspace_bytes, (hipStream_t)stream);
-        if (rc != 1) return rc;
+        if (rgl::scene_forward_covers(graph, value_head, motion_head, n_scenes, scenes_per_crowd, H, workspace_bytes))
+            return rgl::launch_scene_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, value_out,
+                                             humans_next, workspace, workspace_bytes, (hipStream_t)stream);
         rc = rgl::launch_tiles_forward(graph, value_head, motion_head, robot, humans, n_scenes, scenes_per_crowd, H, nullptr, value_out,
-                                       humans_next, workspace, workspace_bytes, (hipStream_t)stream);
-        if (rc != 1) return rc;
+                                       humans_next, workspace, workspace_bytes, (hipStream_t)stream, &taken);
+        if (rc || taken) return rc;
         // RGL_REQUIRE_MFMA_FORWARD=1 (tests): refuse instead of running the general VALU kernel
         if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
     } else if (!workspace && !H_out && !A_out && require_mfma_forward()) {

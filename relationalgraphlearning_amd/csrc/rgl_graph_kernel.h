@@ -650,10 +650,11 @@ static_assert((size_t)(GraphLds<4, 4>::weight_floats(3) + GraphLds<4, 4>::scene_
               "graph_kernel<4, 4, 3, true, ..>: launch_graph_nxl assumes that no scene of N > 32 fits the LDS of a CU");
 template <int NT, int XT, int L, bool COS, bool LW>
 int launch_graph_nxl(const GraphArgs& ga, bool bwd, size_t lds, int grid, hipStream_t st) {
+    // the two forms that are not compiled are never asked for (tiles_cover, plan_graph): an error if they are
     if constexpr (LW && !(XT == 2 && NT <= 2)) {  // layerwise graphs: the softmax / squared normalisations, up to 32 nodes of 32 features (tiles_cover)
-        return 1;
+        return RGL_ERR_BAD_MODE;
     } else if constexpr (NT == 4 && XT == 4 && L == 3) {
-        return bwd ? 1 : launch_graph_kernel<NT, XT, L, false, COS, LW>(ga, lds, grid, st);
+        return bwd ? RGL_ERR_LDS : launch_graph_kernel<NT, XT, L, false, COS, LW>(ga, lds, grid, st);
     } else {
         return bwd ? launch_graph_kernel<NT, XT, L, true, COS, LW>(ga, lds, grid, st)
                    : launch_graph_kernel<NT, XT, L, false, COS, LW>(ga, lds, grid, st);

@@ -123,12 +123,12 @@ __global__ __launch_bounds__(kAnyWaves * 64) void robot_head_any_kernel(const He
 
 }  // namespace
 
-// rows [M][64] (stage-1 hand-off) -> value;  1 = no kernel for this head (see head_variant)
+// rows [M][64] (stage-1 hand-off) -> value;  the caller has asked head_variant: a head without a stage-2 kernel is not staged
 static int launch_stage2(const RglGraph* g, const RglMlp* h, const float* rows, int M, float* value, hipStream_t stream,
                          const float* image, const TailArgs* tail, int* tail_done, int A) {
     if (tail_done) *tail_done = 0;
     const int hv = head_variant(*h);
-    if (hv < 0) return 1;
+    if (hv < 0) return RGL_ERR_BAD_MODE;
     if (hv == 2) {
         HeadAnyArgs aa;
         aa.w_last = g->Ws[g->num_layer - 1];

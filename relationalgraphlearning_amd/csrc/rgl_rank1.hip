@@ -607,10 +607,9 @@ extern "C" int rgl_debug_read_phase_cycles(unsigned long long* out16, int reset)
 
 namespace rgl {
 
-// 1 = outside this kernel's envelope
 int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_out) {
     Rank1Plan rp = plan_rank1(*g, c.P, c.A, c.H);
-    if (!rp.ok) return 1;
+    if (!rp.ok) return RGL_ERR_BAD_MODE;      // rank1_children_covers was not asked
     rp.a.image = rp.image_layout ? c.image : nullptr;
     rp.a.child_robot = c.child_robot;
     rp.a.humans = c.humans_next;
@@ -618,7 +617,7 @@ int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_
     return launch_rank1(rp, g->skip_connection != 0, c.stream);
 }
 
-// host only: would launch_rank1_children take the call?  (rgl_plan_deep_children)
+// host only: does launch_rank1_children take the call?  (route_value_children)
 bool rank1_children_covers(const RglGraph* g, int P, int A, int H) { return plan_rank1(*g, P, A, H).ok; }
 
 }  // namespace rgl

@@ -259,7 +259,7 @@ int launch_scene_k(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* ch
 inline int launch_scene_wide(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* children, hipStream_t st, ScenePlan* plan = nullptr) {
     if (sa.sim == SIM_SOFTMAX) return launch_scene_k<8, 0, 8, true>(sa, lds_bytes, children, st, plan);
     if (sa.sim == SIM_COSINE || sa.sim == SIM_COSINE_SOFTMAX) return launch_scene_k<8, 2, 8, true>(sa, lds_bytes, children, st, plan);
-    if (sa.sim == SIM_CONCAT) return 1;
+    if (sa.sim == SIM_CONCAT) return RGL_ERR_BAD_MODE;      // (never asked: scene_kernel_covers ends the pair MLP at 64 nodes)
     return launch_scene_k<8, 1, 8, true>(sa, lds_bytes, children, st, plan);
 }
 
@@ -398,12 +398,12 @@ size_t scene_image_bytes(const MprlPlanner* pl) {
 }
 
 int pack_scene_image(const MprlPlanner* pl, float* image, hipStream_t stream) {
-    if (!scene_image_bytes(pl)) return 1;
+    if (!scene_image_bytes(pl)) return RGL_ERR_BAD_MODE;      // the caller asks scene_image_bytes first
     return pack_scene_image_for(pl->predictor_graph, &pl->motion_head, image, stream);
 }
 
 int pack_scene_image_for(const RglGraph& g, const RglMlp* mh, float* image, hipStream_t stream) {
-    if (!scene_image_bytes_for(g, mh)) return 1;
+    if (!scene_image_bytes_for(g, mh)) return RGL_ERR_BAD_MODE;      // the caller asks scene_image_bytes_for first
     SceneImageArgs ia;
     ia.wa = bilinear_wa(g);
     for (int l = 0; l < 4; ++l) ia.Ws[l] = l < g.num_layer ? g.Ws[l] : nullptr;
@@ -417,33 +417,33 @@ int pack_scene_image_for(const RglGraph& g, const RglMlp* mh, float* image, hipS
 }
 
 // The level prologue of the fused children kernel (rgl_fused_kernel.hip): the state predictor's scenes of the parents a workgroup owns in the
-// unsplit BX + EMB form of scene_body (one slot per wave, embeddings inside), and the level's reward / next-state pairs.  1 = outside
+// unsplit BX + EMB form of scene_body (one slot per wave, embeddings inside), and the level's reward / next-state pairs.  false = outside
 // that form's envelope: the six-term bf16 scene kernel with two node tiles (softmax similarity, 9-wide robot state, a motion head).
-int level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& ca, float* humans_next, const float* sp_image, LevelPrologue* lp) {
-    if (!sp_image || level_prologue_layout(pl, ca.humans_per, ca.P, ca.H, nullptr, nullptr)) return 1;
+bool level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& ca, float* humans_next, const float* sp_image, LevelPrologue* lp) {
+    if (!sp_image || !level_prologue_layout(pl, ca.humans_per, ca.P, ca.H, nullptr, nullptr)) return false;
     lp->scene_floats = fill_scene_args(lp->scene, pl->predictor_graph, &pl->motion_head, ca.robot, ca.humans, ca.humans_per, ca.P, ca.H,
                                        humans_next, nullptr, nullptr, nullptr, true, sp_image, 8, fused_prologue_region_floats());
-    if (!lp->scene.bx) return 1;
+    if (!lp->scene.bx) return false;
     lp->children = ca;
-    return 0;
+    return true;
 }
 
 // The form check and the LDS layout of level_prologue_args without any array (host only; the planner export rgl_plan_prologue_embedding
-// asks it too): 0 and the scene region's LDS floats / the crowds a chunk's row buffer holds, 1 = outside the form.
-int level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds) {
-    if (pl->linear_state_predictor || pl->contraction_dtype != RGL_CONTRACT_BF16X6) return 1;
+// asks it too): true and the scene region's LDS floats / the crowds a chunk's row buffer holds, false = outside the form.
+bool level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, int* scene_floats, int* chunk_crowds) {
+    if (pl->linear_state_predictor || pl->contraction_dtype != RGL_CONTRACT_BF16X6) return false;
     const RglGraph& g = pl->predictor_graph;
     const int N = H + 1;
-    if (!scene_kernel_covers(g, N) || !mlp_is(pl->motion_head, XD, HID, 5, false) || g.w_r.dims[0] != 9) return 1;
-    if (scene_similarity_mode(g) != SIM_SOFTMAX || (N + 15) / 16 != 2 || crowds_per < 1 || P % crowds_per != 0) return 1;
+    if (!scene_kernel_covers(g, N) || !mlp_is(pl->motion_head, XD, HID, 5, false) || g.w_r.dims[0] != 9) return false;
+    if (scene_similarity_mode(g) != SIM_SOFTMAX || (N + 15) / 16 != 2 || crowds_per < 1 || P % crowds_per != 0) return false;
     SceneArgs sa;
     static const float image_stand_in = 0.f;      // fill_scene_args only asks whether there is an image
     const int fl = fill_scene_args(sa, g, &pl->motion_head, nullptr, nullptr, crowds_per, P, H, nullptr, nullptr, nullptr, nullptr, true,
                                    &image_stand_in, 8, fused_prologue_region_floats());
-    if (!sa.bx || sa.chunk_crowds < 1) return 1;
+    if (!sa.bx || sa.chunk_crowds < 1) return false;
     if (scene_floats) *scene_floats = fl;
     if (chunk_crowds) *chunk_crowds = sa.chunk_crowds;
-    return 0;
+    return true;
 }
 
 // humans_next[s] = motion_head(RGL(robot[s], humans[s / crowds_per]))[1:]  for P scenes (StatePredictor.forward).
@@ -460,9 +460,10 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
     if (!ok) {
         // outside the shipped shapes: the tile kernels (rgl_tile_pipeline.hip) where they cover the model, else the general kernel
         if (P % crowds_per == 0) {
+            bool taken = false;
             const int rc = launch_tiles_forward(&g, nullptr, &mh, robot, humans, P, crowds_per, H, nullptr, nullptr, humans_next, workspace,
-                                                workspace_bytes, stream);
-            if (rc != 1) return rc;
+                                                workspace_bytes, stream, &taken);
+            if (rc || taken) return rc;
         }
         if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
         return launch_generic_forward(&g, nullptr, &mh, robot, humans, P, crowds_per, H, nullptr, nullptr, nullptr,
@@ -484,7 +485,7 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
 // Module forwards (ValueEstimator.forward / StatePredictor.forward on a batch: value_estimator.py:11-20, state_predictor.py:20-39)
 // through the same kernels: embeddings + one wave per scene; values via the value-rows mode + robot_head_kernel.
 // workspace: x0 [S][32] | xh [S / crowds_per][H][32] | rows [S][64] (value head only).
-static bool scene_forward_covers(const RglGraph& g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H) {
+static bool scene_forward_form(const RglGraph& g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H) {
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
     if (!(has_v || has_m) || crowds_per < 1 || S % crowds_per != 0) return false;
     if (!scene_kernel_covers(g, H + 1)) return false;
@@ -494,16 +495,20 @@ static bool scene_forward_covers(const RglGraph& g, const RglMlp* vh, const RglM
 }
 
 size_t scene_forward_workspace_bytes(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H) {
-    if (!g || !scene_forward_covers(*g, vh, mh, S, crowds_per, H)) return 0;
+    if (!g || !scene_forward_form(*g, vh, mh, S, crowds_per, H)) return 0;
     const bool has_v = vh && vh->n_layers > 0;
     return ((size_t)S * XD + (size_t)(S / crowds_per) * H * XD + (has_v ? (size_t)S * 64 : 0)) * sizeof(float);
+}
+
+bool scene_forward_covers(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H, size_t workspace_bytes) {
+    const size_t need = scene_forward_workspace_bytes(g, vh, mh, S, crowds_per, H);
+    return need && workspace_bytes >= need;
 }
 
 int launch_scene_forward(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, const float* robot, const float* humans, int S,
                          int crowds_per, int H, float* value_out, float* humans_next, void* workspace, size_t workspace_bytes,
                          hipStream_t stream, const float* value_rows_image) {
-    if (!scene_forward_covers(*g, vh, mh, S, crowds_per, H)) return 1;
-    if (!workspace || workspace_bytes < scene_forward_workspace_bytes(g, vh, mh, S, crowds_per, H)) return 1;
+    if (!workspace || !scene_forward_covers(g, vh, mh, S, crowds_per, H, workspace_bytes)) return RGL_ERR_BAD_MODE;
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
     float* x0_rows = (float*)workspace;
     float* xh_rows = x0_rows + (size_t)S * XD;
@@ -524,17 +529,20 @@ int launch_scene_forward(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, 
 // Value of the children through the one-wave-per-scene kernel: every child's graph in full (no crowd sharing), any of the
 // similarity functions it implements, layerwise graphs, 1..4 layers -- the MFMA path of everything the shared-crowd kernels do
 // not cover (cosine / cosine_softmax scale the columns by child-dependent norms; layerwise graphs rebuild the adjacency from
-// every H_l).  workspace: x0 [P*A][32] | xh [P*H][32] | rows [P*A][64].  1 = outside this kernel's envelope.
+// every H_l).  workspace: x0 [P*A][32] | xh [P*H][32] | rows [P*A][64].
 size_t scene_children_workspace_bytes(int P, int A, int H) {
     return ((size_t)P * A * (XD + 64) + (size_t)P * H * XD) * sizeof(float);
 }
 
+bool scene_children_covers(const MprlPlanner* pl, int H) {
+    return scene_kernel_covers(pl->value_graph, H + 1) && head_variant(pl->value_head) >= 0;
+}
+
 int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c) {
     const RglGraph& g = pl->value_graph;
-    const int P = c.P, A = c.A, H = c.H, N = H + 1;
-    if (!scene_kernel_covers(g, N) || head_variant(pl->value_head) < 0 || !c.workspace ||
-        c.workspace_bytes < scene_children_workspace_bytes(P, A, H))
-        return 1;
+    const int P = c.P, A = c.A, H = c.H;
+    if (!scene_children_covers(pl, H) || !c.workspace || c.workspace_bytes < scene_children_workspace_bytes(P, A, H))
+        return RGL_ERR_BAD_MODE;
     float* x0_rows = (float*)c.workspace;                    // [P*A][32]
     float* xh_rows = x0_rows + (size_t)P * A * XD;           // [P][H][32]
     float* rows = xh_rows + (size_t)P * H * XD;              // [P*A][64]

@@ -134,4 +134,28 @@ struct ChildrenCall {
     const LevelPrologue* prologue;   // null, or the level's state predictor and reward / next-state pairs, run first (fused_prologue_fits)
 };
 
+// Which kernel family takes a ChildrenCall: route_value_children's answer (rgl_fast.hip), decided on the host before anything is
+// launched.  The ids are RglValueChildrenPlan::family's (rgl_hip.h).
+enum ChildrenFamily {
+    kChildrenRefused = RGL_CHILDREN_REFUSED,      // no launch: ChildrenRoute::refusal is the call's result
+    kChildrenFused = RGL_CHILDREN_FUSED,
+    kChildrenRank1 = RGL_CHILDREN_RANK1,
+    kChildrenDeep = RGL_CHILDREN_DEEP,
+    kChildrenTile = RGL_CHILDREN_TILE,
+    kChildrenScene = RGL_CHILDREN_SCENE,
+    kChildrenTilesForward = RGL_CHILDREN_TILES_FORWARD,
+    kChildrenGeneric = RGL_CHILDREN_GENERIC,
+};
+
+struct ChildrenRoute {
+    ChildrenFamily family;
+    int refusal;                 // kChildrenRefused: the RGL_ERR_* code; RGL_OK otherwise
+    bool staged;                 // a stage-2 head exists and the workspace holds the stage-1 rows (and a packed image at its end)
+    FusedImageMode fused_mode;   // kChildrenFused: the form that runs ...
+    bool own_image;              // ... and whether the call packs an f32 image of its own (bf16x6 wanted, its form does not fit a CU)
+    bool f16;                    // kChildrenDeep: the f16-input contractions
+    bool pair_image;             // the two-stage pair and its head copy their weights from the packed image at hand (none when not
+                                 // staged, or in bf16x6: a three-piece bf16 image is in the fused kernel's layout only)
+};
+
 }  // namespace rgl

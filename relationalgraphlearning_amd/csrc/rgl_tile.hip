@@ -641,10 +641,12 @@ int launch_children(const ChildPlan& pl, hipStream_t st) {
 
 namespace rgl {
 
-// 1 = outside this kernel's envelope
+// host only: does launch_tile_children take the call?  (route_value_children)
+bool tile_children_covers(const RglGraph* g, int P, int A, int H) { return plan_children(*g, P, A, H).ok; }
+
 int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_out) {
     ChildPlan cp = plan_children(*g, c.P, c.A, c.H);
-    if (!cp.ok) return 1;
+    if (!cp.ok) return RGL_ERR_BAD_MODE;      // tile_children_covers was not asked
     cp.a.child_robot = c.child_robot;
     cp.a.humans = c.humans_next;
     cp.a.rows_out = rows_out;

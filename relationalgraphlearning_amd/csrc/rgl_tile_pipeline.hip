@@ -27,7 +27,7 @@
 //
 // Envelope of both: embedded_gaussian, gaussian, squared, equal_attention or diagonal similarity (round 5: the three plain-weight
 // normalisations), one adjacency for all layers -- or, round 6, one per layer (layerwise graphs) for the softmax and squared
-// normalisations at x_dim 32 and N <= 32 --, x_dim 32 | 64, 1-3 layers, N <= 64; any embedding MLPs and heads within the ABI limits.  Outside it: return 1 (the caller falls back to rgl_backward.hip / the general kernel).
+// normalisations at x_dim 32 and N <= 32 --, x_dim 32 | 64, 1-3 layers, N <= 64; any embedding MLPs and heads within the ABI limits.  Outside it: *taken = false before any launch (the caller falls back to rgl_backward.hip / the general kernel).
 //
 // Differentiated forward: graph_model.py:99-130, value_estimator.py:11-20, state_predictor.py:28-36, gcn.py:95-128.
 //
@@ -158,7 +158,7 @@ extern "C" int rgl_plan_graph_tiles(const RglGraph* graph, int n_scenes, int H, 
     if (!tiles_cover(g, H)) return RGL_OK;
     const bool lw = tiles_layerwise(g);
     const GraphPlan p = cap_graph_plan(plan_graph(n_scenes, H + 1, g.x_dim, g.num_layer, backward != 0, lw), max_workgroups);
-    if (p.grid < 1) return RGL_OK;              // a scene does not fit the LDS of a CU: the pipeline answers "not mine"
+    if (p.grid < 1) return RGL_OK;              // a scene does not fit the LDS of a CU: the pipeline does not take it
     const GraphForm f = graph_form(H + 1, g.x_dim, tiles_norm(g), lw);
     plan->covered = 1; plan->node_tiles = f.nt; plan->feature_tiles = f.xt; plan->layers = g.num_layer;
     plan->family = f.family; plan->norm = tiles_norm(g); plan->grid = p.grid; plan->resident = p.resident;
@@ -170,7 +170,7 @@ namespace rgl {
 
 // ------------------------------------------------------------------------------------------------
 // forward on the same tile kernels: models the shipped-shape MFMA kernels (rgl_scene.hip, rgl_fused_kernel.hip, ..) do not cover -- other
-// embedding MLPs (wr_dims / wh_dims), x_dim = 64 -- instead of the general VALU kernel.  0 bytes / 1 = not covered.
+// embedding MLPs (wr_dims / wh_dims), x_dim = 64 -- instead of the general VALU kernel.  0 bytes / *taken = false: not covered.
 //   1. mlp rows (forward): robot rows [S][X], human rows [S / spc][H][X] (sibling scenes share their crowd's rows)
 //   2. graph_kernel<.., false>: H_L -- all rows (motion head, H_out) or the robot row only (value head)
 //   3. mlp rows (forward): value head on row 0 -> value_out, motion head on rows 1.. -> humans_next
@@ -183,36 +183,71 @@ size_t tiles_forward_workspace_bytes(const RglGraph* g, const RglMlp* vh, const 
     return ((size_t)S * X + (size_t)(S / spc) * H * X + hl) * sizeof(float) + 3 * 256;
 }
 
+}  // namespace rgl
+
+namespace {
+
+// The forward's plan: whether the pipeline takes the call (ok) and, if so, its graph launch and row jobs.  vh / mh: the heads whose
+// outputs are wanted (null otherwise); workspace_bytes: 0 = no workspace
+struct TilesForwardPlan {
+    bool ok;
+    GraphPlan gp;
+    RowsJob j_wr, j_wh, j_v, j_m;
+};
+
+TilesForwardPlan plan_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* mh, int S, int spc, int H, bool want_H,
+                                    size_t workspace_bytes) {
+    TilesForwardPlan p;
+    p.ok = false;
+    const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
+    if (!graph || !workspace_bytes || !tiles_cover(*graph, H) || S < 1 || spc < 1 || S % spc) return p;
+    if (tiles_forward_mode() == 0) return p;          // measurements: the general kernel instead
+    if (workspace_bytes < rgl::tiles_forward_workspace_bytes(graph, vh, mh, S, spc, H, want_H)) return p;
+    const RglGraph& g = *graph;
+    p.gp = plan_graph(S, H + 1, g.x_dim, g.num_layer, false, tiles_layerwise(g));
+    if (p.gp.grid < 1) return p;
+    plan_rows_job(p.j_wr, g.w_r, S, 2048);
+    plan_rows_job(p.j_wh, g.w_h, S / spc * H, 2048);
+    if (has_v) plan_rows_job(p.j_v, *vh, S, 2048);
+    if (has_m) plan_rows_job(p.j_m, *mh, S * H, 2048);
+    {
+        RowsJob* emb[2] = {&p.j_wr, &p.j_wh};
+        RowsJob* heads[2] = {has_v ? &p.j_v : nullptr, has_m ? &p.j_m : nullptr};
+        balance_narrow(emb, 2, 2048);
+        balance_narrow(heads, 2, 2048);
+    }
+    for (const RowsJob* J : {&p.j_wr, &p.j_wh, has_v ? &p.j_v : nullptr, has_m ? &p.j_m : nullptr})
+        if (J && J->waves_per_wg < 1) return p;
+    p.ok = true;
+    return p;
+}
+
+}  // namespace
+
+namespace rgl {
+
+bool tiles_forward_covers(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int spc, int H, bool want_H,
+                          size_t workspace_bytes) {
+    return plan_tiles_forward(g, vh, mh, S, spc, H, want_H, workspace_bytes).ok;
+}
+
 int launch_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* mh, const float* robot, const float* humans, int S,
                          int spc, int H, float* H_out, float* value_out, float* humans_next, void* workspace, size_t workspace_bytes,
-                         hipStream_t st) {
+                         hipStream_t st, bool* taken) {
     const bool has_v = vh && vh->n_layers > 0 && value_out, has_m = mh && mh->n_layers > 0 && humans_next;
-    if (!graph || !workspace || !tiles_cover(*graph, H) || S < 1 || spc < 1 || S % spc) return 1;
-    if (tiles_forward_mode() == 0) return 1;          // measurements: the general kernel instead
-    if (workspace_bytes < tiles_forward_workspace_bytes(graph, has_v ? vh : nullptr, has_m ? mh : nullptr, S, spc, H, H_out != nullptr))
-        return 1;
+    TilesForwardPlan tp = plan_tiles_forward(graph, has_v ? vh : nullptr, has_m ? mh : nullptr, S, spc, H, H_out != nullptr,
+                                             workspace ? workspace_bytes : 0);
+    *taken = tp.ok;
+    if (!tp.ok) return RGL_OK;
     const RglGraph& g = *graph;
     const int N = H + 1, L = g.num_layer, X = g.x_dim, crowds = S / spc;
-    const GraphPlan gp = plan_graph(S, N, X, L, false, tiles_layerwise(g));
-    if (gp.grid < 1) return 1;
+    const GraphPlan& gp = tp.gp;
+    RowsJob &j_wr = tp.j_wr, &j_wh = tp.j_wh, &j_v = tp.j_v, &j_m = tp.j_m;
     Taker ws{(char*)workspace};
     float* Xr = ws.take<float>((size_t)S * X);
     float* Xh = ws.take<float>((size_t)crowds * H * X);
     const bool row0 = !has_m && !H_out;
     float* HL = H_out ? H_out : ws.take<float>(row0 ? (size_t)S * X : (size_t)S * N * X);
-    RowsJob j_wr, j_wh, j_v, j_m;
-    plan_rows_job(j_wr, g.w_r, S, 2048);
-    plan_rows_job(j_wh, g.w_h, crowds * H, 2048);
-    if (has_v) plan_rows_job(j_v, *vh, S, 2048);
-    if (has_m) plan_rows_job(j_m, *mh, S * H, 2048);
-    {
-        RowsJob* emb[2] = {&j_wr, &j_wh};
-        RowsJob* heads[2] = {has_v ? &j_v : nullptr, has_m ? &j_m : nullptr};
-        balance_narrow(emb, 2, 2048);
-        balance_narrow(heads, 2, 2048);
-    }
-    for (const RowsJob* J : {&j_wr, &j_wh, has_v ? &j_v : nullptr, has_m ? &j_m : nullptr})
-        if (J && J->waves_per_wg < 1) return 1;
     j_wr.in = RowMap{(float*)robot, 1, 0, (long long)g.w_r.dims[0]};
     j_wr.out = RowMap{Xr, 1, 0, (long long)X};
     j_wh.in = RowMap{(float*)humans, H, g.w_h.dims[0], (long long)H * g.w_h.dims[0]};
@@ -252,30 +287,32 @@ int launch_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* 
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-// 1 = not this path (outside the envelope, below the batch threshold, or the caller's workspace cannot hold the intermediates):
-// the per-scene VALU kernel of rgl_backward.hip runs.  Slab order of grad_out as documented in rgl_hip.h.
+// *taken = false, nothing launched: not this path (outside the envelope, below the batch threshold, or the caller's workspace
+// cannot hold the intermediates): the per-scene VALU kernel of rgl_backward.hip runs.  Every such answer comes before the first
+// launch.  Slab order of grad_out as documented in rgl_hip.h.
 static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp* mh, const float* robot, const float* humans,
                          int S, int H, int detach_graph, const float* d_value, const float* d_humans_next, const float* d_H,
-                         float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice) {
+                         float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice, bool* taken) {
+    *taken = false;
     // RGL_BACKWARD_MFMA = 0: never, 1: whenever the structure allows; default: by batch size, and whenever the per-scene kernel cannot
     // hold a scene in LDS (only_choice)
     const int mode = backward_mfma_mode();
-    if (mode == 0) return 1;
+    if (mode == 0) return RGL_OK;
     if (mode < 1 && !only_choice && S < env_int("RGL_BACKWARD_MFMA_MIN", 256)) {
         // Below the threshold the pipeline's device time is still the shorter one (84 vs 94 us at 100 scenes of 6 nodes, 95 vs 125 us
         // at 20 nodes), but it is seven launches instead of two and an eager training step is bound by the host.  While the stream
         // is being captured into a hipGraph only the device time counts.
         // (never asked of the legacy NULL stream: querying it while another stream captures would invalidate that capture)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (!st || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusActive) return 1;
+        if (!st || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusActive) return RGL_OK;
     }
     const RglGraph& g = *graph;
-    if (!tiles_cover(g, H)) return 1;
+    if (!tiles_cover(g, H)) return RGL_OK;
     const int N = H + 1, L = g.num_layer, X = g.x_dim;
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
     const bool embedded = g.similarity == RGL_SIM_EMBEDDED_GAUSSIAN, lw = tiles_layerwise(g);
     const GraphPlan gpf = plan_graph(S, N, X, L, false, lw), gp_full = plan_graph(S, N, X, L, true, lw);
-    if (gp_full.grid < 1 || gpf.grid < 1) return 1;
+    if (gp_full.grid < 1 || gpf.grid < 1) return RGL_OK;
 
     // gradient vector: w_r | w_h | w_a | Ws | value head | motion head
     const int n_wr = mlp_params(g.w_r), n_wh = mlp_params(g.w_h), n_graph = ((embedded ? 1 : 0) + L) * X * X;
@@ -319,9 +356,10 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
         g_slabs = ws.take<float>((size_t)gp.grid * n_graph);
         if (ws.used <= workspace_bytes) break;
     }
-    if (ws.used > workspace_bytes) return 1;
+    if (ws.used > workspace_bytes) return RGL_OK;
     for (const RowsJob* J : {&j_wr, &j_wh, has_v ? &j_v : nullptr, has_m ? &j_m : nullptr})
-        if (J && J->waves_per_wg < 1) return 1;
+        if (J && J->waves_per_wg < 1) return RGL_OK;
+    *taken = true;
 
     // 1. embeddings
     j_wr.in = RowMap{(float*)robot, 1, 0, (long long)g.w_r.dims[0]};
@@ -404,14 +442,14 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
 }
 
 
-// 1 = not this path (outside the envelope, below the batch threshold, or the caller's workspace cannot hold the intermediates): the
-// per-scene VALU kernel of rgl_backward.hip runs -- unless RGL_BACKWARD_MFMA=2 (tests), which turns "not this path" into an error.
+// *taken = false: not this path, the per-scene VALU kernel of rgl_backward.hip runs -- unless RGL_BACKWARD_MFMA=2 (tests), which
+// turns "not this path" into an error.
 int launch_backward_mfma(const RglGraph* graph, const RglMlp* vh, const RglMlp* mh, const float* robot, const float* humans,
                          int S, int H, int detach_graph, const float* d_value, const float* d_humans_next, const float* d_H,
-                         float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice) {
+                         float* grad_out, void* workspace, size_t workspace_bytes, hipStream_t st, int only_choice, bool* taken) {
     const int rc = backward_tiles(graph, vh, mh, robot, humans, S, H, detach_graph, d_value, d_humans_next, d_H, grad_out, workspace,
-                                  workspace_bytes, st, only_choice);
-    return (rc == 1 && backward_mfma_mode() == 2) ? RGL_ERR_BAD_MODE : rc;
+                                  workspace_bytes, st, only_choice, taken);
+    return (!rc && !*taken && backward_mfma_mode() == 2) ? RGL_ERR_BAD_MODE : rc;
 }
 
 }  // namespace rgl

@@ -195,7 +195,7 @@ int expand_level(const MprlPlanner& pl, const ChildrenArgs& ca, float* humans_ne
     // children.  Traced searches keep the three launches (predictor_ms / children_ms).  RGL_LEVEL_PROLOGUE=0: the three launches.
     LevelPrologue lp;
     const bool fold = level_prologue_enabled() && !before_children &&
-                      rgl::level_prologue_args(&pl, ca, humans_next, sp_image, &lp) == 0 &&
+                      rgl::level_prologue_args(&pl, ca, humans_next, sp_image, &lp) &&
                       rgl::fused_prologue_fits(&pl, P, H, vc.workspace_bytes, lp.scene_floats);
     if (fold) {
         rgl::ChildrenCall folded = vc;
@@ -355,14 +355,23 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
     // weight images of the value-of-children kernels: prepared once, every level copies them into LDS (0 = prepared)
     // (or handed in by the caller, packed once for fixed weights: MprlPlanner::children_image)
     const rgl::FusedImageMode image_mode = pl.contraction_dtype == RGL_CONTRACT_BF16X6 ? rgl::kModeBx : rgl::kModeF32;
-    const int image_ready = (pl.contraction_dtype == RGL_CONTRACT_F32 || image_mode != rgl::kModeF32) &&
-                            (pl.children_image != nullptr ||
-                             rgl::pack_children_images(&pl.value_graph, &pl.value_head, (int)lv[D - 1].P, A, H, ws + scratch_off,
-                                                       (size_t)scratch_bytes, st, image_mode) == 0);
+    int image_ready = 0;
+    if (pl.contraction_dtype == RGL_CONTRACT_F32 || image_mode != rgl::kModeF32) {
+        const int P_max = (int)lv[D - 1].P;
+        if (pl.children_image) image_ready = 1;
+        else if (rgl::fused_children_covers(&pl.value_graph, &pl.value_head, P_max, A, H, image_mode) &&
+                 (size_t)scratch_bytes >= rgl::fused_children_workspace_bytes(P_max, A, H)) {
+            rc = rgl::pack_children_images(&pl.value_graph, &pl.value_head, P_max, A, H, ws + scratch_off, (size_t)scratch_bytes, st, image_mode);
+            if (rc) return rc;
+            image_ready = 1;
+        }
+    }
     const float* sp_image = pl.predictor_image;
     if (!sp_image && rgl::scene_image_bytes(&pl)) {
         float* img = (float*)(ws + align_up256(scratch_off + scratch_bytes));
-        if (rgl::pack_scene_image(&pl, img, st) == RGL_OK) sp_image = img;
+        rc = rgl::pack_scene_image(&pl, img, st);
+        if (rc) return rc;
+        sp_image = img;
     }
     TailArgs tail{};
     tail.enabled = 1;
@@ -594,24 +603,31 @@ extern "C" int gcn_predict_f32(const GcnPlanner* planner, const float* robot, co
     const float* rows_image = nullptr;
     if (pl.contraction_dtype == RGL_CONTRACT_BF16X6) {
         const size_t ib = rgl::scene_image_bytes_for(pl.graph, nullptr);
-        if (ib && ib <= kGcnImageBytes && rgl::pack_scene_image_for(pl.graph, nullptr, w.image, st) == RGL_OK) rows_image = w.image;
+        if (ib && ib <= kGcnImageBytes) {
+            rc = rgl::pack_scene_image_for(pl.graph, nullptr, w.image, st);
+            if (rc) return rc;
+            rows_image = w.image;
+        }
     }
     rc = launch_gcn_prepare(pl.kinematics, A, pl.time_step, pl.actions, pl.root_robot_f64, pl.root_humans_f64, robot, humans, B, H, self6,
                             hum7, reward, st);
     if (rc) return rc;
     // the B x A rotated scenes: one wave per scene on the MFMA kernel where it covers the model (the shipped ValueNetwork: 6 / 7
     // inputs, 64-32 embeddings, head 150-100-100-1), else the general kernel
-    rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, w.fwd, w.fwd_bytes,
-                                   st, rows_image);
-    if (rc == 1)      // other embedding MLPs (x_dim 32: what this workspace is sized for): the tile kernels of rgl_tile_pipeline.hip
+    bool taken = rgl::scene_forward_covers(&pl.graph, &pl.value_head, nullptr, (int)S, 1, H, w.fwd_bytes);
+    if (taken)
+        rc = rgl::launch_scene_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, value, nullptr, w.fwd, w.fwd_bytes,
+                                       st, rows_image);
+    else      // other embedding MLPs (x_dim 32: what this workspace is sized for): the tile kernels of rgl_tile_pipeline.hip
         rc = rgl::launch_tiles_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, value, nullptr, w.fwd,
-                                       w.fwd_bytes, st);
-    if (rc == 1) {
+                                       w.fwd_bytes, st, &taken);
+    if (rc) return rc;
+    if (!taken) {
         if (require_mfma_forward()) return RGL_ERR_BAD_MODE;
         rc = rgl::launch_generic_forward(&pl.graph, &pl.value_head, nullptr, self6, hum7, (int)S, 1, H, nullptr, nullptr, value,
                                          nullptr, st);
+        if (rc) return rc;
     }
-    if (rc) return rc;
     return launch_onestep_select(robot, reward, value, nullptr, B, A, H, pl.gamma, pl.time_step, action_values, best_action, best_value,
                                  nullptr, st);
 }

@@ -406,6 +406,35 @@ typedef struct RglDeepChildrenPlan {
 } RglDeepChildrenPlan;
 int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan);
 
+/* rgl_plan_two_stage_children (ABI 8, additive) -- whether a stand-alone mprl_value_children_f32 call for P parents (crowds of H
+ * humans, planner->num_actions children each, a workspace of mprl_value_children_workspace_bytes) reaches the two-stage pair --
+ * stage 1 children_rank1_kernel<HR, NT, SKIP, SOFT> of rgl_rank1.hip (two layers, at most 32 nodes), stage 2 robot_head_kernel /
+ * robot_head_any_kernel of rgl_head.hip -- and in which forms.  The answer comes from the functions the launchers themselves call:
+ * the route of the call, stage 1's plan and grid, stage 2's variant, grid and cap.  HOST ONLY: no device call, no launch; reads the
+ * dimensions and modes of `planner` (no pointer of it is read) and the process's RGL_CHILDREN_TWO_STAGE, RGL_CHILDREN_FUSED,
+ * RGL_FUSED_MIN_TILES, RGL_CHILDREN_TILE_KERNEL and RGL_FORCE_GENERIC settings (once each).  image_at_hand: the call has a packed
+ * value-estimator image (MprlPlanner.children_image).
+ *   pair                 0: another kernel takes the call, or none (the other fields are 0 then) -- the fused kernel (the shipped head
+ *                        from 1200 child tiles, bf16x6 up to 20 nodes), three layers, more than 32 nodes or 96 children, a
+ *                        similarity outside the four row normalisations, a layerwise graph, a head without a stage-2 kernel
+ *   hr                   HR 8 | 20 | 32: human rows a lane holds in registers (N <= 8, <= 20, <= 32);   node_tiles NT = ceil(N / 16):
+ *                        the crowd waves;   child_tiles CT = ceil(A / 16): the child waves (CT + NT of the 8 waves carry a tile)
+ *   sld                  row stride of the per-child (a, b) table;   norm 0 softmax (embedded_gaussian, gaussian), 1 squared,
+ *                        2 equal_attention, 3 diagonal;   skip: skip connections
+ *   image                1: stage 1 copies its weights from the packed image; 0: from the raw matrices (no image at hand, bf16x6)
+ *   grid                 stage 1's workgroups; workgroup b walks parents b, b + grid, ..: parents_per_wg of them in the busiest
+ *   lds_bytes            dynamic LDS of a stage-1 workgroup
+ *   head_variant         0 robot_head_kernel<32,100,100>, 1 robot_head_kernel<150,100,100>, 2 robot_head_any_kernel
+ *   head_grid, head_tiles, head_tiles_per_wave   stage 2's workgroups, the 16-row tiles of the P * A rows, the most one wave walks
+ *   head_lds_bytes       dynamic LDS of a stage-2 workgroup
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE (P or H < 1). */
+typedef struct RglTwoStageChildrenPlan {
+    int pair, hr, node_tiles, child_tiles, sld, norm, skip, image, grid, parents_per_wg;
+    int head_variant, head_grid, head_tiles, head_tiles_per_wave;
+    size_t lds_bytes, head_lds_bytes;
+} RglTwoStageChildrenPlan;
+int rgl_plan_two_stage_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglTwoStageChildrenPlan* plan);
+
 /* rgl_plan_value_children (ABI 8, additive) -- which kernel family takes a stand-alone mprl_value_children_f32 call for P parents
  * (crowds of H humans, planner->num_actions children each): the one host function that decides it for the call itself, written
  * into a plain struct.  HOST ONLY: no device call, no launch; reads the dimensions and modes of `planner` (no pointer of it is

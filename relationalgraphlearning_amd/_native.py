@@ -105,6 +105,13 @@ class RglDeepChildrenPlan(C.Structure):
                  "parents_per_wg", "grid", "workgroups_per_cu", "reserved")] + [("lds_bytes", C.c_size_t)]
 
 
+class RglTwoStageChildrenPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in
+                ("pair", "hr", "node_tiles", "child_tiles", "sld", "norm", "skip", "image", "grid", "parents_per_wg",
+                 "head_variant", "head_grid", "head_tiles", "head_tiles_per_wave")] + \
+               [("lds_bytes", C.c_size_t), ("head_lds_bytes", C.c_size_t)]
+
+
 class RglValueChildrenPlan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("family", "refusal", "fused_mode", "own_image", "f16", "pair_image")]
 
@@ -202,6 +209,7 @@ SIGNATURES = {
     "rgl_plan_graph_tiles": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglGraphTilesPlan)]),
     "rgl_plan_prologue_embedding": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglPrologueEmbeddingPlan)]),
     "rgl_plan_deep_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.POINTER(RglDeepChildrenPlan)]),
+    "rgl_plan_two_stage_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.POINTER(RglTwoStageChildrenPlan)]),
     "rgl_plan_value_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglValueChildrenPlan)]),
     "rgl_plan_scene_forward": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(RglSceneForwardPlan)]),
@@ -274,7 +282,7 @@ SIGNATURES = {
 
 # Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
-ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_value_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
+ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_two_stage_children", "rgl_plan_value_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
             "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
             "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32"}

@@ -88,6 +88,11 @@ int launch_tile_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
 bool rank1_children_covers(const RglGraph* g, int P, int A, int H);                                                 // rgl_rank1.hip
 bool deep_children_covers(const RglGraph* g, int P, int A, int H, bool f16);                                        // rgl_deep.hip
 bool tile_children_covers(const RglGraph* g, int P, int A, int H);                                                  // rgl_tile.hip
+// the forms the two-stage pair gives a call (host only; rgl_plan_two_stage_children): each field from the function its launcher calls
+struct Rank1Form { int hr, node_tiles, child_tiles, sld, norm, image, grid, parents_per_wg; size_t lds_bytes; };
+bool rank1_children_form(const RglGraph* g, int P, int A, int H, bool image_at_hand, Rank1Form* out);             // rgl_rank1.hip
+struct HeadForm { int variant, grid, tiles, tiles_per_wave; size_t lds_bytes; };
+bool head_children_form(const RglMlp* head, int M, HeadForm* out);      // a stand-alone call's stage 2 (no tail)   // rgl_head.hip
 // the fused kernel's form of `mode` itself (no second form is tried); prologue_scene_floats >= 0: and its level-prologue form, with
 // a scene region of that many LDS floats
 bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, int H, FusedImageMode mode,

@@ -128,3 +128,35 @@ extern "C" int rgl_plan_value_children(const MprlPlanner* planner, int P, int H,
     *plan = RglValueChildrenPlan{r.family, r.refusal, r.fused_mode, r.own_image, r.f16, r.pair_image};
     return RGL_OK;
 }
+
+// A stand-alone call of P parents with a workspace of value_children_workspace_bytes: whether its route (route_value_children, the
+// function launch_value_children itself follows) ends at the two-stage pair, and then the forms its two launchers give it.
+extern "C" int rgl_plan_two_stage_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglTwoStageChildrenPlan* plan) {
+    if (!planner || !plan) return RGL_ERR_NULL;
+    if (P < 1 || H < 1) return RGL_ERR_BAD_SHAPE;
+    *plan = RglTwoStageChildrenPlan{};
+    const rgl::ChildrenRoute r = rgl::route_value_children(planner, P, H, ~(size_t)0, image_at_hand != 0);
+    if (r.family != rgl::kChildrenRank1) return RGL_OK;
+    rgl::Rank1Form s1;
+    rgl::HeadForm s2;
+    if (!rgl::rank1_children_form(&planner->value_graph, P, planner->num_actions, H, r.pair_image, &s1) ||
+        !rgl::head_children_form(&planner->value_head, P * planner->num_actions, &s2))
+        return RGL_OK;      // (the route asked both questions: not reached)
+    plan->pair = 1;
+    plan->hr = s1.hr;
+    plan->node_tiles = s1.node_tiles;
+    plan->child_tiles = s1.child_tiles;
+    plan->sld = s1.sld;
+    plan->norm = s1.norm;
+    plan->skip = planner->value_graph.skip_connection != 0;
+    plan->image = s1.image;
+    plan->grid = s1.grid;
+    plan->parents_per_wg = s1.parents_per_wg;
+    plan->head_variant = s2.variant;
+    plan->head_grid = s2.grid;
+    plan->head_tiles = s2.tiles;
+    plan->head_tiles_per_wave = s2.tiles_per_wave;
+    plan->lds_bytes = s1.lds_bytes;
+    plan->head_lds_bytes = s2.lds_bytes;
+    return RGL_OK;
+}

@@ -14,16 +14,27 @@ __global__ __launch_bounds__(kHeadThreads, 2) void robot_head_kernel(const HeadA
     head_rows_and_tail<D1, D2, D3>(lds, a, blockIdx.x, gridDim.x);
 }
 
+// ---- the launch decisions, each made in ONE place: read by the launchers below and by head_children_form ------------------------
+template <int D1, int D2, int D3>
+constexpr size_t head_lds_bytes() { return (size_t)HeadLds<D1, D2, D3>::total * sizeof(float); }
+// the grid of a launch without tail work: a tile per wave, at most the resident workgroups (1 or 2 per CU); beyond the cap tile t
+// goes to workgroup t % grid, wave (t / grid) % waves
+inline int head_rows_grid(int n_tiles, size_t lds_bytes) {
+    const int grid = (n_tiles + kHeadWaves - 1) / kHeadWaves;
+    const int cap = lds_bytes > 80 * 1024 ? 256 : 512;
+    return grid > cap ? cap : grid;
+}
+// the most tiles one wave of `grid` workgroups of `waves` waves walks
+inline int head_tiles_per_wave(int n_tiles, int grid, int waves) { return (n_tiles + grid * waves - 1) / (grid * waves); }
+
 template <int D1, int D2, int D3>
 int launch_head(const HeadArgs& ha, hipStream_t st) {
     auto kern = robot_head_kernel<D1, D2, D3>;
-    const size_t lds_bytes = (size_t)HeadLds<D1, D2, D3>::total * sizeof(float);
+    const size_t lds_bytes = head_lds_bytes<D1, D2, D3>();
     if (lds_bytes > 64 * 1024)
         RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lds_bytes));
-    int grid = (ha.n_tiles + kHeadWaves - 1) / kHeadWaves;
-    const int cap = lds_bytes > 80 * 1024 ? 256 : 512;          // resident workgroups: 1 or 2 per CU
-    if (grid > cap) grid = cap;
+    int grid = head_rows_grid(ha.n_tiles, lds_bytes);
     if (ha.tail.enabled) grid = (ha.P + ha.parents_per_wg - 1) / ha.parents_per_wg;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kHeadThreads), lds_bytes, st, ha);
     RGL_LAUNCH_CHECK();
@@ -121,6 +132,12 @@ __global__ __launch_bounds__(kAnyWaves * 64) void robot_head_any_kernel(const He
     }
 }
 
+inline size_t head_any_lds_bytes() { return (size_t)kAnyWaves * 2 * kAnyBuf * sizeof(float); }      // 128 KB: one workgroup per CU
+inline int head_any_grid(int n_tiles) {
+    const int grid = (n_tiles + kAnyWaves - 1) / kAnyWaves;
+    return grid > 256 ? 256 : grid;
+}
+
 }  // namespace
 
 // rows [M][64] (stage-1 hand-off) -> value;  the caller has asked head_variant: a head without a stage-2 kernel is not staged
@@ -137,12 +154,11 @@ static int launch_stage2(const RglGraph* g, const RglMlp* h, const float* rows, 
         aa.rows = rows;
         aa.value = value;
         aa.M = M;
-        aa.n_tiles = (M + 15) / 16;
-        const size_t lds_bytes = (size_t)kAnyWaves * 2 * kAnyBuf * sizeof(float);      // 128 KB: one workgroup per CU
+        aa.n_tiles = head_tiles(M);
+        const size_t lds_bytes = head_any_lds_bytes();
         RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(robot_head_any_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        int grid = (aa.n_tiles + kAnyWaves - 1) / kAnyWaves;
-        if (grid > 256) grid = 256;
+        const int grid = head_any_grid(aa.n_tiles);
         hipLaunchKernelGGL(robot_head_any_kernel, dim3(grid), dim3(kAnyWaves * 64), lds_bytes, stream, aa);
         RGL_LAUNCH_CHECK();
         return RGL_OK;
@@ -163,6 +179,17 @@ int launch_head_rows(const RglGraph* g, const RglMlp* h, const float* rows, int 
 
 int launch_head_children(const RglGraph* g, const RglMlp* h, const ChildrenCall& c, const float* rows) {
     return launch_stage2(g, h, rows, c.P * c.A, c.child_value, c.stream, c.image, c.tail, c.tail_done, c.A);
+}
+
+// host only: the form launch_stage2 gives the M rows of a call without tail work (rgl_plan_two_stage_children); false: no stage-2 kernel
+bool head_children_form(const RglMlp* h, int M, HeadForm* out) {
+    const int hv = head_variant(*h);
+    if (hv < 0) return false;
+    const int tiles = head_tiles(M);
+    const size_t lds = hv == 2 ? head_any_lds_bytes() : (hv == 0 ? head_lds_bytes<32, 100, 100>() : head_lds_bytes<150, 100, 100>());
+    const int grid = hv == 2 ? head_any_grid(tiles) : head_rows_grid(tiles, lds);
+    *out = HeadForm{hv, grid, tiles, head_tiles_per_wave(tiles, grid, hv == 2 ? kAnyWaves : kHeadWaves), lds};
+    return true;
 }
 
 }  // namespace rgl

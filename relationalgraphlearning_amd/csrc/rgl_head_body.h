@@ -42,6 +42,7 @@ struct HeadLds {
 
 constexpr int kHeadThreads = 512;     // 8 waves share one weight image; two workgroups per CU -> 4 waves/SIMD
 constexpr int kHeadWaves = kHeadThreads / 64;
+inline int head_tiles(int M) { return (M + 15) / 16; }      // 16-row MFMA tiles of M rows (host)
 
 // weight image of the head into LDS (every thread of an 8-wave workgroup; a barrier must follow)
 template <int D1, int D2, int D3>
@@ -167,7 +168,7 @@ inline void head_args_for(const RglGraph* g, const RglMlp* h, int hv, const floa
     ha.rows = rows;
     ha.value = value;
     ha.M = M;
-    ha.n_tiles = (M + 15) / 16;
+    ha.n_tiles = head_tiles(M);
     ha.tail = TailArgs{};
     ha.A = A; ha.P = A > 0 ? M / A : 0; ha.parents_per_wg = 1; ha.own_rows = 0;
     const TailArgs* ta = (tail && tail->enabled && A > 0 && M % A == 0) ? tail : nullptr;

@@ -571,13 +571,19 @@ inline Rank1Plan plan_rank1(const RglGraph& g, int P, int A, int H) {
     return pl;
 }
 
+// ---- the launch decisions, each made in ONE place: read by the launchers below and by rank1_children_form ------------------------
+// the grid: persistent, one 8-wave workgroup per CU striding the parents (b, b + grid, ..)
+inline int rank1_grid(int P) { return P < 256 ? P : 256; }
+// the weights come from the packed image: the call has one and the LDS offsets coincide with its layout
+inline bool rank1_takes_image(const Rank1Plan& pl, bool image_at_hand) { return pl.image_layout && image_at_hand; }
+
 template <int HR, int NT, bool SKIP, bool SOFT>
 int launch_rank1_ts(const Rank1Plan& pl, hipStream_t st) {
     auto kern = children_rank1_kernel<HR, NT, SKIP, SOFT>;
     if (pl.lds_bytes > 64 * 1024)
         RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)pl.lds_bytes));
-    const int grid = pl.a.P < 256 ? pl.a.P : 256;          // persistent: one 16-wave workgroup per CU
+    const int grid = rank1_grid(pl.a.P);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(pl.a.n_waves * 64), pl.lds_bytes, st, pl.a);
     RGL_LAUNCH_CHECK();
     return RGL_OK;
@@ -610,7 +616,7 @@ namespace rgl {
 int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_out) {
     Rank1Plan rp = plan_rank1(*g, c.P, c.A, c.H);
     if (!rp.ok) return RGL_ERR_BAD_MODE;      // rank1_children_covers was not asked
-    rp.a.image = rp.image_layout ? c.image : nullptr;
+    rp.a.image = rank1_takes_image(rp, c.image != nullptr) ? c.image : nullptr;
     rp.a.child_robot = c.child_robot;
     rp.a.humans = c.humans_next;
     rp.a.rows_out = rows_out;
@@ -619,5 +625,15 @@ int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_
 
 // host only: does launch_rank1_children take the call?  (route_value_children)
 bool rank1_children_covers(const RglGraph* g, int P, int A, int H) { return plan_rank1(*g, P, A, H).ok; }
+
+// host only: the form launch_rank1_children gives the call (rgl_plan_two_stage_children); false where rank1_children_covers says no
+bool rank1_children_form(const RglGraph* g, int P, int A, int H, bool image_at_hand, Rank1Form* out) {
+    const Rank1Plan rp = plan_rank1(*g, P, A, H);
+    if (!rp.ok) return false;
+    const int grid = rank1_grid(P);
+    *out = Rank1Form{rp.hr, rp.a.NT, rp.a.CT, rp.a.SLD, rp.a.sim, rank1_takes_image(rp, image_at_hand) ? 1 : 0, grid,
+                     (P + grid - 1) / grid, rp.lds_bytes};
+    return true;
+}
 
 }  // namespace rgl

@@ -80,6 +80,7 @@ int launch_generic_forward(const RglGraph* graph, const RglMlp* value_head, cons
 // ---- value of the sibling children: one ChildrenCall (rgl_search_args.h) from launch_value_children to the kernel it chooses ------
 // `c.image` (the two-stage pair and the stage-2 head): null, or the packed weight image of these weights (FusedLds layout,
 // pack_images_kernel) -- the kernels then copy their weight images instead of building them from the raw matrices
+// `rows_out`: the stage-1 rows [P A][64], at the start of the workspace's shared region (carve_children below)
 int launch_rank1_children(const RglGraph* g, const ChildrenCall& c, float* rows_out);                               // rgl_rank1.hip
 int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_out, int f16, const RglMlp* head,
                          int* head_done);                                                                           // rgl_deep.hip
@@ -101,30 +102,49 @@ bool fused_children_covers(const RglGraph* g, const RglMlp* head, int P, int A, 
 // whole parents and run the call's tail for them (*tail_done = 1 / 2 as for the fused children kernel; the generic-dims head has none)
 int launch_head_rows(const RglGraph* g, const RglMlp* head, const float* rows, int M, float* value, hipStream_t stream);   // rgl_head.hip
 int launch_head_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, const float* rows);         // rgl_head.hip
+// The children workspace (mprl_value_children_workspace_bytes), carved in ONE place: over a null base the same walk is its size.
+//   image   the weight image slot of the fused kernel and the two-stage pair: the first kImageBytes (rgl_fused.h) when H + 1 <= 32,
+//           absent (null) otherwise.  Its place depends on neither P nor the size the caller passed: a search packs it once for its
+//           widest level and every level's call, at any smaller P, finds it there; an own_image call packs into the same slot.
+//   region  one region behind it that its users share, one at a time: the stage-1 rows [P A][64], the fused kernel's partial-tile rows,
+//           the state predictor's embeddings, the scene-children rows, the tile pipeline's forward.  As long as the largest of their
+//           own carves; each user is handed (region, region_bytes), none the raw workspace.
+struct ChildrenWorkspace {
+    float* image;
+    void* region;
+    size_t region_bytes;
+    size_t bytes;
+};
+ChildrenWorkspace carve_children(void* base, const MprlPlanner* pl, int P, int H);                                  // rgl_fused.hip
+// the same for a call's own workspace: all null / 0 when the call has none or a shorter one (no user gets any of it)
+inline ChildrenWorkspace carve_children_call(const MprlPlanner* pl, const ChildrenCall& c) {
+    const ChildrenWorkspace w = carve_children(c.workspace, pl, c.P, c.H);
+    return c.workspace && c.workspace_bytes >= w.bytes ? w : ChildrenWorkspace{};
+}
 // the fused tile kernel (rgl_fused_kernel.hip; its planner and this driver: rgl_fused.hip).  Its weight image is prepared in global memory by pack_images_kernel: by the caller once per
 // parameter state (c.image = MprlPlanner::children_image), else once per tree search (c.image_ready = 1 on the per-level calls)
-// or by the call itself, at the END of the workspace it is given.
+// or by the call itself, in the image slot of its workspace `w`.
 // kModeBx: the six-term bf16 products (RGL_CONTRACT_BF16X6): the image then holds three-piece bf16 fragments for that kernel only
 // own_image: the call packs the image of `mode` itself whatever c.image / c.image_ready offer (ChildrenRoute::own_image)
-int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode, bool own_image);   // rgl_fused.hip
-// P = the largest launch; asked first: fused_children_covers(.., mode) and a workspace of fused_children_workspace_bytes
-int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, FusedImageMode mode);                                                  // rgl_fused_image.hip
-size_t fused_children_workspace_bytes(int P, int A, int H);                                                         // rgl_fused.hip
-const float* fused_workspace_image(const void* workspace, size_t workspace_bytes);   // where pack_children_images put the image   // rgl_fused_image.hip
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, const ChildrenWorkspace& w, FusedImageMode mode,
+                          bool own_image);                                                                          // rgl_fused.hip
+// P = the largest launch; asked first: fused_children_covers(.., mode).  `image`: ChildrenWorkspace::image
+int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, float* image, hipStream_t stream,
+                         FusedImageMode mode);                                                                      // rgl_fused_image.hip
 // The ladder of the kernels above, as ONE host function: what a call of these sizes will do.  Launches nothing, reads no device
 // data.  prologue_scene_floats >= 0: the call carries a LevelPrologue with a scene region of that many LDS floats
-// workspace_bytes: 0 = none
+// workspace_bytes: 0 = none; only ever compared against carve_children's sizes
 ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t workspace_bytes, bool image_at_hand,
                                    int prologue_scene_floats = -1);                                                 // rgl_fast.hip
 int launch_value_children(const MprlPlanner* pl, ChildrenCall c);                                                  // rgl_fast.hip
-size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H);                                        // rgl_fast.hip
 // `level`: the parents and crowds, and their independent next-state / reward work; when the MFMA scene kernel runs, it executes that
 // work on extra workgroups of the same launch and sets *children_done.
 // `sp_image`: the three-piece bf16 weight image of the scene kernel (scene_image_bytes, pack_scene_image) when the planner's mode is
 // RGL_CONTRACT_BF16X6; without one the f32 form of the kernel runs
+// `workspace`: a region of predict_humans_workspace_bytes (inside a search: ChildrenWorkspace::region)
 int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, float* humans_next, void* workspace,
                           size_t workspace_bytes, hipStream_t stream, int* children_done, const float* sp_image);   // rgl_scene.hip
+size_t predict_humans_workspace_bytes(int P, int crowds_per, int H);                                                // rgl_scene.hip
 // the level prologue of the fused children kernel (RGL_LEVEL_PROLOGUE) for the parents, crowds and reward work of `children`;
 // false = the state predictor is outside the prologue's form (host only: nothing is launched either way)
 bool level_prologue_args(const MprlPlanner* pl, const ChildrenArgs& children, float* humans_next, const float* sp_image,
@@ -140,8 +160,8 @@ int pack_scene_image(const MprlPlanner* pl, float* image, hipStream_t stream);
 size_t scene_image_bytes_for(const RglGraph& g, const RglMlp* motion_head);          // the same for a graph (+ optional motion head)
 int pack_scene_image_for(const RglGraph& g, const RglMlp* motion_head, float* image, hipStream_t stream);
 
-int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c);                                           // rgl_scene.hip
-bool scene_children_covers(const MprlPlanner* pl, int H);      // ... given a stage-2 head and a workspace of scene_children_workspace_bytes
+int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c, void* region, size_t region_bytes);       // rgl_scene.hip
+bool scene_children_covers(const MprlPlanner* pl, int H);      // ... given a stage-2 head and a region of scene_children_workspace_bytes
 size_t scene_children_workspace_bytes(int P, int A, int H);                                                        // rgl_scene.hip
 
 // the backward pass of large batches as MFMA tile kernels; *taken = false (RGL_OK, nothing launched): outside its envelope, below

@@ -946,7 +946,7 @@ int launch_deep_children(const RglGraph* g, const ChildrenCall& c, float* rows_o
 
 }  // namespace rgl
 
-// A stand-alone call of P parents with a workspace of value_children_workspace_bytes: whether its route (route_value_children, the
+// A stand-alone call of P parents with a workspace of mprl_value_children_workspace_bytes: whether its route (route_value_children, the
 // function launch_value_children itself follows) ends at the deep kernel, and then the form plan_deep gives the launch.
 extern "C" int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglDeepChildrenPlan* plan) {
     if (!planner || !plan) return RGL_ERR_NULL;

@@ -14,22 +14,6 @@
 
 namespace rgl {
 
-size_t value_children_workspace_bytes(const MprlPlanner* pl, int P, int H) {
-    const size_t children = (size_t)P * pl->num_actions * 64 * sizeof(float);
-    const size_t predictor = (size_t)P * (H + 1) * XD * sizeof(float);         // embeddings of launch_predict_humans
-    const size_t fused = H + 1 <= 32 ? fused_children_workspace_bytes(P, pl->num_actions, H) : 0;
-    const size_t scene = scene_children_workspace_bytes(P, pl->num_actions, H);
-    // the tile kernels, for planners outside the shipped shapes: children of the value graph, scenes of the state predictor
-    const size_t tiles_v = tiles_forward_workspace_bytes(&pl->value_graph, &pl->value_head, nullptr, P * pl->num_actions, pl->num_actions, H, 0);
-    const size_t tiles_p = pl->linear_state_predictor ? 0 : tiles_forward_workspace_bytes(&pl->predictor_graph, nullptr, &pl->motion_head, P, 1, H, 0);
-    const size_t tiles = tiles_v > tiles_p ? tiles_v : tiles_p;
-    const size_t m0 = children > predictor ? children : predictor;
-    const size_t m1 = m0 > scene ? m0 : scene;
-    const size_t m = m1 > tiles ? m1 : tiles;
-    // the fused kernel keeps its weight images at the END of the workspace: room for them behind every other use
-    return H + 1 <= 32 ? ((m + 255) & ~(size_t)255) + fused_children_workspace_bytes(0, pl->num_actions, H) + (fused > m ? fused - m : 0) : m;
-}
-
 // Which kernel takes the value-of-children call of P parents -- the ladder, written once: launch_value_children switches on the
 // answer, rgl_plan_value_children / rgl_plan_deep_children / fused_prologue_fits report it.  Every condition is the owning unit's
 // own question (.._covers: its plan's answer); nothing is launched, no device data is read.
@@ -46,8 +30,10 @@ ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t w
     // offers them -- the first 64 input features of the fused kernel's last head matrix; plain f32 everywhere else
     const bool want_b6 = pl->contraction_dtype == RGL_CONTRACT_BF16X6;
     if (pl->contraction_dtype != RGL_CONTRACT_F32 && !want_f16 && !want_b6) return refuse(RGL_ERR_BAD_MODE);      // (2, the split-f16 mode of ABI 4..7, is gone)
-    r.staged = head_variant(*head) >= 0 && workspace_bytes >= value_children_workspace_bytes(pl, P, H);
-    // packed weight image of the value estimator (the caller's, or this search's at the end of the workspace): the two-stage pair
+    const ChildrenWorkspace need = carve_children(nullptr, pl, P, H);      // the sizes alone
+    const bool fits = workspace_bytes >= need.bytes;
+    r.staged = head_variant(*head) >= 0 && fits;
+    // packed weight image of the value estimator (the caller's, or this search's in the workspace's image slot): the two-stage pair
     // copies its weight images from it instead of building them from the raw matrices (most of a small launch)
     r.pair_image = r.staged && !want_b6 && image_at_hand;      // (a three-piece bf16 image is in the fused kernel's layout only)
     const bool prologue = prologue_scene_floats >= 0;
@@ -76,12 +62,12 @@ ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t w
         if (deep_children_covers(g, P, A, H, false)) return take(kChildrenDeep);
         if (tile_children_covers(g, P, A, H)) return take(kChildrenTile);
         // every child's graph in full, one wave per child: the remaining similarity functions and layerwise graphs (`staged`: a
-        // stage-2 head, and a workspace that holds scene_children_workspace_bytes)
+        // stage-2 head, and a workspace whose region holds scene_children_workspace_bytes)
         if (scene_children_covers(pl, H)) return take(kChildrenScene);
     }
     if (want_f16) return refuse(RGL_ERR_BAD_MODE);
     // outside the shipped shapes (other embedding MLPs, x_dim = 64): the tile kernels, the children of a parent sharing its crowd's rows
-    if (tiles_forward_covers(g, head, nullptr, P * A, A, H, false, workspace_bytes)) return take(kChildrenTilesForward);
+    if (tiles_forward_covers(g, head, nullptr, P * A, A, H, false, fits ? need.region_bytes : 0)) return take(kChildrenTilesForward);
     // RGL_REQUIRE_MFMA_CHILDREN=1 (tests): refuse instead of running the general VALU kernel
     static const bool require = [] { const char* e = getenv("RGL_REQUIRE_MFMA_CHILDREN"); return e && e[0] == '1'; }();
     return require ? refuse(RGL_ERR_BAD_MODE) : take(kChildrenGeneric);
@@ -94,20 +80,21 @@ int launch_value_children(const MprlPlanner* pl, ChildrenCall c) {
     const RglMlp* head = &pl->value_head;
     const ChildrenRoute r = route_value_children(pl, c.P, c.H, c.workspace ? c.workspace_bytes : 0, c.image || c.image_ready,
                                                  c.prologue ? c.prologue->scene_floats : -1);
-    if (r.family == kChildrenFused) return launch_fused_children(g, head, c, r.fused_mode, r.own_image);
-    c.image = !r.pair_image ? nullptr : c.image ? c.image : fused_workspace_image(c.workspace, c.workspace_bytes);
-    float* rows = (float*)c.workspace;
+    const ChildrenWorkspace w = carve_children_call(pl, c);
+    if (r.family == kChildrenFused) return launch_fused_children(g, head, c, w, r.fused_mode, r.own_image);
+    c.image = !r.pair_image ? nullptr : c.image ? c.image : w.image;
+    float* rows = (float*)w.region;
     int rc = RGL_OK, head_done = 0;
     switch (r.family) {
         case kChildrenRefused: return r.refusal;
         case kChildrenRank1: rc = launch_rank1_children(g, c, rows); break;
         case kChildrenDeep: rc = launch_deep_children(g, c, rows, r.f16, head, &head_done); break;      // (may run stage 2 and the tail itself)
         case kChildrenTile: rc = launch_tile_children(g, c, rows); break;
-        case kChildrenScene: return launch_scene_children(pl, c);
+        case kChildrenScene: return launch_scene_children(pl, c, w.region, w.region_bytes);
         case kChildrenTilesForward: {
             bool taken = false;
             rc = launch_tiles_forward(g, head, nullptr, c.child_robot, c.humans_next, c.P * c.A, c.A, c.H, nullptr, c.child_value, nullptr,
-                                      c.workspace, c.workspace_bytes, c.stream, &taken);
+                                      w.region, w.region_bytes, c.stream, &taken);
             return (rc || taken) ? rc : RGL_ERR_BAD_MODE;
         }
         default:
@@ -129,7 +116,7 @@ extern "C" int rgl_plan_value_children(const MprlPlanner* planner, int P, int H,
     return RGL_OK;
 }
 
-// A stand-alone call of P parents with a workspace of value_children_workspace_bytes: whether its route (route_value_children, the
+// A stand-alone call of P parents with a workspace of mprl_value_children_workspace_bytes: whether its route (route_value_children, the
 // function launch_value_children itself follows) ends at the two-stage pair, and then the forms its two launchers give it.
 extern "C" int rgl_plan_two_stage_children(const MprlPlanner* planner, int P, int H, int image_at_hand, RglTwoStageChildrenPlan* plan) {
     if (!planner || !plan) return RGL_ERR_NULL;

@@ -90,7 +90,8 @@ static_assert(!fused_form_fits(20, 2, false, true) && !fused_form_fits(32, 2, tr
 constexpr int kPrologueHR = 20, kPrologueNT = 2;      // bf16x6, 17..20 nodes, softmax similarity
 static_assert(fused_form_fits(kPrologueHR, kPrologueNT, true, true), "the prologue's form is compiled");
 
-// sized for the larger layout: one buffer size whatever the contraction mode
+// sized for the larger layout: one buffer size whatever the contraction mode (a caller's MprlPlanner::children_image, and the first
+// kImageBytes of a children workspace: carve_children, rgl_common.h)
 constexpr size_t max2(size_t x, size_t y) { return x > y ? x : y; }
 constexpr size_t kImageFloats = max2(FusedImage<false>::scratch, FusedImage<true>::scratch);
 constexpr size_t kImageBytes = (kImageFloats * sizeof(float) + 255) & ~(size_t)255;
@@ -118,7 +119,6 @@ int launch_fused(const FusedPlan& pl, bool skip, hipStream_t st);
 // ---- rgl_fused_image.hip ----
 // one packed image, in the layout of the kernel that will read it (kModeBx: the bf16 / f32 hybrid of the last head matrix)
 int launch_pack_image(const FusedArgs& a, float* img, int mode, hipStream_t stream);
-float* image_of(void* workspace, size_t workspace_bytes);      // the image at the END of a children workspace
 
 }  // namespace fused
 }  // namespace rgl

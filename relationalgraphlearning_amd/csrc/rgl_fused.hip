@@ -193,16 +193,33 @@ inline bool prologue_form(const FusedPlan& pl, int scene_floats) {
 
 namespace rgl {
 
-// workspace: rows of the partial tiles [P][A % 16][64] | ... | weight image (at the END)
-size_t fused_children_workspace_bytes(int P, int A, int H) {
-    (void)H;
-    const size_t main_bytes = (size_t)P * (A % 16) * 64 * sizeof(float);
-    return ((main_bytes + 255) & ~(size_t)255) + kImageBytes;
+// The children workspace: the weight image slot | one region as long as the longest of its users' carves (rgl_common.h).
+ChildrenWorkspace carve_children(void* base, const MprlPlanner* pl, int P, int H) {
+    const int A = pl->num_actions;
+    auto rows = [](long long n) { Carver c{nullptr, 0}; c.take<float>(n * 64 * sizeof(float)); return (size_t)c.off; };
+    const size_t users[] = {
+        rows((long long)P * A),                                      // stage-1 rows of the rank-1, deep and tile kernels
+        H + 1 <= 32 ? rows((long long)P * (A % 16)) : 0,             // FusedArgs::rows_left
+        predict_humans_workspace_bytes(P, 1, H),
+        scene_children_workspace_bytes(P, A, H),
+        // the tile kernels, for planners outside the shipped shapes: children of the value graph, scenes of the state predictor
+        tiles_forward_workspace_bytes(&pl->value_graph, &pl->value_head, nullptr, P * A, A, H, 0),
+        pl->linear_state_predictor ? 0 : tiles_forward_workspace_bytes(&pl->predictor_graph, nullptr, &pl->motion_head, P, 1, H, 0)};
+    size_t longest = 0;
+    for (const size_t u : users) longest = u > longest ? u : longest;
+    Carver c{(char*)base, 0};
+    ChildrenWorkspace w;
+    w.image = H + 1 <= 32 ? c.take<float>(kImageBytes) : nullptr;
+    w.region = c.take<char>((long long)longest);
+    w.region_bytes = longest;
+    w.bytes = (size_t)c.off;
+    return w;
 }
 
-// The caller has asked route_value_children: the form of `mode` covers the call (with its prologue, if it carries one), the workspace
-// holds value_children_workspace_bytes, and own_image says whose image the kernel reads.
-int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, FusedImageMode mode, bool own_image) {
+// The caller has asked route_value_children: the form of `mode` covers the call (with its prologue, if it carries one), `w` is the
+// call's workspace (it holds carve_children's bytes), and own_image says whose image the kernel reads.
+int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenCall& c, const ChildrenWorkspace& w, FusedImageMode mode,
+                          bool own_image) {
     const int P = c.P, A = c.A, H = c.H;
     if (c.tail_done) *c.tail_done = 0;
     // the search's tail: selection always; the back-up chain + root step at the deepest level when handing whole roots to
@@ -213,17 +230,16 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenC
     FusedPlan fp = plan_fused(*g, *head, P, A, H, unit, mode);      // (.ok does not depend on `unit`: the route asked with 1)
     if (!fp.ok) return RGL_ERR_BAD_MODE;
     fp.pro = c.prologue;
+    if (!w.image) return RGL_ERR_BAD_MODE;      // (the route asked: a fused plan has at most 32 nodes, and a workspace)
     if (own_image || (!c.image_ready && !c.image)) {
-        int rc = launch_pack_image(fp.a, image_of(c.workspace, c.workspace_bytes), fp.mode(), c.stream);
+        int rc = launch_pack_image(fp.a, w.image, fp.mode(), c.stream);
         if (rc) return rc;
     }
-    const float* image = (c.image && !own_image) ? c.image : image_of(c.workspace, c.workspace_bytes);
-    float* rows_left = (float*)c.workspace;
     fp.a.child_robot = c.child_robot;
     fp.a.humans = c.humans_next;
     fp.a.value = c.child_value;
-    fp.a.image = image;
-    fp.a.rows_left = rows_left;
+    fp.a.image = (c.image && !own_image) ? c.image : w.image;
+    fp.a.rows_left = (float*)w.region;
     static const int image_sync = env_int("RGL_FUSED_IMAGE_SYNC", 0);
     fp.a.image_sync = image_sync;
     static const int phase_delay = env_int("RGL_FUSED_PHASE_DELAY", 0), prio = env_int("RGL_FUSED_PRIO", 2);

@@ -1,5 +1,5 @@
 // rgl_fused_image.hip -- the packed weight image of the fused children kernel (rgl_fused_kernel.hip; FusedLds, rgl_mlp_chain.h): the
-// packing kernel, where a workspace keeps the image, and the ABI calls with which a caller of fixed weights packs it once.
+// packing kernel, and the ABI calls with which a caller of fixed weights packs it once.
 #include "rgl_fused.h"
 
 using namespace rgl::fused;
@@ -154,20 +154,12 @@ int fused::launch_pack_image(const FusedArgs& a, float* img, int mode, hipStream
     return RGL_OK;
 }
 
-float* fused::image_of(void* workspace, size_t workspace_bytes) {
-    return reinterpret_cast<float*>((char*)workspace + ((workspace_bytes - kImageBytes) & ~(size_t)255));
-}
-
-const float* fused_workspace_image(const void* workspace, size_t workspace_bytes) {
-    return image_of(const_cast<void*>(workspace), workspace_bytes);
-}
-
-// asked first: fused_children_covers(.., mode) and a workspace of fused_children_workspace_bytes
-int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream, FusedImageMode mode) {
+// asked first: fused_children_covers(.., mode); `image`: the image slot of a children workspace (carve_children)
+int pack_children_images(const RglGraph* g, const RglMlp* head, int P, int A, int H, float* image, hipStream_t stream,
+                         FusedImageMode mode) {
     FusedPlan fp = plan_fused(*g, *head, P, A, H, 1, mode);
-    if (!fp.ok || !workspace || workspace_bytes < fused_children_workspace_bytes(P, A, H)) return RGL_ERR_BAD_MODE;
-    return launch_pack_image(fp.a, image_of(workspace, workspace_bytes), fp.mode(), stream);
+    if (!fp.ok || !image) return RGL_ERR_BAD_MODE;
+    return launch_pack_image(fp.a, image, fp.mode(), stream);
 }
 
 }  // namespace rgl

@@ -379,6 +379,20 @@ static int run_scene_kernels(const RglGraph& g, const RglMlp* mh, const float* r
     }
 }
 
+// The rows of S scenes around run_scene_kernels, one Carver walk: the embeddings x0 [S][32] | xh [S / crowds_per][H][32] | rows [S][64],
+// the value rows (with_rows: callers with a value head).  Null base: the size.  The embeddings are ONE take (one launch writes both):
+// gcn_predict_f32's forward scratch is the rows' sum rounded up once, which holds one padding in front of `rows`, not two.
+struct SceneRows { float *x0, *xh, *rows; size_t bytes; };
+SceneRows carve_scene_rows(void* base, long long S, int crowds_per, int H, bool with_rows) {
+    Carver c{(char*)base, 0};
+    SceneRows w;
+    w.x0 = c.take<float>((S + S / crowds_per * H) * XD * sizeof(float));
+    w.xh = w.x0 ? w.x0 + S * XD : nullptr;
+    w.rows = with_rows ? c.take<float>(S * 64 * sizeof(float)) : nullptr;
+    w.bytes = (size_t)c.off;
+    return w;
+}
+
 }  // namespace
 
 namespace rgl {
@@ -446,6 +460,8 @@ bool level_prologue_layout(const MprlPlanner* pl, int crowds_per, int P, int H, 
     return true;
 }
 
+size_t predict_humans_workspace_bytes(int P, int crowds_per, int H) { return carve_scene_rows(nullptr, P, crowds_per, H, false).bytes; }
+
 // humans_next[s] = motion_head(RGL(robot[s], humans[s / crowds_per]))[1:]  for P scenes (StatePredictor.forward).
 int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, float* humans_next, void* workspace,
                           size_t workspace_bytes, hipStream_t stream, int* children_done, const float* sp_image) {
@@ -455,8 +471,8 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
     const RglGraph& g = pl->predictor_graph;
     const RglMlp& mh = pl->motion_head;
     const int N = H + 1;
-    const bool ok = scene_kernel_covers(g, N) && mlp_is(mh, XD, HID, 5, false) && workspace &&
-                    workspace_bytes >= (size_t)P * N * XD * sizeof(float) && P % crowds_per == 0;
+    const bool ok = scene_kernel_covers(g, N) && mlp_is(mh, XD, HID, 5, false) && workspace && P % crowds_per == 0 &&
+                    workspace_bytes >= predict_humans_workspace_bytes(P, crowds_per, H);
     if (!ok) {
         // outside the shipped shapes: the tile kernels (rgl_tile_pipeline.hip) where they cover the model, else the general kernel
         if (P % crowds_per == 0) {
@@ -469,14 +485,13 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
         return launch_generic_forward(&g, nullptr, &mh, robot, humans, P, crowds_per, H, nullptr, nullptr, nullptr,
                                       humans_next, stream);
     }
-    float* x0_rows = (float*)workspace;                      // [P][32]
-    float* xh_rows = x0_rows + (size_t)P * XD;               // [n_crowds][H][32]
+    const SceneRows w = carve_scene_rows(workspace, P, crowds_per, H, false);
     // the level's reward / next-state work rides in the scene kernel's launch while the scene workgroups leave LDS free (few scenes),
     // in the embedding launch otherwise: never a launch of its own on this path
     const int children_in_scene_below = scene_children_below(pl->contraction_dtype == RGL_CONTRACT_BF16X6);
     const ChildrenArgs* in_scene = P < children_in_scene_below ? &level : nullptr;
     const ChildrenArgs* in_embed = in_scene ? nullptr : &level;
-    const int rc = run_scene_kernels(g, &mh, robot, humans, crowds_per, P, H, humans_next, nullptr, x0_rows, xh_rows, in_scene, stream,
+    const int rc = run_scene_kernels(g, &mh, robot, humans, crowds_per, P, H, humans_next, nullptr, w.x0, w.xh, in_scene, stream,
                                      in_embed, pl->contraction_dtype == RGL_CONTRACT_BF16X6 ? sp_image : nullptr);
     if (rc == RGL_OK) *children_done = 1;
     return rc;
@@ -484,7 +499,7 @@ int launch_predict_humans(const MprlPlanner* pl, const ChildrenArgs& level, floa
 
 // Module forwards (ValueEstimator.forward / StatePredictor.forward on a batch: value_estimator.py:11-20, state_predictor.py:20-39)
 // through the same kernels: embeddings + one wave per scene; values via the value-rows mode + robot_head_kernel.
-// workspace: x0 [S][32] | xh [S / crowds_per][H][32] | rows [S][64] (value head only).
+// workspace: carve_scene_rows, the value rows for a value head only.
 static bool scene_forward_form(const RglGraph& g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H) {
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
     if (!(has_v || has_m) || crowds_per < 1 || S % crowds_per != 0) return false;
@@ -496,8 +511,7 @@ static bool scene_forward_form(const RglGraph& g, const RglMlp* vh, const RglMlp
 
 size_t scene_forward_workspace_bytes(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H) {
     if (!g || !scene_forward_form(*g, vh, mh, S, crowds_per, H)) return 0;
-    const bool has_v = vh && vh->n_layers > 0;
-    return ((size_t)S * XD + (size_t)(S / crowds_per) * H * XD + (has_v ? (size_t)S * 64 : 0)) * sizeof(float);
+    return carve_scene_rows(nullptr, S, crowds_per, H, vh && vh->n_layers > 0).bytes;
 }
 
 bool scene_forward_covers(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int crowds_per, int H, size_t workspace_bytes) {
@@ -510,18 +524,16 @@ int launch_scene_forward(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, 
                          hipStream_t stream, const float* value_rows_image) {
     if (!workspace || !scene_forward_covers(g, vh, mh, S, crowds_per, H, workspace_bytes)) return RGL_ERR_BAD_MODE;
     const bool has_v = vh && vh->n_layers > 0, has_m = mh && mh->n_layers > 0;
-    float* x0_rows = (float*)workspace;
-    float* xh_rows = x0_rows + (size_t)S * XD;
-    float* rows = xh_rows + (size_t)(S / crowds_per) * H * XD;
+    const SceneRows w = carve_scene_rows(workspace, S, crowds_per, H, has_v);
     if (has_m) {
-        int rc = run_scene_kernels(*g, mh, robot, humans, crowds_per, S, H, humans_next, nullptr, x0_rows, xh_rows, nullptr, stream);
+        int rc = run_scene_kernels(*g, mh, robot, humans, crowds_per, S, H, humans_next, nullptr, w.x0, w.xh, nullptr, stream);
         if (rc) return rc;
     }
     if (has_v) {
-        int rc = run_scene_kernels(*g, nullptr, robot, humans, crowds_per, S, H, nullptr, rows, x0_rows, xh_rows, nullptr, stream, nullptr,
+        int rc = run_scene_kernels(*g, nullptr, robot, humans, crowds_per, S, H, nullptr, w.rows, w.x0, w.xh, nullptr, stream, nullptr,
                                    value_rows_image);
         if (rc) return rc;
-        return launch_head_rows(g, vh, rows, S, value_out, stream);
+        return launch_head_rows(g, vh, w.rows, S, value_out, stream);
     }
     return RGL_OK;
 }
@@ -529,26 +541,21 @@ int launch_scene_forward(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, 
 // Value of the children through the one-wave-per-scene kernel: every child's graph in full (no crowd sharing), any of the
 // similarity functions it implements, layerwise graphs, 1..4 layers -- the MFMA path of everything the shared-crowd kernels do
 // not cover (cosine / cosine_softmax scale the columns by child-dependent norms; layerwise graphs rebuild the adjacency from
-// every H_l).  workspace: x0 [P*A][32] | xh [P*H][32] | rows [P*A][64].
-size_t scene_children_workspace_bytes(int P, int A, int H) {
-    return ((size_t)P * A * (XD + 64) + (size_t)P * H * XD) * sizeof(float);
-}
+// every H_l).  Its region: carve_scene_rows of the P A children, the A of a parent sharing its crowd's rows.
+size_t scene_children_workspace_bytes(int P, int A, int H) { return carve_scene_rows(nullptr, (long long)P * A, A, H, true).bytes; }
 
 bool scene_children_covers(const MprlPlanner* pl, int H) {
     return scene_kernel_covers(pl->value_graph, H + 1) && head_variant(pl->value_head) >= 0;
 }
 
-int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c) {
+int launch_scene_children(const MprlPlanner* pl, const ChildrenCall& c, void* region, size_t region_bytes) {
     const RglGraph& g = pl->value_graph;
     const int P = c.P, A = c.A, H = c.H;
-    if (!scene_children_covers(pl, H) || !c.workspace || c.workspace_bytes < scene_children_workspace_bytes(P, A, H))
-        return RGL_ERR_BAD_MODE;
-    float* x0_rows = (float*)c.workspace;                    // [P*A][32]
-    float* xh_rows = x0_rows + (size_t)P * A * XD;           // [P][H][32]
-    float* rows = xh_rows + (size_t)P * H * XD;              // [P*A][64]
-    int rc = run_scene_kernels(g, nullptr, c.child_robot, c.humans_next, A, P * A, H, nullptr, rows, x0_rows, xh_rows, nullptr, c.stream);
+    const SceneRows w = carve_scene_rows(region, (long long)P * A, A, H, true);
+    if (!scene_children_covers(pl, H) || !region || region_bytes < w.bytes) return RGL_ERR_BAD_MODE;
+    int rc = run_scene_kernels(g, nullptr, c.child_robot, c.humans_next, A, P * A, H, nullptr, w.rows, w.x0, w.xh, nullptr, c.stream);
     if (rc) return rc;
-    return launch_head_rows(&g, &pl->value_head, rows, P * A, c.child_value, c.stream);
+    return launch_head_rows(&g, &pl->value_head, w.rows, P * A, c.child_value, c.stream);
 }
 
 }  // namespace rgl

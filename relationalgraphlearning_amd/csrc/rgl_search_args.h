@@ -128,7 +128,8 @@ struct ChildrenCall {
     size_t workspace_bytes;
     hipStream_t stream;
     const float* image;         // null, or the packed weight image of the value estimator (MprlPlanner::children_image)
-    int image_ready;            // 1: the end of the workspace holds that image (pack_children_images), no call packs its own
+    int image_ready;            // 1: the workspace's image slot (carve_children, rgl_common.h: the same place for every P) holds that
+                                // image (pack_children_images), no call packs its own
     const TailArgs* tail;       // null, or the search's select / back-up / root steps for these parents: the kernel runs them in its tail
     int* tail_done;             // and reports 1 (selection done) or 2 (deepest level: back-up steps and root decision too); 0 = not run
     const LevelPrologue* prologue;   // null, or the level's state predictor and reward / next-state pairs, run first (fused_prologue_fits)
@@ -150,7 +151,7 @@ enum ChildrenFamily {
 struct ChildrenRoute {
     ChildrenFamily family;
     int refusal;                 // kChildrenRefused: the RGL_ERR_* code; RGL_OK otherwise
-    bool staged;                 // a stage-2 head exists and the workspace holds the stage-1 rows (and a packed image at its end)
+    bool staged;                 // a stage-2 head exists and the workspace holds carve_children's bytes (the image slot and the stage-1 rows)
     FusedImageMode fused_mode;   // kChildrenFused: the form that runs ...
     bool own_image;              // ... and whether the call packs an f32 image of its own (bf16x6 wanted, its form does not fit a CU)
     bool f16;                    // kChildrenDeep: the f16-input contractions

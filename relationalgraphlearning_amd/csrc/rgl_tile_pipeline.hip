@@ -136,16 +136,19 @@ void graph_args(GraphArgs& ga, const RglGraph& g, int S, int N, int spc) {
     ga.xr_stride = g.x_dim; ga.xh_stride = (N - 1) * g.x_dim;
 }
 
-struct Taker {                 // carves 256-byte aligned pieces out of a workspace
-    char* base;
-    size_t used = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = (T*)(base + used);
-        used += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
+// The forward's workspace, one Carver walk (null base: its size): robot rows [S][X] | human rows [crowds][H][X] (sibling scenes share
+// their crowd's rows) | H_L -- all rows [S][N][X] for the motion head, the robot rows [S][X] for the value head alone; none when the
+// caller's H_out doubles as H_L
+struct TilesForwardRows { float *Xr, *Xh, *HL; size_t bytes; };
+TilesForwardRows carve_tiles_forward(void* base, long long S, long long crowds, int H, int X, bool has_m, bool want_H) {
+    Carver c{(char*)base, 0};
+    TilesForwardRows w;
+    w.Xr = c.take<float>(S * X * sizeof(float));
+    w.Xh = c.take<float>(crowds * H * X * sizeof(float));
+    w.HL = want_H ? nullptr : c.take<float>((has_m ? S * (H + 1) * X : S * X) * sizeof(float));
+    w.bytes = (size_t)c.off;
+    return w;
+}
 
 }  // namespace
 
@@ -177,10 +180,7 @@ namespace rgl {
 // ------------------------------------------------------------------------------------------------
 size_t tiles_forward_workspace_bytes(const RglGraph* g, const RglMlp* vh, const RglMlp* mh, int S, int spc, int H, int want_H) {
     if (!g || !tiles_cover(*g, H) || S < 1 || spc < 1 || S % spc) return 0;
-    const bool has_m = mh && mh->n_layers > 0;
-    const size_t X = g->x_dim, N = H + 1;
-    const size_t hl = (has_m && !want_H) ? (size_t)S * N * X : ((!has_m && !want_H) ? (size_t)S * X : 0);     // H_out doubles as H_L
-    return ((size_t)S * X + (size_t)(S / spc) * H * X + hl) * sizeof(float) + 3 * 256;
+    return carve_tiles_forward(nullptr, S, S / spc, H, g->x_dim, mh && mh->n_layers > 0, want_H != 0).bytes;
 }
 
 }  // namespace rgl
@@ -243,11 +243,10 @@ int launch_tiles_forward(const RglGraph* graph, const RglMlp* vh, const RglMlp* 
     const int N = H + 1, L = g.num_layer, X = g.x_dim, crowds = S / spc;
     const GraphPlan& gp = tp.gp;
     RowsJob &j_wr = tp.j_wr, &j_wh = tp.j_wh, &j_v = tp.j_v, &j_m = tp.j_m;
-    Taker ws{(char*)workspace};
-    float* Xr = ws.take<float>((size_t)S * X);
-    float* Xh = ws.take<float>((size_t)crowds * H * X);
+    const TilesForwardRows ws = carve_tiles_forward(workspace, S, crowds, H, X, has_m, H_out != nullptr);
+    float *Xr = ws.Xr, *Xh = ws.Xh;
     const bool row0 = !has_m && !H_out;
-    float* HL = H_out ? H_out : ws.take<float>(row0 ? (size_t)S * X : (size_t)S * N * X);
+    float* HL = H_out ? H_out : ws.HL;
     j_wr.in = RowMap{(float*)robot, 1, 0, (long long)g.w_r.dims[0]};
     j_wr.out = RowMap{Xr, 1, 0, (long long)X};
     j_wh.in = RowMap{(float*)humans, H, g.w_h.dims[0], (long long)H * g.w_h.dims[0]};
@@ -321,20 +320,20 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
 
     // workspace: X | H_L | dH_L, each [S][N][X] | slabs of the row jobs and of the graph kernel.  dX replaces dH_L in place (a scene's
     // upstream rows are in the workgroup's LDS long before its dX rows are written, and no other workgroup touches them)
-    Taker ws{(char*)workspace};
+    Carver ws{(char*)workspace, 0};
     const size_t feat = (size_t)S * N * X;
-    float* Xs = ws.take<float>(feat);
-    float* HL = ws.take<float>(feat);
-    float* dHL = ws.take<float>(feat);
+    float* Xs = ws.take<float>(feat * sizeof(float));
+    float* HL = ws.take<float>(feat * sizeof(float));
+    float* dHL = ws.take<float>(feat * sizeof(float));
     float* dXs = dHL;
     // one slab per wave: fewer waves per row job (more tiles each) when the caller's workspace -- sized for the per-scene kernel's
     // slabs, n_scenes x n_params floats -- is short (few scenes of many nodes)
     RowsJob j_wr, j_wh, j_v, j_m;
     float* g_slabs = nullptr;
-    const size_t used_feat = ws.used;
+    const long long off_feat = ws.off;
     GraphPlan gp = gp_full;
     for (int max_waves = 2048; max_waves >= 1; max_waves >>= 1) {
-        ws.used = used_feat;
+        ws.off = off_feat;
         gp = cap_graph_plan(gp_full, max_waves);
         plan_rows_job(j_wr, g.w_r, S, max_waves);
         plan_rows_job(j_wh, g.w_h, S * H, max_waves);
@@ -346,17 +345,17 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
             balance_narrow(emb, 2, max_waves);
             balance_narrow(heads, 2, max_waves);
         }
-        auto slabs_for = [&](RowsJob& J) { J.slabs = ws.take<float>((size_t)J.n_waves * J.n_params); };
+        auto slabs_for = [&](RowsJob& J) { J.slabs = ws.take<float>((long long)J.n_waves * J.n_params * sizeof(float)); };
         // (a detached graph's slabs are set aside all the same: the heads' waves, and with them the order in which their gradients
         // are summed, must not depend on detach_graph -- the motion head's gradients of a detached step are bit for bit those of
         // the step that is not)
         slabs_for(j_wr); slabs_for(j_wh);
         if (has_v) slabs_for(j_v);
         if (has_m) slabs_for(j_m);
-        g_slabs = ws.take<float>((size_t)gp.grid * n_graph);
-        if (ws.used <= workspace_bytes) break;
+        g_slabs = ws.take<float>((long long)gp.grid * n_graph * sizeof(float));
+        if ((size_t)ws.off <= workspace_bytes) break;
     }
-    if (ws.used > workspace_bytes) return RGL_OK;
+    if ((size_t)ws.off > workspace_bytes) return RGL_OK;
     for (const RowsJob* J : {&j_wr, &j_wh, has_v ? &j_v : nullptr, has_m ? &j_m : nullptr})
         if (J && J->waves_per_wg < 1) return RGL_OK;
     *taken = true;

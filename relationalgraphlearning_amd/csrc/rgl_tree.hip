@@ -95,44 +95,47 @@ inline dim3 grid_for(long long n, int block = kBlock) { return dim3((unsigned)((
 // ------------------------------------------------------------------------------------------------
 // workspace layout of the tree search
 // ------------------------------------------------------------------------------------------------
+// Byte offsets into the search's workspace (MprlLevelView reports them): one Carver walk, its `off` before each take.
 struct LevelLayout {
     long long P;
     long long robot, humans, humans_next, child_robot, reward, child_value, value1, keep, backup, best_slot;
     long long reward_clip;      // level 0 only (-1 elsewhere): the root rewards as upstream's action_clip reads them
 };
+struct TreeLayout {
+    LevelLayout lv[8];
+    long long scratch, scratch_bytes;      // the children workspace (rgl::carve_children) of the widest (= deepest) level, shared by all
+    long long scene_image;                 // three-piece bf16 image of the state predictor's scene kernel, packed once per search unless
+                                           // the caller hands one in (scene_image_bytes: 0 = none)
+    long long bytes;
+};
 
-inline int plan_levels(const MprlPlanner& pl, int B, int H, LevelLayout* lv, long long* total,
-                       long long* scratch_off = nullptr, long long* scratch_bytes = nullptr) {
+inline int plan_levels(const MprlPlanner& pl, int B, int H, TreeLayout* t) {
     const int A = pl.num_actions, D = pl.planning_depth;
     const int W = pl.do_action_clip ? pl.planning_width : A;
-    long long off = 0, P = B;
+    Carver c{nullptr, 0};
+    auto take = [&c](long long bytes) { const long long at = c.off; c.take<char>(bytes); return at; };
+    long long P = B;
     for (int l = 0; l < D; ++l) {
-        LevelLayout& L = lv[l];
+        LevelLayout& L = t->lv[l];
         L.P = P;
-        L.robot = off;        off = align_up256(off + (l == 0 ? 0 : P * 9 * 4));          // level 0 reads the caller's arrays
-        L.humans = -1;                                                               // = previous level's humans_next
-        L.humans_next = off;  off = align_up256(off + P * H * 5 * 4);
-        L.child_robot = off;  off = align_up256(off + P * A * 9 * 4);
-        L.reward = off;       off = align_up256(off + P * A * 4);
-        L.reward_clip = -1;
-        if (l == 0) { L.reward_clip = off; off = align_up256(off + P * A * 4); }
-        L.child_value = off;  off = align_up256(off + P * A * 4);
-        L.value1 = off;       off = align_up256(off + P * A * 4);
-        L.keep = off;         off = align_up256(off + P * W * 4);
-        L.backup = off;       off = align_up256(off + P * W * 4);
-        L.best_slot = off;    off = align_up256(off + P * 4);
-        if (l > 0) lv[l].humans = lv[l - 1].humans_next;
+        L.robot = take(l == 0 ? 0 : P * 9 * 4);                                     // level 0 reads the caller's arrays
+        L.humans = l > 0 ? t->lv[l - 1].humans_next : -1;
+        L.humans_next = take(P * H * 5 * 4);
+        L.child_robot = take(P * A * 9 * 4);
+        L.reward = take(P * A * 4);
+        L.reward_clip = l == 0 ? take(P * A * 4) : -1;
+        L.child_value = take(P * A * 4);
+        L.value1 = take(P * A * 4);
+        L.keep = take(P * W * 4);
+        L.backup = take(P * W * 4);
+        L.best_slot = take(P * 4);
         if (l + 1 < D) P *= W;
         if (P > (1ll << 31) / (A * 9)) return RGL_ERR_BAD_SHAPE;
     }
-    // hand-off buffer of the two-stage value kernels, sized for the widest (= deepest) level
-    const long long sb = (long long)rgl::value_children_workspace_bytes(&pl, (int)P, H);
-    if (scratch_off) *scratch_off = off;
-    if (scratch_bytes) *scratch_bytes = sb;
-    off = align_up256(off + sb);
-    // split-f16 image of the state predictor's scene kernel, packed once per search unless the caller hands one in
-    off = align_up256(off + (long long)rgl::scene_image_bytes(&pl));
-    *total = off;
+    t->scratch_bytes = (long long)rgl::carve_children(nullptr, &pl, (int)P, H).bytes;
+    t->scratch = take(t->scratch_bytes);
+    t->scene_image = take((long long)rgl::scene_image_bytes(&pl));
+    t->bytes = c.off;
     return RGL_OK;
 }
 
@@ -220,7 +223,8 @@ int expand_level(const MprlPlanner& pl, const ChildrenArgs& ca, float* humans_ne
         }
         RGL_LAUNCH_CHECK();
     } else {
-        int rc = rgl::launch_predict_humans(&pl, ca, humans_next, vc.workspace, vc.workspace_bytes, st, &children_done, sp_image);
+        const rgl::ChildrenWorkspace w = rgl::carve_children_call(&pl, vc);
+        int rc = rgl::launch_predict_humans(&pl, ca, humans_next, w.region, w.region_bytes, st, &children_done, sp_image);
         if (rc) return rc;
     }
     if (!children_done) {
@@ -269,7 +273,7 @@ extern "C" int mprl_expand_f32(const MprlPlanner* planner, const float* robot, c
 
 extern "C" size_t mprl_value_children_workspace_bytes(const MprlPlanner* planner, int P, int H) {
     if (!planner || P < 1 || H < 1) return 0;
-    return rgl::value_children_workspace_bytes(planner, P, H);
+    return rgl::carve_children(nullptr, planner, P, H).bytes;
 }
 
 extern "C" int mprl_value_children_f32(const MprlPlanner* planner, const float* child_robot, const float* humans_next,
@@ -296,21 +300,18 @@ extern "C" int mprl_pack_predictor_image_f32(const MprlPlanner* planner, float* 
 
 extern "C" size_t mprl_tree_workspace_bytes(const MprlPlanner* planner, int B, int H) {
     if (!planner || B < 1 || planner->planning_depth < 1 || planner->planning_depth > 8) return 0;
-    LevelLayout lv[8];
-    long long total = 0;
-    if (plan_levels(*planner, B, H, lv, &total)) return 0;
-    return (size_t)total;
+    TreeLayout t;
+    return plan_levels(*planner, B, H, &t) ? 0 : (size_t)t.bytes;
 }
 
 extern "C" int mprl_tree_level_view(const MprlPlanner* planner, int B, int H, int level, MprlLevelView* view) {
     if (!planner || !view) return RGL_ERR_NULL;
     if (planner->planning_depth < 1 || planner->planning_depth > 8 || level < 0 || level >= planner->planning_depth)
         return RGL_ERR_BAD_SHAPE;
-    LevelLayout lv[8];
-    long long total = 0;
-    int rc = plan_levels(*planner, B, H, lv, &total);
+    TreeLayout t;
+    int rc = plan_levels(*planner, B, H, &t);
     if (rc) return rc;
-    const LevelLayout& L = lv[level];
+    const LevelLayout& L = t.lv[level];
     view->n_parents = L.P;
     view->robot_off = level == 0 ? -1 : L.robot;
     view->humans_off = L.humans;
@@ -343,11 +344,11 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
         // the select kernel keeps the ids of the groups taken so far in kMaxSparseWidth registers
         if (W > kMaxSparseWidth) return RGL_ERR_BAD_MODE;
     }
-    LevelLayout lv[8];
-    long long total = 0, scratch_off = 0, scratch_bytes = 0;
-    rc = plan_levels(pl, B, H, lv, &total, &scratch_off, &scratch_bytes);
+    TreeLayout t;
+    rc = plan_levels(pl, B, H, &t);
     if (rc) return rc;
-    if ((long long)workspace_bytes < total) return RGL_ERR_WORKSPACE;
+    if ((long long)workspace_bytes < t.bytes) return RGL_ERR_WORKSPACE;
+    const LevelLayout* lv = t.lv;
     char* ws = (char*)workspace;
     hipStream_t st = (hipStream_t)stream;
     const float gamma_f = (float)pl.gamma_bar;
@@ -359,16 +360,17 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
     if (pl.contraction_dtype == RGL_CONTRACT_F32 || image_mode != rgl::kModeF32) {
         const int P_max = (int)lv[D - 1].P;
         if (pl.children_image) image_ready = 1;
-        else if (rgl::fused_children_covers(&pl.value_graph, &pl.value_head, P_max, A, H, image_mode) &&
-                 (size_t)scratch_bytes >= rgl::fused_children_workspace_bytes(P_max, A, H)) {
-            rc = rgl::pack_children_images(&pl.value_graph, &pl.value_head, P_max, A, H, ws + scratch_off, (size_t)scratch_bytes, st, image_mode);
+        else if (rgl::fused_children_covers(&pl.value_graph, &pl.value_head, P_max, A, H, image_mode)) {
+            // (the slot's place does not depend on P: every level's call finds the image there)
+            rc = rgl::pack_children_images(&pl.value_graph, &pl.value_head, P_max, A, H,
+                                           rgl::carve_children(ws + t.scratch, &pl, P_max, H).image, st, image_mode);
             if (rc) return rc;
             image_ready = 1;
         }
     }
     const float* sp_image = pl.predictor_image;
     if (!sp_image && rgl::scene_image_bytes(&pl)) {
-        float* img = (float*)(ws + align_up256(scratch_off + scratch_bytes));
+        float* img = (float*)(ws + t.scene_image);
         rc = rgl::pack_scene_image(&pl, img, st);
         if (rc) return rc;
         sp_image = img;
@@ -406,8 +408,8 @@ int tree_search(const MprlPlanner* planner, const float* robot, const float* hum
         int tail_done = 0;           // 1: the children kernel selected for its parents; 2: ... and finished the search (deepest level)
         if (events) RGL_HIP_TRY(hipEventRecord((hipEvent_t)events[3 * l], st));
         float* humans_next = (float*)(ws + L.humans_next);
-        rgl::ChildrenCall vc = children_call_for(pl, tail.child_robot, humans_next, P, H, (float*)(ws + L.child_value), ws + scratch_off,
-                                                 (size_t)scratch_bytes, st);
+        rgl::ChildrenCall vc = children_call_for(pl, tail.child_robot, humans_next, P, H, (float*)(ws + L.child_value), ws + t.scratch,
+                                                 (size_t)t.scratch_bytes, st);
         vc.image_ready = image_ready; vc.tail = &tail; vc.tail_done = &tail_done;
         rc = expand_level(pl, children_args_for(pl, pr, ph, humans_per, P, H, l == 0 ? roots_are_joint_states : 0,
                                                 (float*)(ws + L.child_robot), (float*)(ws + L.reward), reward_clip),

@@ -392,15 +392,17 @@ REPLAY_BYTES = {
     (40, 2048): 344320,
     (200, 257): 208384,
 }
+# (re-recorded when the children workspace became one carve, csrc/rgl_common.h carve_children: the weight image slot is reserved once,
+# not twice, so the searches whose widest level has few parents need less; profiles/workspace_carve.txt has the old and new values)
 TREE_BYTES = {      # (planning_depth, B, H): bytes; width 2, 81 actions, clipped, empty descriptors
-    (1, 1, 1): 248064,
-    (1, 1, 2): 248320,
+    (1, 1, 1): 158208,
+    (1, 1, 2): 158464,
     (1, 17, 5): 735232,
     (1, 2048, 19): 78247936,
-    (1, 3, 21): 257536,
+    (1, 3, 21): 237312,
     (1, 2, 127): 109568,
-    (2, 1, 1): 257792,
-    (2, 1, 2): 257792,
+    (2, 1, 1): 198912,
+    (2, 1, 2): 199168,
     (2, 17, 5): 1414144,
     (2, 2048, 19): 164640768,
     (2, 3, 21): 366080,
@@ -412,6 +414,46 @@ TREE_BYTES = {      # (planning_depth, B, H): bytes; width 2, 81 actions, clippe
     (3, 3, 21): 622592,
     (3, 2, 127): 475136,
 }
+# The children workspace and the module forwards' workspace with the shipped descriptors (dimensions and modes only: the size queries
+# read no pointer), so that every user of the children workspace's region has a size: recorded from the build that made each of
+# them one carve, every entry within the layout's bound of the build before it (at most 768 bytes of padding more; the children
+# workspace of few parents less by about the weight image, which was reserved twice)
+CHILDREN_BYTES = {(1, 1): 152064, (1, 2): 152320, (17, 5): 660480, (2048, 19): 68802560, (3, 21): 222208, (2, 127): 94720}   # (P, H)
+FORWARD_VALUE_BYTES = {(1, 1): 31232, (1, 2): 31488, (17, 5): 539648, (2048, 19): 68681728, (3, 21): 101376,
+                       (2, 127): 94720}                      # (B, H): B * 81 scenes, the 81 of a crowd sharing its rows
+FORWARD_MOTION_BYTES = {(1, 1): 256, (1, 2): 512, (17, 5): 13056, (2048, 19): 5242880, (3, 21): 8448, (2, 127): 32768}   # B scenes
+# mprl_tree_level_view of a depth-3, width-2 search of 3 roots with 21 humans: the offsets of the build before plan_levels walked a Carver
+LEVEL_VIEWS = [
+    dict(n_parents=3, robot_off=-1, humans_off=-1, humans_next_off=0, child_robot_off=1280, reward_off=10240, reward_clip_off=11264,
+         child_value_off=12288, value1_off=13312, keep_off=14336, backup_off=14592, best_slot_off=14848),
+    dict(n_parents=6, robot_off=15104, humans_off=0, humans_next_off=15360, child_robot_off=17920, reward_off=35584, reward_clip_off=-1,
+         child_value_off=37632, value1_off=39680, keep_off=41728, backup_off=41984, best_slot_off=42240),
+    dict(n_parents=12, robot_off=42496, humans_off=15360, humans_next_off=43008, child_robot_off=48128, reward_off=83200,
+         reward_clip_off=-1, child_value_off=87296, value1_off=91392, keep_off=95488, backup_off=95744, best_slot_off=96000),
+]
+
+
+def _dims_mlp(dims, last_relu):
+    m = nat.RglMlp()
+    m.n_layers, m.last_relu = len(dims) - 1, int(last_relu)
+    for i, d in enumerate(dims):
+        m.dims[i] = d
+    return m
+
+
+def _shipped_graph():
+    g = nat.RglGraph()
+    g.w_r, g.w_h = _dims_mlp((9, 64, 32), True), _dims_mlp((5, 64, 32), True)
+    g.x_dim, g.num_layer, g.similarity, g.skip_connection = 32, 2, nat.SIMILARITY["embedded_gaussian"], 1
+    return g
+
+
+def _shipped_planner():
+    pl = nat.MprlPlanner()
+    pl.value_graph, pl.value_head = _shipped_graph(), _dims_mlp((32, 32, 100, 100, 1), False)
+    pl.predictor_graph, pl.motion_head = _shipped_graph(), _dims_mlp((32, 64, 5), False)
+    pl.num_actions = 81
+    return pl
 
 
 def test_workspace_sizes_are_the_recorded_ones(monkeypatch):
@@ -441,6 +483,34 @@ def test_workspace_sizes_are_the_recorded_ones(monkeypatch):
         pl.planning_depth, pl.planning_width, pl.num_actions, pl.do_action_clip = depth, 2, 81, 1
         assert lib.mprl_tree_workspace_bytes(ctypes.byref(pl), B, H) == want, (depth, B, H)
     assert {(B, H) for _, B, H in TREE_BYTES} == set(SIZE_CASES)
+    sp, g = ctypes.byref(_shipped_planner()), ctypes.byref(_shipped_graph())
+    vh, mh = ctypes.byref(_dims_mlp((32, 32, 100, 100, 1), False)), ctypes.byref(_dims_mlp((32, 64, 5), False))
+    assert {k: lib.mprl_value_children_workspace_bytes(sp, *k) for k in SIZE_CASES} == CHILDREN_BYTES
+    assert {(B, H): lib.rgl_graph_forward_workspace_bytes(g, vh, None, B * 81, 81, H) for B, H in SIZE_CASES} == FORWARD_VALUE_BYTES
+    assert {(B, H): lib.rgl_graph_forward_workspace_bytes(g, None, mh, B, 1, H) for B, H in SIZE_CASES} == FORWARD_MOTION_BYTES
+
+
+def test_children_workspace_grows_with_the_parents():
+    """A search gives ONE children workspace, sized for its widest level, to the calls of all its levels: a call of fewer parents must
+    never ask for more.  Empty descriptors and the shipped ones, on both sides of the image slot's end (H + 1 = 32 | 33)."""
+    lib = nat.lib()
+    empty = nat.MprlPlanner()
+    empty.num_actions = 81
+    Ps = (1, 2, 3, 17, 199, 200, 256, 2048)
+    for pl in (empty, _shipped_planner()):
+        for H in (1, 5, 19, 24, 31, 32, 49):
+            sizes = [lib.mprl_value_children_workspace_bytes(ctypes.byref(pl), P, H) for P in Ps]
+            assert sizes[0] > 0 and sizes == sorted(sizes), (H, sizes)
+
+
+def test_tree_level_view_offsets_are_the_recorded_ones():
+    lib = nat.lib()
+    pl = nat.MprlPlanner()
+    pl.planning_depth, pl.planning_width, pl.num_actions, pl.do_action_clip = 3, 2, 81, 1
+    for level, want in enumerate(LEVEL_VIEWS):
+        v = nat.MprlLevelView()
+        assert lib.mprl_tree_level_view(ctypes.byref(pl), 3, 21, level, ctypes.byref(v)) == 0
+        assert {name: getattr(v, name) for name, _ in nat.MprlLevelView._fields_} == want, level
 
 
 def test_predict_entry_points_refuse_one_byte_less():

@@ -207,6 +207,24 @@ typedef struct RglGraphTilesPlan {
 } RglGraphTilesPlan;
 int rgl_plan_graph_tiles(const RglGraph* graph, int n_scenes, int H, int backward, int max_workgroups, RglGraphTilesPlan* plan);
 
+/* rgl_plan_scene_backward (ABI 8, additive) -- what the per-scene kernel of rgl_graph_backward_f32 (one workgroup per scene, every
+ * activation of the scene in LDS) would launch for n_scenes scenes of H humans: the answers of the functions the launch itself
+ * calls.  HOST ONLY: no device call, no launch.  The descriptors are validated as the launch validates them -- widths, depths and
+ * non-NULL weight pointers -- but no pointer is read.  Whether rgl_graph_backward_f32 hands a call to the tile pipeline instead is
+ * rgl_plan_graph_tiles' question, not this one's.
+ *   fits           1: a scene's activations fit the 160 KB LDS of a CU; 0: the per-scene kernel answers RGL_ERR_LDS
+ *   lds_bytes      dynamic LDS of a workgroup (also where it does not fit)
+ *   n_params       floats of a gradient slab = rgl_graph_param_count()
+ *   threads        of a workgroup
+ *   grid           workgroups: min(n_scenes, 4096); workgroup b walks scenes b, b + grid, ..: scenes_per_wg is the most one walks
+ * Errors: RGL_ERR_NULL, RGL_ERR_BAD_SHAPE, RGL_ERR_BAD_MODE as rgl_graph_backward_f32 gives them for the descriptors; n_scenes < 1. */
+typedef struct RglSceneBackwardPlan {
+    int fits, n_params, threads, grid, scenes_per_wg, reserved;
+    size_t lds_bytes;
+} RglSceneBackwardPlan;
+int rgl_plan_scene_backward(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head, int n_scenes, int H,
+                            RglSceneBackwardPlan* plan);
+
 /* rgl_transpose_f32 -- dst[c][r] = src[r][c]; turns a torch Linear weight (out,in) into the
  * k-major layout RglMlp wants.  Host-side convenience of this ABI (no reference counterpart). */
 int rgl_transpose_f32(const float* src, float* dst, int rows, int cols, rgl_stream_t stream);

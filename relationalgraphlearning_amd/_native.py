@@ -54,6 +54,11 @@ class RglGraphTilesPlan(C.Structure):
                 ("norm", C.c_int), ("grid", C.c_int), ("resident", C.c_int), ("lds_bytes", C.c_size_t)]
 
 
+class RglSceneBackwardPlan(C.Structure):
+    _fields_ = [("fits", C.c_int), ("n_params", C.c_int), ("threads", C.c_int), ("grid", C.c_int), ("scenes_per_wg", C.c_int),
+                ("reserved", C.c_int), ("lds_bytes", C.c_size_t)]
+
+
 class RglPrologueEmbeddingPlan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("prologue", "parents_per_wg", "workgroups", "chunk_parents", "chunk_crowds", "human_tiles",
                                        "robot_tiles", "row_floats", "chunks_per_wg", "reserved")]
@@ -207,6 +212,8 @@ SIGNATURES = {
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "rgl_plan_mlp_rows": (C.c_int, [C.POINTER(RglMlp), C.c_int, C.c_int, C.POINTER(RglRowsPlan)]),
     "rgl_plan_graph_tiles": (C.c_int, [C.POINTER(RglGraph), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglGraphTilesPlan)]),
+    "rgl_plan_scene_backward": (C.c_int, [C.POINTER(RglGraph), C.POINTER(RglMlp), C.POINTER(RglMlp), C.c_int, C.c_int,
+                                          C.POINTER(RglSceneBackwardPlan)]),
     "rgl_plan_prologue_embedding": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RglPrologueEmbeddingPlan)]),
     "rgl_plan_deep_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.POINTER(RglDeepChildrenPlan)]),
     "rgl_plan_two_stage_children": (C.c_int, [C.POINTER(MprlPlanner), C.c_int, C.c_int, C.c_int, C.POINTER(RglTwoStageChildrenPlan)]),
@@ -282,7 +289,7 @@ SIGNATURES = {
 
 # Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
-ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_two_stage_children", "rgl_plan_value_children", "rgl_plan_scene_forward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
+ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_two_stage_children", "rgl_plan_value_children", "rgl_plan_scene_forward", "rgl_plan_scene_backward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
             "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
             "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32"}

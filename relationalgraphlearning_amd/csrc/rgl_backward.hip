@@ -1,9 +1,9 @@
 // rgl_backward.hip -- gradients of the relational-graph forward with respect to every parameter
 // (training path: crowd_nav/utils/trainer.py:110-161,199-250 call forward+backward on batches of ~100
-// scenes).  One 256-thread workgroup per scene recomputes the forward with every activation kept in LDS and
-// back-propagates through  heads -> GCN layers -> row softmax -> similarity -> embedding MLPs ; each scene
-// writes its own gradient slab (every element exactly once, by one thread, as a fixed-order sum), and
-// reduce_slabs_kernel adds the slabs in scene order (in blocks of 256 scenes), so the result is deterministic.
+// scenes).  One 1024-thread workgroup (kThreads) per scene -- beyond 4096 scenes a workgroup walks scenes b, b + 4096, .. --
+// recomputes the forward with every activation kept in LDS and back-propagates through  heads -> GCN layers -> row softmax ->
+// similarity -> embedding MLPs ; each scene writes its own gradient slab (every element exactly once, by one thread, as a
+// fixed-order sum), and reduce_slabs_kernel adds the slabs in scene order (in blocks of 256 scenes), so the result is deterministic.
 //
 // Supported structure: all eight similarity functions of compute_similarity_matrix (graph_model.py:63-97), one adjacency for
 // all layers or one per layer (layerwise_graph), any depth / skip / MLP shapes within the ABI limits; a configuration whose
@@ -706,7 +706,33 @@ int plan_backward(const RglGraph* graph, const RglMlp* vh, const RglMlp* mh, int
     return RGL_OK;
 }
 
+// the per-scene kernel's launch for a plan: read by rgl_graph_backward_f32 and by rgl_plan_scene_backward
+constexpr int kMaxGrid = 4096;
+struct SceneBackwardLaunch { int grid, scenes_per_wg; size_t lds_bytes; };
+SceneBackwardLaunch scene_backward_launch(const BackwardArgs& a, int n_scenes) {
+    const int grid = n_scenes < kMaxGrid ? n_scenes : kMaxGrid;
+    return {grid, (n_scenes + grid - 1) / grid, (size_t)a.total * sizeof(float)};
+}
+
 }  // namespace
+
+extern "C" int rgl_plan_scene_backward(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head, int n_scenes,
+                                       int H, RglSceneBackwardPlan* plan) {
+    if (!graph || !plan) return RGL_ERR_NULL;
+    if (n_scenes < 1) return RGL_ERR_BAD_SHAPE;
+    *plan = RglSceneBackwardPlan{};
+    BackwardArgs a;
+    const int rc = plan_backward(graph, value_head, motion_head, H, a);
+    if (rc && rc != RGL_ERR_LDS) return rc;
+    const SceneBackwardLaunch launch = scene_backward_launch(a, n_scenes);
+    plan->fits = rc == RGL_OK ? 1 : 0;
+    plan->n_params = a.n_params;
+    plan->threads = kThreads;
+    plan->grid = launch.grid;
+    plan->scenes_per_wg = launch.scenes_per_wg;
+    plan->lds_bytes = launch.lds_bytes;
+    return RGL_OK;
+}
 
 extern "C" int rgl_graph_param_count(const RglGraph* graph, const RglMlp* value_head, const RglMlp* motion_head) {
     if (!graph) return RGL_ERR_NULL;
@@ -743,13 +769,13 @@ extern "C" int rgl_graph_backward_f32(const RglGraph* graph, const RglMlp* value
     a.robot = robot; a.humans = humans; a.n_scenes = n_scenes; a.H = H;
     a.d_value = d_value; a.d_humans_next = d_humans_next; a.d_H = d_H;
     a.slabs = (float*)workspace;
-    const size_t lds_bytes = (size_t)a.total * sizeof(float);
+    const SceneBackwardLaunch launch = scene_backward_launch(a, n_scenes);
+    const size_t lds_bytes = launch.lds_bytes;
     if (lds_bytes > 64 * 1024)
         RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rgl_scene_backward_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipStream_t st = (hipStream_t)stream;
-    const int grid = n_scenes < 4096 ? n_scenes : 4096;
-    hipLaunchKernelGGL(rgl_scene_backward_kernel, dim3(grid), dim3(kThreads), lds_bytes, st, a);
+    hipLaunchKernelGGL(rgl_scene_backward_kernel, dim3(launch.grid), dim3(kThreads), lds_bytes, st, a);
     RGL_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3((a.n_params + 255) / 256), dim3(256), 0, st, (const float*)workspace, n_scenes,
                        a.n_params, grad_out);

@@ -226,19 +226,27 @@ def scenes(run):
     always lie that close; among those of DISTINCT scenes a seed is found at which none does (reference: `margin`)."""
     from tests.test_gpu_parity import seeded_scenes
     distinct = DISTINCT if run.H <= 5 else DISTINCT_CROWDED
-    robot, humans = seeded_scenes(7000 + run.seed + run.H, min(run.S, distinct), run.H)
-    reps = -(-run.S // distinct)
+    first = getattr(run, "first", 0)        # tests/per_scene_backward.py: the run is scenes first .. first + S - 1 of the sequence
+    robot, humans = seeded_scenes(7000 + run.seed + run.H, min(first + run.S, distinct), run.H)
+    reps = -(-(first + run.S) // distinct)
     crowds = run.S // graph_flags(run)[4]   # sibling scenes share a crowd (forward only): humans [S / spc][H][5]
-    return robot.repeat(reps, 1)[:run.S].contiguous(), humans.repeat(reps, 1, 1)[:crowds].contiguous()
+    return robot.repeat(reps, 1)[first:first + run.S].contiguous(), humans.repeat(reps, 1, 1)[first:first + crowds].contiguous()
 
 
 def upstream(run):
-    """The gradient fed into the module's output, as test_gradients_value_estimator_and_state_predictor feeds it."""
+    """The gradient fed into the module's output, as test_gradients_value_estimator_and_state_predictor feeds it.  A table whose
+    Run has `first` and `dark` (tests/per_scene_backward.py) takes scenes first .. first + S - 1 of the sequence's gradient, zero
+    for the scenes of the sequence below `dark`."""
+    first, dark = getattr(run, "first", 0), getattr(run, "dark", 0)
+    S = first + run.S
     if run.module == "value":
-        return torch.linspace(-1.0, 1.5, run.S).reshape(run.S, 1)
-    if run.module == "rgl":                 # d_H on all rows, as test_gradients_rgl_output_and_path_g feeds it
-        return torch.randn(run.S, run.H + 1, run.X, generator=torch.Generator().manual_seed(5))
-    return torch.randn(run.S, run.H, run.head[-1], generator=torch.Generator().manual_seed(3))
+        up = torch.linspace(-1.0, 1.5, S).reshape(S, 1)
+    elif run.module == "rgl":               # d_H on all rows, as test_gradients_rgl_output_and_path_g feeds it
+        up = torch.randn(S, run.H + 1, run.X, generator=torch.Generator().manual_seed(5))
+    else:
+        up = torch.randn(S, run.H, run.head[-1], generator=torch.Generator().manual_seed(3))
+    up[:dark] = 0.0
+    return up[first:].contiguous()
 
 
 class relu_inputs(object):
@@ -296,7 +304,17 @@ def grad_error(got, want):
     return float(np.abs(np.asarray(got, np.float64) - want).max()) / max(1e-3, float(np.abs(want).max()))
 
 
-TABLES = {"rows": RUN}              # tests/graph_forms.py adds its own
+TABLES = {"rows": RUN}              # tests/graph_forms.py and tests/per_scene_backward.py add their own
+
+
+def _margin(a, b, zeros_decided):
+    """(a ReLU layer's smallest float64 |pre-activation|) / (the float32 evaluation's largest error in the layer)."""
+    small = np.abs(a)
+    if zeros_decided:
+        small = small[~((a == 0) & (b == 0))]
+        if small.size == 0:
+            return float("inf")
+    return float(small.min()) / max(float(np.abs(a - b).max()), 1e-300)
 
 
 @functools.lru_cache(maxsize=None)
@@ -305,7 +323,10 @@ def reference(run_id, detach=False, table="rows"):
     SAME oracle evaluated in float32 on the CPU (forward; gradients, worst over the parameters), scaled like the assertions.
     masks_agree: the two evaluations took the same side of every ReLU.  margin: the smallest over the ReLU layers of (the layer's
     smallest float64 |pre-activation|) / (the float32 evaluation's largest error in that layer); at 8 and above -- the factor the
-    regression-level bounds keep -- no float32 summation order puts a row on the other side of a ReLU."""
+    regression-level bounds keep -- no float32 summation order puts a row on the other side of a ReLU.  A table whose Run says
+    `zeros_decided` (tests/per_scene_backward.py) leaves out of the smallest the entries that are EXACTLY 0 in both evaluations:
+    the unnormalised adjacency of `concatenation` has all-zero rows, whose T_i and GCN pre-activations are 0 in any precision and
+    any summation order, and torch and the kernels both close a ReLU at 0."""
     run = TABLES[table][run_id]
     out, grads, pre = oracle(run, torch.float64, detach)
     out32, grads32, pre32 = oracle(run, torch.float32, detach)
@@ -313,7 +334,7 @@ def reference(run_id, detach=False, table="rows"):
     ref = {"out": out, "grads": grads,
            "yard_fwd": forward_error(out32, out), "yard_grad": max(grad_error(grads32[k], grads[k]) for k in grads),
            "masks_agree": all(np.array_equal(a > 0, b > 0) for a, b in zip(pre, pre32)), "n_masks": len(pre),
-           "margin": min(float(np.abs(a).min()) / max(float(np.abs(a - b).max()), 1e-300) for a, b in zip(pre, pre32))}
+           "margin": min(_margin(a, b, getattr(run, "zeros_decided", False)) for a, b in zip(pre, pre32))}
     for a in [out] + list(grads.values()):
         a.setflags(write=False)
     return ref

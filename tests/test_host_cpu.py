@@ -42,6 +42,7 @@ def test_struct_layout_matches_header_sizes():
     assert ctypes.sizeof(nat.RglTransposeJob) == 2 * 8 + 2 * 4 and ctypes.sizeof(nat.RglGatherJob) == 2 * 8 + 2 * 4      # ABI 7
     assert ctypes.sizeof(nat.RglValueChildrenPlan) == 6 * 4
     assert ctypes.sizeof(nat.RglTwoStageChildrenPlan) == 14 * 4 + 2 * 8
+    assert ctypes.sizeof(nat.RglSceneBackwardPlan) == 6 * 4 + 8
 
 
 def test_contraction_modes_and_level_view_match_the_header():

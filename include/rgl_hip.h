@@ -997,6 +997,12 @@ int sarl_value_train_f32(const SarlPlanner* planner, const float* rows, int n_sc
 int sarl_value_backward_f32(const SarlPlanner* planner, const float* rows, const float* grad_value, int n_scenes, int H,
                             void* workspace, size_t workspace_bytes, const SarlGrads* grads, rgl_stream_t stream);
 
+/* The library's RGL_* environment switches ("Environment switches"), host only (added within ABI 8): the name of
+ * switch i (NULL past the end), and the value the library would read for it from `text_or_null` -- the variable's text, NULL when it
+ * is unset.  Nothing is read from the environment; RGL_ERR_BAD_SHAPE: no such switch. */
+const char* rgl_switch_name(int i);
+int rgl_switch_parse(int i, const char* text_or_null, int* value);
+
 /* library identification: ABI version and the gfx target the device code was built for */
 int rgl_abi_version(void);
 const char* rgl_build_target(void);

@@ -283,16 +283,19 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "sarl_value_backward_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                           C.POINTER(SarlGrads), C.c_void_p]),
+    "rgl_switch_name": (C.c_char_p, [C.c_int]),
+    "rgl_switch_parse": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     "rgl_abi_version": (C.c_int, []),
     "rgl_build_target": (C.c_char_p, []),
 }
 
-# Exports added within an ABI version (host-only planners, the replay push, the exploration kernels): an older build of the same version (RGL_HIP_LIBRARY:
+# Exports added within an ABI version (host-only planners, the replay push, the exploration kernels, the switch table): an older build of the same version (RGL_HIP_LIBRARY:
 # the A/B of two builds under one Python tree) lacks them and still loads; asking such a build for one raises AttributeError.
 ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_two_stage_children", "rgl_plan_value_children", "rgl_plan_scene_forward", "rgl_plan_scene_backward", "rgl_replay_push_workspace_bytes", "rgl_replay_push_f32",
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
             "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
-            "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32"}
+            "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32",
+            "rgl_switch_name", "rgl_switch_parse"}
 
 _lib = None
 

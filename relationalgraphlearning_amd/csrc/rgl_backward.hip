@@ -770,13 +770,9 @@ extern "C" int rgl_graph_backward_f32(const RglGraph* graph, const RglMlp* value
     a.d_value = d_value; a.d_humans_next = d_humans_next; a.d_H = d_H;
     a.slabs = (float*)workspace;
     const SceneBackwardLaunch launch = scene_backward_launch(a, n_scenes);
-    const size_t lds_bytes = launch.lds_bytes;
-    if (lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rgl_scene_backward_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(rgl_scene_backward_kernel, dim3(launch.grid), dim3(kThreads), lds_bytes, st, a);
-    RGL_LAUNCH_CHECK();
+    rc = rgl::launch_lds(rgl_scene_backward_kernel, dim3(launch.grid), dim3(kThreads), launch.lds_bytes, st, a);
+    if (rc) return rc;
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3((a.n_params + 255) / 256), dim3(256), 0, st, (const float*)workspace, n_scenes,
                        a.n_params, grad_out);
     RGL_LAUNCH_CHECK();

@@ -6,6 +6,7 @@
 
 #include "rgl_hip.h"
 #include "rgl_search_args.h"
+#include "rgl_switches.h"
 
 #define RGL_HIP_TRY(expr)                          \
     do {                                           \
@@ -21,7 +22,24 @@
 
 namespace rgl {
 
+constexpr int kCuCount = 256;      // MI355X
 constexpr int kLdsBytesPerCu = 160 * 1024;
+// workgroups of `lds_bytes` each that a CU's LDS holds, `most` at the most (what the kernel's waves or registers allow)
+inline int workgroups_per_cu_by_lds(size_t lds_bytes, int most) {
+    const int fit = (int)((size_t)kLdsBytesPerCu / lds_bytes);
+    return fit < most ? fit : most;
+}
+
+// A launch with dynamic LDS: above the size every kernel may ask for, the kernel's attribute is raised first.  Returns what
+// hipGetLastError() says (hipSuccess is RGL_OK).
+constexpr size_t kLdsBytesWithoutAttribute = 64 * 1024;
+template <class K, class... A>
+int launch_lds(K kern, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const A&... args) {
+    if (lds_bytes > kLdsBytesWithoutAttribute)
+        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, args...);
+    return (int)hipGetLastError();
+}
 
 inline int validate_mlp(const RglMlp& m, int want_in, int want_out) {
     if (m.n_layers < 1 || m.n_layers > RGL_MAX_MLP_LAYERS) return RGL_ERR_BAD_SHAPE;
@@ -218,25 +236,6 @@ struct Carver {
         return p;
     }
 };
-
-// an integer environment switch, read on every call (a caller that wants it read once per process keeps a `static` of its own)
-inline int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e && e[0]) ? atoi(e) : dflt;
-}
-// The switches more than one function asks for, one reader each ("Environment switches").  Read on every call:
-inline bool require_mfma_forward() { const char* e = getenv("RGL_REQUIRE_MFMA_FORWARD"); return e && e[0] == '1'; }
-inline int tiles_forward_mode() { return env_int("RGL_TILES_FORWARD", 1); }      // 0: never the tile kernels, 2: the tile kernels first
-inline int backward_mfma_mode() { return env_int("RGL_BACKWARD_MFMA", -1); }
-// ... and once per process:
-inline bool level_prologue_enabled() {               // off only when it starts with 0
-    static const bool on = [] { const char* e = getenv("RGL_LEVEL_PROLOGUE"); return !(e && e[0] == '0'); }();
-    return on;
-}
-inline bool fused_tail_disabled() {                  // select, back-up and root as stand-alone kernels
-    static const bool off = env_int("RGL_FUSED_NO_TAIL", 0) != 0;
-    return off;
-}
 
 // One operation, rounded on its own.  The search's bookkeeping, the rewards and path G's features follow the reference's chains of
 // scalar / tensor operations -- a product and the sum that takes it are two roundings -- and tests/search_bookkeeping.py and

@@ -786,8 +786,6 @@ __global__ __launch_bounds__(kDeepThreads, 2) void children_deep_kernel(const De
     }
 }
 
-inline int deep_workgroups_per_cu(size_t lds_bytes) { return lds_bytes * 2 <= (size_t)rgl::kLdsBytesPerCu ? 2 : 1; }
-
 struct DeepPlan {
     DeepArgs a;
     size_t lds_bytes;
@@ -813,8 +811,7 @@ inline DeepPlan plan_deep(const RglGraph& g, int P, int A, int H) {
     a.TLD = (N + 3) & ~3;
     // last node tile with at most four valid nodes, three layers, softmax similarity: the T4 form of the kernel (4 x 4 x 1 MFMA for
     // that tile).  Its table rows end at node 16 LT + 3 (TLD = (N + 3) & ~3 >= 16 LT + 4): every row the T4 kernel touches is inside.
-    static const bool t4_off = [] { const char* e = getenv("RGL_DEEP_T4"); return e && e[0] == '0'; }();
-    const bool t4_wanted = !t4_off && a.L == 3 && pl.NT >= 2 && N - 16 * (pl.NT - 1) <= 4 && a.sim == SIM_SOFTMAX;
+    const bool t4_wanted = deep_t4_enabled() && a.L == 3 && pl.NT >= 2 && N - 16 * (pl.NT - 1) <= 4 && a.sim == SIM_SOFTMAX;
     pl.t4 = t4_wanted;
     int off = 0;
     auto take = [&](int nfl) { int o = off; off += (nfl + 3) & ~3; return o; };
@@ -844,11 +841,10 @@ inline bool deep_form_exists(const DeepPlan& pl, bool f16) { return !f16 || pl.a
 // the T4 instantiation: plan_deep found the shape eligible (three layers, softmax, NT >= 2, RGL_DEEP_T4 not 0) and the form is f32
 inline bool deep_takes_t4(const DeepPlan& pl, bool f16) { return pl.t4 && !f16; }
 // workgroup slots a launch keeps resident
-inline int deep_slots(size_t lds_bytes) { return 256 * deep_workgroups_per_cu(lds_bytes); }
+inline int deep_slots(size_t lds_bytes) { return rgl::kCuCount * rgl::workgroups_per_cu_by_lds(lds_bytes, 2); }
 // stage 2 inside the launch: the shipped value head, the call's packed image at hand, RGL_DEEP_FUSE_HEAD not 0
 inline bool deep_fuses_head(const RglMlp* head, bool outputs_at_hand, bool image_at_hand) {
-    static const bool fuse_off = [] { const char* e = getenv("RGL_DEEP_FUSE_HEAD"); return e && e[0] == '0'; }();
-    return head && outputs_at_hand && image_at_hand && !fuse_off && head_variant(*head) == 0;
+    return head && outputs_at_hand && image_at_hand && deep_fuse_head_enabled() && head_variant(*head) == 0;
 }
 // ... its LDS (the head's fragments take the tables' place) and, without the search's tail, the contiguous parents of a workgroup
 inline size_t deep_fused_lds_bytes(size_t lds_bytes) {
@@ -872,13 +868,7 @@ int launch_deep_t(const DeepPlan& pl, const HeadArgs& ha, hipStream_t st) {
         if (deep_takes_t4(pl, F16)) return launch_deep_t<NT, F16, SKIP, SOFT, true>(pl, ha, st);      // plan_deep: eligible and its tables fit (RGL_DEEP_T4=0: never)
     }
     auto kern = children_deep_kernel<NT, F16, SKIP, SOFT, T4>;
-    if (pl.lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)pl.lds_bytes));
-    const int grid = deep_grid(pl);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kDeepThreads), pl.lds_bytes, st, pl.a, ha);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern, dim3(deep_grid(pl)), dim3(kDeepThreads), pl.lds_bytes, st, pl.a, ha);
 }
 
 template <int NT>
@@ -976,7 +966,7 @@ extern "C" int rgl_plan_deep_children(const MprlPlanner* planner, int P, int H, 
     plan->fuse_head = pl.a.fuse_head;
     plan->parents_per_wg = pl.a.parents_per_wg;
     plan->grid = deep_grid(pl);
-    plan->workgroups_per_cu = deep_workgroups_per_cu(pl.lds_bytes);
+    plan->workgroups_per_cu = rgl::workgroups_per_cu_by_lds(pl.lds_bytes, 2);
     plan->lds_bytes = pl.lds_bytes;
     return RGL_OK;
 }

@@ -69,8 +69,7 @@ ChildrenRoute route_value_children(const MprlPlanner* pl, int P, int H, size_t w
     // outside the shipped shapes (other embedding MLPs, x_dim = 64): the tile kernels, the children of a parent sharing its crowd's rows
     if (tiles_forward_covers(g, head, nullptr, P * A, A, H, false, fits ? need.region_bytes : 0)) return take(kChildrenTilesForward);
     // RGL_REQUIRE_MFMA_CHILDREN=1 (tests): refuse instead of running the general VALU kernel
-    static const bool require = [] { const char* e = getenv("RGL_REQUIRE_MFMA_CHILDREN"); return e && e[0] == '1'; }();
-    return require ? refuse(RGL_ERR_BAD_MODE) : take(kChildrenGeneric);
+    return require_mfma_children() ?refuse(RGL_ERR_BAD_MODE) : take(kChildrenGeneric);
 }
 
 // V(child) for the A children of each of P parents; children of one parent share humans_next[p].

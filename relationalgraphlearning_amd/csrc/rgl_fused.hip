@@ -1,7 +1,7 @@
 // rgl_fused.hip -- planner and driver of the fused children kernel (rgl_fused_kernel.hip), host code only: which launches take the
 // kernel, which form of it, how their tiles are cut into work items and dealt over the waves, and the call that launches a level
-// (launch_fused_children).  Every process-wide switch and cache of the fused path lives in this unit: a change to a launch decision
-// recompiles nothing else.
+// (launch_fused_children).  Every process-wide cache of the fused path lives in this unit and its switches (rgl_switches.h) are
+// asked here: a change to a launch decision recompiles nothing else.
 #include "rgl_fused.h"
 #include "rgl_scene_body.h"      // the level prologue's chunk arithmetic (prologue_chunk_end, prologue_row_floats), host side
 
@@ -16,15 +16,8 @@ namespace {
 // pipe-bound (MFMA + VALU issue, no co-execution) at a shader clock that drops with utilisation.  The fused kernel is one launch
 // that reads the child rows and writes the values; from ~3 k tiles (P ~ 500 parents of 81 actions) upwards it is the faster one
 // (P = 1024: 76 vs 79 us, 2048: 114 vs 131, 4096: 205 vs 233); below, the two-stage pair (8 waves share a parent, 4 waves per
-// SIMD in the head) hides the per-tile latency better.  RGL_CHILDREN_FUSED=1 / RGL_CHILDREN_TWO_STAGE=1 force one (tests).
-inline int fused_policy() {
-    static const int pol = [] {
-        const char* f = getenv("RGL_CHILDREN_FUSED");
-        const char* t = getenv("RGL_CHILDREN_TWO_STAGE");
-        return (f && f[0] == '1') ? 1 : ((t && t[0] == '1') ? -1 : 0);
-    }();
-    return pol;
-}
+// SIMD in the head) hides the per-tile latency better.  RGL_CHILDREN_FUSED=1 / RGL_CHILDREN_TWO_STAGE=1 force one (tests):
+// fused_policy().
 
 // How the tiles of a launch are cut into work items.  A work item = G consecutive full tiles of one parent (the last group of a
 // parent may be shorter, and also carries the parent's partial tile); its wave computes the parent's crowd quantities first, so
@@ -34,7 +27,7 @@ struct ItemPlan { int G, ipp, rot, grid, k_wg, inline_partial; };
 
 inline int fused_cu_count() {
     static const int n_cu = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev);
-                                 (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+                                 (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : rgl::kCuCount; }();
     return n_cu;
 }
 
@@ -60,7 +53,7 @@ inline ItemPlan plan_items(int P, int n_full, int rem, int unit) {
     if (k < 1) k = 1;
     k = ((k + unit - 1) / unit) * unit;
     const int grid = (P + k - 1) / k;
-    static const int force_g = env_int("RGL_FUSED_G", 0), force_inline = env_int("RGL_FUSED_INLINE_PARTIAL", -1);   // measurements
+    const int force_g = fused_forced_g(), force_inline = fused_forced_inline_partial();   // measurements
     ItemPlan best{1, n_full > 0 ? n_full : 1, 0, grid, k, 0};
     float best_cost = -1.f;
     for (int inl = 0; inl <= 1; ++inl) {
@@ -148,7 +141,7 @@ FusedPlan plan_fused(const RglGraph& g, const RglMlp& head, int P, int A, int H,
     pl.ok = false;
     pl.bx = mode == kModeBx;                    // any similarity: the head does not depend on it
     if (!fused_enabled()) return pl;
-    static const int min_tiles = env_int("RGL_FUSED_MIN_TILES", 1200);
+    const int min_tiles = fused_min_tiles();
     if (!pl.bx && fused_policy() == 0 && (long)P * ((A + 15) / 16) < min_tiles) return pl;
     if (!fused_architecture(g, head)) return pl;
     const int N = H + 1;
@@ -240,13 +233,10 @@ int launch_fused_children(const RglGraph* g, const RglMlp* head, const ChildrenC
     fp.a.value = c.child_value;
     fp.a.image = (c.image && !own_image) ? c.image : w.image;
     fp.a.rows_left = (float*)w.region;
-    static const int image_sync = env_int("RGL_FUSED_IMAGE_SYNC", 0);
-    fp.a.image_sync = image_sync;
-    static const int phase_delay = env_int("RGL_FUSED_PHASE_DELAY", 0), prio = env_int("RGL_FUSED_PRIO", 2);
-    fp.a.phase_delay = phase_delay;
-    fp.a.prio = prio;
-    static const int head_early = env_int("RGL_FUSED_HEAD_EARLY", 1);
-    fp.a.head_early = head_early;
+    fp.a.image_sync = fused_image_sync();
+    fp.a.phase_delay = fused_phase_delay();
+    fp.a.prio = fused_prio();
+    fp.a.head_early = fused_head_early();
     if (ta) {
         fp.a.tail = *ta;
         fp.a.tail.chain = chain;

@@ -949,17 +949,15 @@ int launch_fused_ts(const FusedPlan& pl, hipStream_t st) {
     if constexpr (!fused_form_fits(HR, NT, SOFT, BX)) return RGL_ERR_BAD_MODE;
     else {
     auto kern = children_fused_kernel<HR, NT, SKIP, SOFT, 32, 100, 100, BX, PRO>;
-    RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)pl.lds_bytes));
-    const int grid = pl.grid;                        // persistent, one 8-wave workgroup per CU (LDS-bound)
+    // pl.lds_bytes is this form's fused_lds_floats (plan_fused): launch_lds raises the kernel's attribute for every compiled form
+    static_assert(fused_lds_floats(HR, NT, SOFT, BX) * sizeof(float) > rgl::kLdsBytesWithoutAttribute, "the weight image alone is larger");
     PrologueArgs<PRO> pa{};
     if constexpr (PRO) {
         pa.scene = pl.pro->scene;
         pa.children = pl.pro->children;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kFusedWaves * 64), pl.lds_bytes, st, pl.a, pa);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    // persistent, one 8-wave workgroup per CU (LDS-bound)
+    return rgl::launch_lds(kern, dim3(pl.grid), dim3(kFusedWaves * 64), pl.lds_bytes, st, pl.a, pa);
     }
 }
 

@@ -385,14 +385,8 @@ int launch_generic_forward(const RglGraph* graph, const RglMlp* value_head, cons
     if (lds_bytes > (size_t)kLdsBytesPerCu) return RGL_ERR_LDS;
     a.L = L;
 
-    if (lds_bytes > 64 * 1024) {
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rgl_scene_forward_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    }
-    const int grid = n_scenes < 256 * 64 ? n_scenes : 256 * 64;
-    hipLaunchKernelGGL(rgl_scene_forward_kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, a);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    const int grid = n_scenes < kCuCount * 64 ? n_scenes : kCuCount * 64;
+    return launch_lds(rgl_scene_forward_kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, a);
 }
 
 }  // namespace rgl

@@ -18,11 +18,10 @@ GraphPlan plan_graph_nx(int S, int N, int L, bool bwd, bool lw) {
     if (p.lds > (size_t)rgl::kLdsBytesPerCu) return p;
     // persistent workgroups: as many as are resident at once (LDS, and the waves the kernel's register budget allows), scenes dealt
     // round robin
-    int per_cu = (int)((size_t)rgl::kLdsBytesPerCu / p.lds);
     const int by_waves = lw ? 2 : ((NT == 2 && XT == 2) ? 16 : (NT == 1 ? 12 : 8)) / (2 * NT);
-    per_cu = per_cu > by_waves ? by_waves : per_cu;
+    int per_cu = workgroups_per_cu_by_lds(p.lds, by_waves);
     per_cu = per_cu < 1 ? 1 : per_cu;
-    p.resident = 256 * per_cu;
+    p.resident = kCuCount * per_cu;
     p.grid = S < p.resident ? S : p.resident;
     return p;
 }

@@ -636,11 +636,7 @@ __global__ __launch_bounds__(NT * 128, LW ? 2 : ((NT == 2 && XT == 2) ? 4 : (NT 
 template <int NT, int XT, int L, bool BWD, bool COS, bool LW = false>
 int launch_graph_kernel(const GraphArgs& ga, size_t lds, int grid, hipStream_t st) {
     auto kern = graph_kernel<NT, XT, L, BWD, COS, LW>;
-    if (lds > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT * 128), lds, st, ga);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern, dim3(grid), dim3(NT * 128), lds, st, ga);
 }
 
 // graph_kernel<4, 4, 3, true, ..> is never launched: 64 features in three layers with the backward's buffers need more than the LDS

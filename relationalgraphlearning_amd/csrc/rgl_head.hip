@@ -21,7 +21,7 @@ constexpr size_t head_lds_bytes() { return (size_t)HeadLds<D1, D2, D3>::total * 
 // goes to workgroup t % grid, wave (t / grid) % waves
 inline int head_rows_grid(int n_tiles, size_t lds_bytes) {
     const int grid = (n_tiles + kHeadWaves - 1) / kHeadWaves;
-    const int cap = lds_bytes > 80 * 1024 ? 256 : 512;
+    const int cap = rgl::kCuCount * rgl::workgroups_per_cu_by_lds(lds_bytes, 2);
     return grid > cap ? cap : grid;
 }
 // the most tiles one wave of `grid` workgroups of `waves` waves walks
@@ -31,14 +31,9 @@ template <int D1, int D2, int D3>
 int launch_head(const HeadArgs& ha, hipStream_t st) {
     auto kern = robot_head_kernel<D1, D2, D3>;
     const size_t lds_bytes = head_lds_bytes<D1, D2, D3>();
-    if (lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds_bytes));
     int grid = head_rows_grid(ha.n_tiles, lds_bytes);
     if (ha.tail.enabled) grid = (ha.P + ha.parents_per_wg - 1) / ha.parents_per_wg;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kHeadThreads), lds_bytes, st, ha);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern, dim3(grid), dim3(kHeadThreads), lds_bytes, st, ha);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -132,10 +127,11 @@ __global__ __launch_bounds__(kAnyWaves * 64) void robot_head_any_kernel(const He
     }
 }
 
-inline size_t head_any_lds_bytes() { return (size_t)kAnyWaves * 2 * kAnyBuf * sizeof(float); }      // 128 KB: one workgroup per CU
+constexpr size_t head_any_lds_bytes() { return (size_t)kAnyWaves * 2 * kAnyBuf * sizeof(float); }      // 128 KB: one workgroup per CU
+static_assert(head_any_lds_bytes() > rgl::kLdsBytesWithoutAttribute, "launch_lds raises robot_head_any_kernel's attribute at every launch, as before");
 inline int head_any_grid(int n_tiles) {
     const int grid = (n_tiles + kAnyWaves - 1) / kAnyWaves;
-    return grid > 256 ? 256 : grid;
+    return grid > rgl::kCuCount ? rgl::kCuCount : grid;
 }
 
 }  // namespace
@@ -155,13 +151,7 @@ static int launch_stage2(const RglGraph* g, const RglMlp* h, const float* rows, 
         aa.value = value;
         aa.M = M;
         aa.n_tiles = head_tiles(M);
-        const size_t lds_bytes = head_any_lds_bytes();
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(robot_head_any_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        const int grid = head_any_grid(aa.n_tiles);
-        hipLaunchKernelGGL(robot_head_any_kernel, dim3(grid), dim3(kAnyWaves * 64), lds_bytes, stream, aa);
-        RGL_LAUNCH_CHECK();
-        return RGL_OK;
+        return rgl::launch_lds(robot_head_any_kernel, dim3(head_any_grid(aa.n_tiles)), dim3(kAnyWaves * 64), head_any_lds_bytes(), stream, aa);
     }
     HeadArgs ha;
     int chain = 0;

@@ -214,17 +214,6 @@ inline int head_variant(const RglMlp& h) {
     return 2;
 }
 
-inline bool fast_path_enabled() {
-    static const bool off = [] { const char* e = getenv("RGL_FORCE_GENERIC"); return e && e[0] == '1'; }();
-    return !off;
-}
-
-// RGL_CHILDREN_TILE_KERNEL=1 disables the shared-crowd kernels (rank-1, deep) in favour of the tile kernel (tests)
-inline bool rank1_enabled() {
-    static const bool off = [] { const char* e = getenv("RGL_CHILDREN_TILE_KERNEL"); return e && e[0] == '1'; }();
-    return !off;
-}
-
 // ReLU in the clamp bit of a packed FMA.  VOP3P has no packed f32 max, but every packed op can clamp its result to [0, 1] (DX10
 // clamp mode: NaN -> 0): on operands scaled by a power of two 2^-k the clamp IS the ReLU -- clamp01(2^-k x) = 2^-k relu(x) for
 // x < 2^k, and power-of-two scalings commute with the rounding of every product and sum (no overflow, and what underflows is

@@ -573,20 +573,14 @@ inline Rank1Plan plan_rank1(const RglGraph& g, int P, int A, int H) {
 
 // ---- the launch decisions, each made in ONE place: read by the launchers below and by rank1_children_form ------------------------
 // the grid: persistent, one 8-wave workgroup per CU striding the parents (b, b + grid, ..)
-inline int rank1_grid(int P) { return P < 256 ? P : 256; }
+inline int rank1_grid(int P) { return P < rgl::kCuCount ? P : rgl::kCuCount; }
 // the weights come from the packed image: the call has one and the LDS offsets coincide with its layout
 inline bool rank1_takes_image(const Rank1Plan& pl, bool image_at_hand) { return pl.image_layout && image_at_hand; }
 
 template <int HR, int NT, bool SKIP, bool SOFT>
 int launch_rank1_ts(const Rank1Plan& pl, hipStream_t st) {
     auto kern = children_rank1_kernel<HR, NT, SKIP, SOFT>;
-    if (pl.lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)pl.lds_bytes));
-    const int grid = rank1_grid(pl.a.P);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(pl.a.n_waves * 64), pl.lds_bytes, st, pl.a);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern, dim3(rank1_grid(pl.a.P)), dim3(pl.a.n_waves * 64), pl.lds_bytes, st, pl.a);
 }
 
 template <int HR, int NT, bool SKIP>

@@ -782,12 +782,6 @@ __global__ __launch_bounds__(kNarrowWaves * 64, 3) void mlp2_rows_kernel(const R
 namespace rgl {
 namespace tiles {
 
-// RGL_HEAD_ROWS_DIRECT (read once per process): 0 = the staged one-tile forms of mlp_rows_kernel instead of head_rows_kernel
-bool rows_direct() {
-    static const bool direct = [] { const char* e = getenv("RGL_HEAD_ROWS_DIRECT"); return !e || atoi(e) != 0; }();
-    return direct;
-}
-
 void plan_rows_job(RowsJob& J, const RglMlp& m, int n_rows, int max_waves) {
     J = RowsJob{};
     J.m = m;
@@ -892,13 +886,9 @@ static int launch_rows_kernel(K kernel, RowsArgs& ra, hipStream_t st) {
         ra.job[j].wg_begin = wgs;
         wgs += ra.job[j].n_wgs;
     }
-    if (lds > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     bool any_coop = false;
     for (int j = 0; j < ra.n_jobs; ++j) any_coop |= ra.job[j].coop != 0;
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(ra.job[0].kind >= 10 ? kNarrowWaves * 64 : (any_coop ? kCoopWaves * 64 : 256)), lds, st, ra);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kernel, dim3(wgs), dim3(ra.job[0].kind >= 10 ? kNarrowWaves * 64 : (any_coop ? kCoopWaves * 64 : 256)), lds, st, ra);
 }
 
 // The narrow jobs that share a launch (same kernel kind) get the same number of tiles per wave, chosen so that all their waves are

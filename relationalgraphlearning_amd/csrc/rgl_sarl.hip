@@ -14,8 +14,6 @@
 // CU's LDS holds for up to kSarlLdsHumans humans.  Above that the same slots live in a region of the workspace per workgroup (the
 // kernel's SarlValueGlobalArgs form); what bounds H is then gcn_prepare_f32's H + 1 <= RGL_MAX_NODES (RGL_SARL_MAX_HUMANS).  A
 // workgroup is one wave below kSarlWideFrom humans and four waves sharing one tile above.
-#include <cstring>
-
 #include "rgl_mfma.h"
 #include "rgl_onestep.h"
 #include "rgl_sarl_maps.h"
@@ -369,18 +367,12 @@ int launch_sarl_value_as(const SarlValueArgs& va, hipStream_t st) {
     auto kern = sarl_value_kernel<KT0, GLOBAL, WAVES>;
     const size_t lds = (size_t)va.H * kParkFloats * sizeof(float);
     if (lds > (size_t)rgl::kLdsBytesPerCu) return RGL_ERR_LDS;
-    if (lds > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // persistent: as many workgroups as the LDS lets a CU hold (at most 8 waves), each walking tiles grid apart
-    int per_cu = (int)((size_t)rgl::kLdsBytesPerCu / lds);
-    per_cu = per_cu > 8 / WAVES ? 8 / WAVES : per_cu;
-    int cap = 256 * per_cu;
-    const int asked = env_int("RGL_SARL_GRID_CAP", 0);     // tests: fewer workgroups, so that small launches walk several tiles too
+    int cap = rgl::kCuCount * rgl::workgroups_per_cu_by_lds(lds, 8 / WAVES);
+    const int asked = sarl_grid_cap_asked();     // tests: fewer workgroups, so that small launches walk several tiles too
     if (asked >= 1 && asked < cap) cap = asked;
     const int grid = va.n_tiles < cap ? va.n_tiles : cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, st, va);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern, dim3(grid), dim3(64 * WAVES), lds, st, va);
 }
 
 constexpr int kSarlLdsHumans = 20;      // humans whose slots a CU's LDS holds (148 KB of 160 KB); above, the slots live in the workspace
@@ -390,13 +382,12 @@ constexpr int kSarlGlobalPerCu = 2;     // workgroups of the global form per CU:
 // RGL_SARL_PARK=global (read per launch; tests): the global form at any H.  Anything else: LDS up to kSarlLdsHumans humans.
 inline bool sarl_parks_globally(int H) {
     if (H > kSarlLdsHumans) return true;
-    const char* e = getenv("RGL_SARL_PARK");
-    return e && !strcmp(e, "global");
+    return sarl_park_global();
 }
 
 inline int sarl_global_grid(long long n_tiles) {
-    int cap = 256 * kSarlGlobalPerCu;
-    const int asked = env_int("RGL_SARL_GRID_CAP", 0);
+    int cap = rgl::kCuCount * kSarlGlobalPerCu;
+    const int asked = sarl_grid_cap_asked();
     if (asked >= 1 && asked < cap) cap = asked;
     return n_tiles < cap ? (int)n_tiles : cap;
 }

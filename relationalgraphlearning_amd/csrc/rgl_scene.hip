@@ -180,15 +180,14 @@ inline int scene_node_tiles(int N) { return N > 64 ? 8 : (N + 15) / 16; }
 
 // Split scenes (NT waves per scene) below this many scenes: env RGL_SCENE_SPLIT_BELOW overrides (0 = never, tests / measurements)
 inline int scene_split_below(int nt) {
-    static const int env = [] { const char* e = getenv("RGL_SCENE_SPLIT_BELOW"); return e ? atoi(e) : -1; }();
+    const int env = scene_split_below_asked();
     if (env >= 0) return env;
     return nt == 2 ? 3072 : 4096;
 }
 
 // few scenes of the shipped shape: the scene kernel embeds its own node tiles (one launch for the level instead of two)
 inline bool scene_embeds_inside(const RglGraph& g, int NT0, int P, bool embed_children) {
-    static const bool emb_off = [] { const char* e = getenv("RGL_SCENE_EMBED_INSIDE"); return e && e[0] == '0'; }();
-    return !emb_off && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
+    return scene_embed_inside_enabled() && !embed_children && g.w_r.dims[0] == 9 && scene_similarity_mode(g) == SIM_SOFTMAX &&
            (NT0 == 1 || NT0 == 2 || NT0 == 4) && P <= 512 &&     // measured: +1.5-3 % up to 512 scenes, -2 % at 1-2 k (sibling scenes repeat their crowd's rows)
            (NT0 == 1 || P < scene_split_below(NT0));       // the split form (see launch_scene)
 }
@@ -197,7 +196,7 @@ inline bool scene_embeds_inside(const RglGraph& g, int NT0, int P, bool embed_ch
 // takes with the embeddings inside -- one per NT waves of its 8 (with the unsplit count a 50-agent scene workgroup held 95 KB instead
 // of 76: one per CU, and the launch's reward workgroups, which reserve the same LDS, waited for a scene workgroup to retire)
 inline int scene_region_slots(int NT, bool embed_inside) {
-    static const bool wide_slots = [] { const char* e = getenv("RGL_SCENE_WIDE_SLOTS"); return e && e[0] == '1'; }();      // measurements
+    const bool wide_slots = scene_wide_slots();      // measurements
     return (embed_inside && (NT == 2 || NT == 4) && !wide_slots) ? 8 / NT : (NT <= 2 ? 8 : (NT <= 4 ? 4 : 1));
 }
 
@@ -205,14 +204,14 @@ inline int scene_region_slots(int NT, bool embed_inside) {
 // workgroups: twice as many)
 constexpr int scene_slots(bool split, int waves, int nt) { return split ? waves / nt : waves; }
 inline int scene_grid_cap(size_t lds_bytes, int waves) {
-    return 256 * (lds_bytes * 2 <= (size_t)rgl::kLdsBytesPerCu ? 2 : 1) * (waves == 4 ? 2 : 1);
+    return rgl::kCuCount * rgl::workgroups_per_cu_by_lds(lds_bytes, 2) * (waves == 4 ? 2 : 1);
 }
 
 // the level's reward / next-state work rides in the scene kernel's launch below this many scenes (launch_predict_humans)
 // cross-over: ~3 k scenes for the f32 scene kernel (round 2), ~1.1 k once its weight products run on the matrix pipe (round 5:
 // 2048 roots 0.3022 -> 0.2988 ms, 1024 roots 0.1773 -> 0.1759, 512 roots unchanged); RGL_SCENE_CHILDREN_BELOW overrides (measurements)
 inline int scene_children_below(bool bf16x6) {
-    static const int below_env = [] { const char* e = getenv("RGL_SCENE_CHILDREN_BELOW"); return e ? atoi(e) : -1; }();
+    const int below_env = scene_children_below_asked();
     return below_env >= 0 ? below_env : (bf16x6 ? 1100 : 3072);
 }
 
@@ -246,12 +245,7 @@ int launch_scene_k(const SceneArgs& sa, size_t lds_bytes, const ChildrenArgs* ch
         grid_children = (int)(blocks < 2048 ? blocks : 2048);
     }
     auto kern = children ? scene_graph_kernel<NT, SK, WAVES, true, SPLIT, EMB, BX> : scene_graph_kernel<NT, SK, WAVES, false, SPLIT, EMB, BX>;
-    if (lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(grid + grid_children), dim3(WAVES * 64), lds_bytes, st, sa, ca, grid);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    return rgl::launch_lds(kern,dim3(grid + grid_children), dim3(WAVES * 64), lds_bytes, st, sa, ca, grid);
 }
 
 // 64 < N <= 128: eight column tiles, always split over the eight waves of a workgroup (one scene per workgroup pass; the

@@ -613,14 +613,9 @@ inline ChildPlan plan_children(const RglGraph& g, int P, int A, int H) {
 template <int KS, int MODE, bool VAGG, bool SKIP>
 int launch_children_skip(const ChildPlan& pl, hipStream_t st) {
     auto kern = children_graph_kernel<KS, MODE, VAGG, SKIP>;
-    if (pl.lds_bytes > 64 * 1024)
-        RGL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)pl.lds_bytes));
-    const int per_cu = pl.lds_bytes * 2 <= (size_t)rgl::kLdsBytesPerCu ? 2 : 1;
-    const int grid = pl.a.P < 256 * per_cu ? pl.a.P : 256 * per_cu;      // persistent: the weight image is built once
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(pl.a.n_waves * 64), pl.lds_bytes, st, pl.a);
-    RGL_LAUNCH_CHECK();
-    return RGL_OK;
+    const int slots = rgl::kCuCount * rgl::workgroups_per_cu_by_lds(pl.lds_bytes, 2);
+    const int grid = pl.a.P < slots ? pl.a.P : slots;      // persistent: the weight image is built once
+    return rgl::launch_lds(kern, dim3(grid), dim3(pl.a.n_waves * 64), pl.lds_bytes, st, pl.a);
 }
 
 template <int KS, int MODE, bool VAGG>

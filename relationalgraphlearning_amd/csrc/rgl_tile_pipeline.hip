@@ -297,7 +297,7 @@ static int backward_tiles(const RglGraph* graph, const RglMlp* vh, const RglMlp*
     // hold a scene in LDS (only_choice)
     const int mode = backward_mfma_mode();
     if (mode == 0) return RGL_OK;
-    if (mode < 1 && !only_choice && S < env_int("RGL_BACKWARD_MFMA_MIN", 256)) {
+    if (mode < 1 && !only_choice && S < backward_mfma_min()) {
         // Below the threshold the pipeline's device time is still the shorter one (84 vs 94 us at 100 scenes of 6 nodes, 95 vs 125 us
         // at 20 nodes), but it is seven launches instead of two and an eager training step is bound by the host.  While the stream
         // is being captured into a hipGraph only the device time counts.

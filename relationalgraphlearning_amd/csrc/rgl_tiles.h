@@ -74,7 +74,6 @@ struct GraphForm { int nt, xt, family; };       // family: 0 plain (norm 0-3), 1
 struct GraphPlan { int grid; size_t lds; int resident; };       // resident: the grid before min(S, .)
 
 // ---- the row kernels (rgl_rows.hip) ----
-bool rows_direct();
 void plan_rows_job(RowsJob& J, const RglMlp& m, int n_rows, int max_waves);
 size_t rows_job_lds(const RowsJob& J);
 void balance_narrow(RowsJob* const* jobs, int n, int max_waves);

@@ -189,7 +189,11 @@ def test_bounds_are_the_projects():
     src = open(ts.ROOT + "/tests/test_gpu_parity.py").read()
     got = {k: float(re.search(r"^%s = (\S+)" % k, src, flags=re.M).group(1)) for k in ("TOL", "REG_F32")}
     assert got == {"TOL": ts.TOL, "REG_F32": ts.REG_F32} == {"TOL": 1e-4, "REG_F32": 1e-6}
-    assert ts.FUSED_MIN_TILES == 1200 and "\"RGL_FUSED_MIN_TILES\", 1200" in open(ts.ROOT + "/relationalgraphlearning_amd/csrc/rgl_fused.hip").read()
+    # the threshold is the default of the library's switch table (csrc/rgl_switches.hip): what an unset RGL_FUSED_MIN_TILES parses to
+    lib, unset = nat.lib(), ctypes.c_int(-1)
+    row = [i for i in range(64) if lib.rgl_switch_name(i) == b"RGL_FUSED_MIN_TILES"]
+    assert len(row) == 1 and lib.rgl_switch_parse(row[0], None, ctypes.byref(unset)) == 0
+    assert ts.FUSED_MIN_TILES == 1200 == unset.value and "fused_min_tiles()" in open(ts.ROOT + "/relationalgraphlearning_amd/csrc/rgl_fused.hip").read()
     assert set(df.TABLES.items()) <= set(ts.TABLES.items())
 
 

@@ -997,6 +997,70 @@ int sarl_value_train_f32(const SarlPlanner* planner, const float* rows, int n_sc
 int sarl_value_backward_f32(const SarlPlanner* planner, const float* rows, const float* grad_value, int n_scenes, int H,
                             void* workspace, size_t workspace_bytes, const SarlGrads* grads, rgl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * LSTM-RL / OM-LSTM-RL (ABI 8, additive): the one-step search of MultiHumanRL.predict behind the distance sort of LstmRL.predict
+ * (crowd_nav/policy/lstm_rl.py:94-108) with the recurrent value networks of lstm_rl.py:9-69.  Evaluation only: there is no
+ * gradient call.
+ *
+ * Supported shapes -- every other request returns RGL_ERR_BAD_SHAPE / RGL_ERR_BAD_MODE before anything is launched:
+ *   lstm_hidden_dim 50; mlp 56-150-100-100-1; with_interaction_module: mlp1 D-150-100-100-50 (no ReLU after its last layer) in
+ *   front of nn.LSTM(50, 50) (ValueNetwork2), otherwise nn.LSTM(D, 50) on the rows themselves (ValueNetwork1);
+ *   D = 13 + cell_num^2 om_channel_size in {13, 29, 45, 61}; 2 <= H with maps, 1 <= H without, H <= RGL_SARL_MAX_HUMANS;
+ *   contraction_dtype RGL_CONTRACT_F32 only; n_scenes = B num_actions <= 2^26.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct LstmPlanner {
+    RglMlp mlp1;                            /* ValueNetwork2.mlp1; not read when with_interaction_module is 0           */
+    RglMlp mlp;                             /* the head on [six self features | h_n]                                    */
+    const float* weight_ih;                 /* device, torch's layout: lstm.weight_ih_l0 [200][50 | D], gate rows i f g o */
+    const float* weight_hh;                 /* device, lstm.weight_hh_l0 [200][50]                                      */
+    const float* bias_ih;                   /* device [200]                                                             */
+    const float* bias_hh;                   /* device [200]                                                             */
+    int with_interaction_module;
+    int lstm_hidden_dim;                    /* 50                                                                       */
+    int om_channel_size;                    /* 0: no occupancy maps; 1 | 2 | 3                                          */
+    int cell_num;
+    double cell_size;
+    int kinematics;
+    int num_actions;
+    int contraction_dtype;                  /* RGL_CONTRACT_F32                                                         */
+    int reserved;
+    double time_step;
+    double gamma;                           /* raw gamma; the discount is gamma^(time_step * v_pref)                    */
+    const double* actions;                  /* device [A][2]                                                            */
+} LstmPlanner;
+
+/* The value network for n_scenes sequences of H rows in one launch (plus one that lays the weights out as MFMA fragments in
+ * `workspace`, device, >= lstm_value_workspace_bytes(planner); 0 = outside the supported shapes; the size depends on neither
+ * n_scenes nor H: h and c stay in registers).  The LSTM runs over the rows of a scene in row order from h = c = 0, gates
+ * W_ih x + b_ih + W_hh h + b_hh in torch's order i, f, g, o; the value is the head on [row 0's first six features | h_n].  Input,
+ * either
+ *   rows   device [n_scenes][H][D] (the other three pointers are not read; scenes_per_root is taken as 1), or
+ *   self6  device [n_scenes][6], hum7 device [n_scenes][H][7] as gcn_prepare_f32 writes them, and (D > 13) maps device
+ *          [n_scenes / scenes_per_root][H][D - 13]: scene s reads the maps of root s / scenes_per_root.
+ * D must be the planner's 13 + cell_num^2 om_channel_size.  lengths: null (every scene runs H steps), or device [n_scenes] int32,
+ * each in 1..H -- NOT checked: scene s stops updating h and c after lengths[s] steps (pack_padded_sequence's hn).  The rows
+ * behind a scene's length are read and must be addressable; their content does not reach the value.  value device [n_scenes].
+ * The gate non-linearities saturate: no pre-activation produces NaN or Inf.  RGL_SARL_GRID_CAP caps the launch's grid (tests).
+ * Reads the two MLPs, the four LSTM tensors, with_interaction_module, lstm_hidden_dim, om_channel_size, cell_num and
+ * contraction_dtype of `planner`. */
+size_t lstm_value_workspace_bytes(const LstmPlanner* planner);
+int lstm_value_f32(const LstmPlanner* planner, const float* rows, const float* self6, const float* hum7, const float* maps,
+                   const int* lengths, int n_scenes, int H, int D, int scenes_per_root, void* workspace, size_t workspace_bytes,
+                   float* value, rgl_stream_t stream);
+
+/* The search for B roots.  One launch sorts every root's humans by DECREASING float64 distance sqrt(dx dx + dy dy) to the robot
+ * (every operation rounded on its own; from robot_f64 / humans_f64 when BOTH are given, else from the widened float32 rows), ties
+ * in their given order as python's sorted(.., reverse=True) leaves them.  On the sorted humans: gcn_prepare_f32, the maps (once per
+ * root), the value network over the B x A scenes, value = reward + gamma^(time_step v_pref) V in float64 and the strict `>` walk.
+ *   robot device [B][9], humans device [B][H][5]; robot_f64 [B][9] / humans_f64 [B][H][5] device float64, nullable: the states the
+ *   float32 arrays were rounded from; workspace device, >= lstm_predict_workspace_bytes(planner, B, H) (0: unsupported)
+ *   action_values device [B][A], best_action device [B] int32 (-1 where no value beats -inf), best_value device [B] (nullable; 0
+ *   where best_action = -1), order device [B][H] int32 (nullable): order[b][k] = the given index of the human at sorted place k. */
+size_t lstm_predict_workspace_bytes(const LstmPlanner* planner, int B, int H);
+int lstm_predict_f32(const LstmPlanner* planner, const float* robot, const float* humans, const double* robot_f64,
+                     const double* humans_f64, int B, int H, void* workspace, size_t workspace_bytes, float* action_values,
+                     int* best_action, float* best_value, int* order, rgl_stream_t stream);
+
 /* The library's RGL_* environment switches ("Environment switches"), host only (added within ABI 8): the name of
  * switch i (NULL past the end), and the value the library would read for it from `text_or_null` -- the variable's text, NULL when it
  * is unset.  Nothing is read from the environment; RGL_ERR_BAD_SHAPE: no such switch. */

@@ -87,6 +87,14 @@ class SarlPlanner(C.Structure):
                 ("actions", C.c_void_p), ("root_robot_f64", C.c_void_p), ("root_humans_f64", C.c_void_p)]
 
 
+class LstmPlanner(C.Structure):
+    _fields_ = [("mlp1", RglMlp), ("mlp", RglMlp), ("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p), ("bias_ih", C.c_void_p),
+                ("bias_hh", C.c_void_p), ("with_interaction_module", C.c_int), ("lstm_hidden_dim", C.c_int),
+                ("om_channel_size", C.c_int), ("cell_num", C.c_int), ("cell_size", C.c_double), ("kinematics", C.c_int),
+                ("num_actions", C.c_int), ("contraction_dtype", C.c_int), ("reserved", C.c_int), ("time_step", C.c_double),
+                ("gamma", C.c_double), ("actions", C.c_void_p)]
+
+
 SARL_LAYERS = 11
 
 
@@ -283,6 +291,12 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "sarl_value_backward_f32": (C.c_int, [C.POINTER(SarlPlanner), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                           C.POINTER(SarlGrads), C.c_void_p]),
+    "lstm_value_workspace_bytes": (C.c_size_t, [C.POINTER(LstmPlanner)]),
+    "lstm_value_f32": (C.c_int, [C.POINTER(LstmPlanner), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lstm_predict_workspace_bytes": (C.c_size_t, [C.POINTER(LstmPlanner), C.c_int, C.c_int]),
+    "lstm_predict_f32": (C.c_int, [C.POINTER(LstmPlanner), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rgl_switch_name": (C.c_char_p, [C.c_int]),
     "rgl_switch_parse": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     "rgl_abi_version": (C.c_int, []),
@@ -295,6 +309,7 @@ ADDITIVE = {"rgl_plan_prologue_embedding", "rgl_plan_deep_children", "rgl_plan_t
             "crowd_explore_seed_u32", "crowd_explore_select_f64", "crowd_step_nonstop_f64", "sarl_occupancy_maps_f32", "sarl_value_workspace_bytes",
             "sarl_value_f32", "sarl_predict_workspace_bytes", "sarl_predict_f32", "sarl_value_workspace_bytes_for",
             "sarl_train_workspace_bytes", "sarl_value_train_f32", "sarl_value_backward_f32", "rgl_replay_push_sarl_f32",
+            "lstm_value_workspace_bytes", "lstm_value_f32", "lstm_predict_workspace_bytes", "lstm_predict_f32",
             "rgl_switch_name", "rgl_switch_parse"}
 
 _lib = None

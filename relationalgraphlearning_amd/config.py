@@ -21,6 +21,8 @@ def policy_config(name="model_predictive_rl", **over):
                 similarity_function='embedded_gaussian', layerwise_graph=False, skip_connection=True)
     c.sarl = Bag(mlp1_dims=[150, 100], mlp2_dims=[100, 50], attention_dims=[100, 100, 1], mlp3_dims=[150, 100, 100, 1],
                  multiagent_training=True, with_om=True, with_global_state=True)       # config.py:94-101
+    c.lstm_rl = Bag(global_state_dim=50, mlp1_dims=[150, 100, 100, 50], mlp2_dims=[150, 100, 100, 1], multiagent_training=True,
+                    with_om=False, with_interaction_module=True)                        # config.py:80-86
     c.model_predictive_rl = Bag(linear_state_predictor=False, planning_depth=1, planning_width=1,
                                 do_action_clip=False, sparse_search=False, motion_predictor_dims=[64, 5],
                                 value_network_dims=[32, 100, 100, 1], share_graph_model=False)

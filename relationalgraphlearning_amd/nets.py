@@ -673,3 +673,100 @@ class SarlValueNetwork(nn.Module):
         # hipGraph cannot copy to the host: the row stays on the device until it is read
         self._attention = att[0] if torch.cuda.is_current_stream_capturing() else att[0].cpu().numpy()
         return value
+
+
+# --------------------------------------------------------------------------------------------------
+# LSTM-RL / OM-LSTM-RL module
+# --------------------------------------------------------------------------------------------------
+class LstmValueNetwork(nn.Module):
+    """lstm_rl.ValueNetwork1 / ValueNetwork2 (crowd_nav/policy/lstm_rl.py:9-69) as one module: `mlp1_dims` None is ValueNetwork1
+    (nn.LSTM on the rows), a list ValueNetwork2 (mlp1 in front of it).  The parameters live in a real nn.LSTM and `mlp` containers,
+    so upstream's state-dict keys load unchanged (mlp1.{0,2,4,6}, lstm.{weight,bias}_{ih,hh}_l0, mlp.{0,2,4,6}).  `forward(rows)` or
+    `forward((rows, lengths))` is lstm_value_f32; evaluation only -- a forward that would have to record a graph for autograd
+    raises, and there is no CPU path."""
+
+    def __init__(self, input_dim, self_state_dim, mlp1_dims, mlp_dims, lstm_hidden_dim):
+        super().__init__()
+        self.input_dim = input_dim
+        self.self_state_dim = self_state_dim
+        self.lstm_hidden_dim = lstm_hidden_dim
+        self.with_interaction_module = mlp1_dims is not None
+        if self.with_interaction_module:
+            self.mlp1 = mlp(input_dim, mlp1_dims)
+        self.lstm = nn.LSTM(mlp1_dims[-1] if self.with_interaction_module else input_dim, lstm_hidden_dim, batch_first=True)
+        self.mlp = mlp(self_state_dim + lstm_hidden_dim, mlp_dims)
+        self.cell_num, self.cell_size = 4, 1.0      # the geometry of the maps behind the 13 relation features; LstmRL.configure sets its own
+        self._cache = _PackCache()
+        self._ws = None
+
+    def _pack(self, keep, reuse=None):
+        mlp1 = pack_mlp(self.mlp1, keep, reuse) if self.with_interaction_module else nat.RglMlp()
+        head = pack_mlp(self.mlp, keep, reuse)
+        cell = [_require_device_tensor(getattr(self.lstm, name).detach(), "lstm." + name)
+                for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+        keep.extend(cell)
+        return mlp1, head, cell
+
+    def fill_planner(self, pl):
+        """The network's share of an LstmPlanner: the MLPs, the four LSTM tensors as torch keeps them, and the map shape the row
+        width implies."""
+        pl.mlp1, pl.mlp, cell = self._cache.get([self], self._pack)
+        pl.weight_ih, pl.weight_hh, pl.bias_ih, pl.bias_hh = [t.data_ptr() for t in cell]
+        pl.with_interaction_module = int(self.with_interaction_module)
+        pl.lstm_hidden_dim = int(self.lstm_hidden_dim)
+        extra = self.input_dim - 13
+        cells = int(self.cell_num) ** 2
+        pl.cell_num = int(self.cell_num)
+        pl.cell_size = float(self.cell_size)
+        pl.om_channel_size = extra // cells if extra > 0 and cells > 0 and extra % cells == 0 else (0 if extra == 0 else -1)
+        pl.contraction_dtype = nat.CONTRACTION_DTYPES["f32"]
+        return pl
+
+    def descriptor(self):
+        return self.fill_planner(nat.LstmPlanner())
+
+    def check_no_grad(self):
+        if _needs_grad(_flat_params(self)):
+            raise NotImplementedError("LSTM-RL training is not provided: the value network has no backward pass (no silent autograd, "
+                                      "no CPU path).  Evaluate under torch.no_grad() or freeze its parameters")
+
+    @staticmethod
+    def _check_lengths(lengths, S, H):
+        """Upstream's `lengths` (a CPU tensor or list, one per sequence): each in 1..H and non-increasing, as
+        pack_padded_sequence demands.  Returns them as a list of ints."""
+        seq = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else list(lengths))]
+        if len(seq) != S:
+            raise ValueError("lengths has %d entries for %d sequences" % (len(seq), S))
+        if any(v < 1 or v > H for v in seq):
+            raise ValueError("every length must be in 1..%d, got %s" % (H, seq))
+        if any(a < b for a, b in zip(seq, seq[1:])):
+            raise ValueError("lengths must be sorted in decreasing order (pack_padded_sequence), got %s" % (seq,))
+        return seq
+
+    def forward(self, state_input):
+        self.check_no_grad()
+        state, lengths = state_input if isinstance(state_input, tuple) else (state_input, None)
+        if not torch.is_tensor(state) or state.dim() != 3 or state.shape[2] != self.input_dim:
+            raise ValueError("LstmValueNetwork takes (batch, humans, %d) rows, got %s"
+                             % (self.input_dim, tuple(state.shape) if torch.is_tensor(state) else type(state)))
+        S, H = state.shape[0], state.shape[1]
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, S, H)
+        state = _require_device_tensor(state, "rotated joint states")
+        dev = state.device
+        with torch.cuda.device(dev):
+            pl = self.fill_planner(nat.LstmPlanner())
+            lib = nat.lib()
+            need = lib.lstm_value_workspace_bytes(C.byref(pl))
+            if need == 0:
+                raise nat.NativeLibraryError("lstm_value_f32: widths outside the shipped LSTM-RL shapes (%s)" % nat.ERRORS[-1])
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            if nat.poison_workspaces():
+                self._ws.fill_(255)     # tests: NaN bit patterns wherever the kernel reads what this call has not written
+            len_dev = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=dev)
+            value = torch.empty(S, 1, dtype=torch.float32, device=dev)
+            rc = lib.lstm_value_f32(C.byref(pl), state.data_ptr(), None, None, None, None if len_dev is None else len_dev.data_ptr(),
+                                    S, H, self.input_dim, 1, self._ws.data_ptr(), self._ws.numel(), value.data_ptr(), _stream())
+        nat.check(rc, "lstm_value_f32")
+        return value

@@ -4,9 +4,10 @@ Mirrors (reference paths): crowd_sim/envs/policy/policy.py:6-65 (`Policy`),
 crowd_nav/policy/model_predictive_rl.py:15-370 (`ModelPredictiveRL`), crowd_nav/policy/gcn.py:131-157 +
 multi_human_rl.py:12-112 + cadrl.py:70-138 (`GCN`), crowd_nav/policy/policy_factory.py:9-13 (registration),
 
-crowd_nav/policy/sarl.py:76-99 + multi_human_rl.py:12-171 (`SARL`; training after `enable_training()`).
+crowd_nav/policy/sarl.py:76-99 + multi_human_rl.py:12-171 (`SARL`; training after `enable_training()`),
+crowd_nav/policy/lstm_rl.py:72-108 (`LstmRL`; evaluation only).
 
-`register(policy_factory)` installs the classes under the reference's keys ('model_predictive_rl', 'gcn', 'sarl'),
+`register(policy_factory)` installs the classes under the reference's keys ('model_predictive_rl', 'gcn', 'sarl', 'lstm_rl'),
 so crowd_nav's train.py / test.py pick them up unchanged.
 """
 import logging
@@ -15,8 +16,8 @@ import numpy as np
 import torch
 
 from . import actions as act
-from .nets import RGL, ValueEstimator, StatePredictor, LinearStatePredictor, ValueNetwork, SarlValueNetwork
-from .rollout import TreeSearch, GcnSearch, SarlSearch, rotate, prepare_scenes, occupancy_maps
+from .nets import RGL, ValueEstimator, StatePredictor, LinearStatePredictor, ValueNetwork, SarlValueNetwork, LstmValueNetwork
+from .rollout import TreeSearch, GcnSearch, SarlSearch, LstmSearch, rotate, prepare_scenes, occupancy_maps
 
 
 class Policy(object):
@@ -618,7 +619,29 @@ class GCN(Policy):
         return rotate(joint, self.kinematics)
 
 
-class SARL(GCN):
+class _MapRows(object):
+    """The rows of the MultiHumanRL policies that may carry occupancy maps (SARL, LSTM-RL; multi_human_rl.py:98-171): the 13
+    relation features of every human and, with_om, its map behind them.  Mixed in before GCN."""
+
+    def input_dim(self):
+        return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
+
+    def build_occupancy_maps(self, human_states):
+        """(H, cell_num^2 om_channel_size) float32 device tensor: multi_human_rl.py:117-171 for a list of human states."""
+        rows = [[h.px, h.py, h.vx, h.vy, h.radius] for h in human_states]
+        if len(rows) < 2:
+            raise ValueError("need at least one array to concatenate")         # np.concatenate([]) upstream (:125-126)
+        h64 = torch.tensor([rows], dtype=torch.float64, device=self.device)
+        return occupancy_maps(h64, self.cell_num, self.cell_size, self.om_channel_size)[0]
+
+    def transform(self, state):
+        rotated = super().transform(state)
+        if self.with_om:
+            rotated = torch.cat([rotated, self.build_occupancy_maps(state.human_states)], dim=1)
+        return rotated
+
+
+class SARL(_MapRows, GCN):
     """SARL / OM-SARL (crowd_nav/policy/sarl.py:76-99 over multi_human_rl.py:12-171): path G's one-step lookahead -- propagate,
     rotate, reward, action table, greedy action for an empty crowd, all inherited from GCN -- with the attention value network and,
     with_om, the occupancy maps appended to every human's row.  `enable_training()` opts in to the value network's backward pass
@@ -647,9 +670,6 @@ class SARL(GCN):
             self.name = 'OM-SARL'
         self._search = None
         logging.info('Policy: {} {} global state'.format(self.name, 'w/' if sc.with_global_state else 'w/o'))
-
-    def input_dim(self):
-        return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
 
     def get_attention_weights(self):
         return self.attention_weights
@@ -691,19 +711,74 @@ class SARL(GCN):
             raise NotImplementedError("SARL with query_env=True is not provided")
         return super().predict_batch(robot, humans, roots_are_joint_states)
 
-    def build_occupancy_maps(self, human_states):
-        """(H, cell_num^2 om_channel_size) float32 device tensor: multi_human_rl.py:117-171 for a list of human states."""
-        rows = [[h.px, h.py, h.vx, h.vy, h.radius] for h in human_states]
-        if len(rows) < 2:
-            raise ValueError("need at least one array to concatenate")         # np.concatenate([]) upstream (:125-126)
-        h64 = torch.tensor([rows], dtype=torch.float64, device=self.device)
-        return occupancy_maps(h64, self.cell_num, self.cell_size, self.om_channel_size)[0]
 
-    def transform(self, state):
-        rotated = super().transform(state)
-        if self.with_om:
-            rotated = torch.cat([rotated, self.build_occupancy_maps(state.human_states)], dim=1)
-        return rotated
+
+class LstmRL(_MapRows, GCN):
+    """LSTM-RL / OM-LSTM-RL (crowd_nav/policy/lstm_rl.py:72-108 over multi_human_rl.py:12-171): path G's one-step lookahead with
+    the humans sorted by decreasing distance to the robot and the recurrent value network over them (ValueNetwork2 with the
+    interaction module, ValueNetwork1 without).  Evaluation only: the value network has no backward pass, VectorExplorer refuses to
+    store its replay rows, and query_env=True stays refused.  Upstream reads `state.self_state` in `predict`, a field JointState
+    does not have; it is read as `state.robot_state` here."""
+
+    def __init__(self):
+        super().__init__()
+        self.name = 'LSTM-RL'                                  # upstream keeps the name with maps, too
+        self.with_om = None
+        self.with_interaction_module = None
+        self.cell_num = None
+        self.cell_size = None
+        self.om_channel_size = None
+
+    def configure(self, config):
+        self.set_common_parameters(config)
+        self.cell_num = config.om.cell_num                     # cadrl.py:78-80
+        self.cell_size = config.om.cell_size
+        self.om_channel_size = config.om.om_channel_size
+        lc = config.lstm_rl
+        self.with_om = lc.with_om
+        self.multiagent_training = lc.multiagent_training
+        self.with_interaction_module = lc.with_interaction_module
+        self.model = LstmValueNetwork(self.input_dim(), self.self_state_dim, lc.mlp1_dims if lc.with_interaction_module else None,
+                                      lc.mlp2_dims, lc.global_state_dim)
+        self.model.cell_num, self.model.cell_size = self.cell_num, self.cell_size
+        self._search = None
+        logging.info('Policy: {}LSTM-RL {} pairwise interaction module'.format(
+            'OM-' if self.with_om else '', 'w/' if lc.with_interaction_module else 'w/o'))
+
+    def get_matrix_A(self):
+        raise AttributeError("LSTM-RL has no adjacency matrix")
+
+    def gcn_search(self):
+        key = (self.kinematics, self.time_step, self.gamma)
+        if self._search is None or self._search[0] != key:
+            self._search = (key, LstmSearch(self.model, act.as_array(self.action_space), self.kinematics, self.time_step, self.gamma))
+        return self._search[1]
+
+    def predict(self, state):
+        """lstm_rl.py:94-108: the humans sorted IN PLACE by decreasing distance to the robot (python's stable sort, numpy's norm),
+        then the inherited flow; the search's own sort then finds them in order."""
+        robot = state.robot_state
+
+        def dist(human):
+            return np.linalg.norm(np.array((human.px, human.py)) - np.array((robot.px, robot.py)))
+
+        state.human_states = sorted(state.human_states, key=dist, reverse=True)
+        return super().predict(state)
+
+    def _before_decision(self, crowd):
+        if crowd and self.query_env:
+            raise NotImplementedError("LSTM-RL with query_env=True is not provided: the maps and rewards of the search come from the "
+                                      "constant-velocity guess only")
+
+    def _refresh_adjacency(self, robot, humans):
+        pass                                                                # no graph, no adjacency: get_matrix_A refuses
+
+    def predict_batch(self, robot, humans, roots_are_joint_states=True):
+        """Additive API: robot (B,9), humans (B,H,5) device tensors in any order -> (action index (B,), its value (B,)); the sort
+        happens on the device and stays on the search as last_order (B,H)."""
+        if self.query_env:
+            raise NotImplementedError("LSTM-RL with query_env=True is not provided")
+        return super().predict_batch(robot, humans, roots_are_joint_states)
 
 
 def _first_strict_maximum(vals):
@@ -722,4 +797,5 @@ def register(policy_factory):
     policy_factory['model_predictive_rl'] = ModelPredictiveRL
     policy_factory['gcn'] = GCN
     policy_factory['sarl'] = SARL
+    policy_factory['lstm_rl'] = LstmRL
     return policy_factory

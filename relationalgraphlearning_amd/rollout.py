@@ -558,6 +558,52 @@ class SarlSearch(_OneStepSearch):
         return vals, best
 
 
+class LstmSearch(_OneStepSearch):
+    """One-step lookahead over the rotation-major action table with the LSTM-RL / OM-LSTM-RL value network (lstm_predict_f32:
+    the humans of every root sorted by decreasing distance to the robot as LstmRL.predict does, lstm_rl.py:94-108, then
+    multi_human_rl.py:36-64 with the recurrent networks of lstm_rl.py:9-69 and, with maps, the occupancy maps of :117-171)."""
+
+    def __init__(self, value_network, actions, kinematics="holonomic", time_step=0.25, gamma=0.9, contraction_dtype="f32"):
+        if contraction_dtype != "f32":
+            raise ValueError("LSTM-RL contraction mode %r: only 'f32' (the reference's arithmetic) is offered" % (contraction_dtype,))
+        super().__init__(value_network, actions, kinematics, time_step, gamma)
+        self.last_order = None
+
+    def planner(self, dev, H, B=None):
+        return self._fill_search(self.model.fill_planner(nat.LstmPlanner()), dev, B, H, None)
+
+    def search(self, robot, humans, roots64=None):
+        """robot (B,9), humans (B,H,5) in any order -> (action_values (B,A) fp32, best_action (B,) int32), device tensors; the
+        selected action's value is kept as last_best_value (B,), the sort as last_order (B,H) int32: last_order[b, k] is the given
+        index of the human the search put at place k."""
+        if self.model.input_dim > 13 and humans.shape[1] < 2:
+            # upstream: np.concatenate of an empty list (multi_human_rl.py:125-126) -- on the host, before anything is launched
+            raise ValueError("need at least one array to concatenate: occupancy maps of a single human have no other humans")
+        robot = _require_device_tensor(robot, "robot states")
+        humans = _require_device_tensor(humans, "human states")
+        B, H, dev = robot.shape[0], humans.shape[1], robot.device
+        r64 = h64 = None
+        if roots64 is not None:
+            r64, h64 = _check_roots64(roots64, B, H)
+        with torch.cuda.device(dev):
+            pl = self.planner(dev, H, B)
+            lib = nat.lib()
+            need = lib.lstm_predict_workspace_bytes(C.byref(pl), B, H)
+            if need == 0:
+                nat.check(-1, "lstm_predict_f32 (H = %d of at most %d; the widths and map sizes of the shipped shapes)"
+                          % (H, nat.SARL_MAX_HUMANS))
+            ws = self._ws.get(need, dev)
+            vals, best, best_value = self._outputs(B, dev)
+            order = torch.empty(B, H, dtype=torch.int32, device=dev)
+            rc = lib.lstm_predict_f32(C.byref(pl), robot.data_ptr(), humans.data_ptr(), None if r64 is None else r64.data_ptr(),
+                                      None if h64 is None else h64.data_ptr(), B, H, ws.data_ptr(), ws.numel(), vals.data_ptr(),
+                                      best.data_ptr(), best_value.data_ptr(), order.data_ptr(), _stream())
+        nat.check(rc, "lstm_predict_f32")
+        self.last_best_value = best_value
+        self.last_order = order
+        return vals, best
+
+
 def occupancy_maps(humans64, cell_num=4, cell_size=1.0, om_channel_size=3, time_step=0.0):
     """sarl_occupancy_maps_f32: humans (B,H,5) float64 device tensor -> maps (B,H,cell_num^2 om_channel_size) float32 of the states
     moved on by `time_step` at constant velocity (MultiHumanRL.build_occupancy_maps, multi_human_rl.py:117-171).  A float32 tensor

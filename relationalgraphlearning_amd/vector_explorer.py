@@ -548,6 +548,10 @@ class VectorExplorer(object):
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None, epoch=None,
                        print_failure=False):
+        if update_memory and getattr(self.target_policy, "name", None) == "LSTM-RL":
+            # evaluation only: the recurrent value network has no backward pass, and nothing fills a memory with its sorted rows
+            raise NotImplementedError("LSTM-RL training is not provided: the replay memory does not store LSTM-RL's sorted rows and "
+                                      "the value network has no backward pass")
         if update_memory and self._sarl_target():
             if not self.target_policy.training_enabled():
                 # opt-in, like the network's backward pass: SARL's replay rows carry the occupancy maps behind the 13 relation features
